@@ -10,7 +10,11 @@ its env's action touches from the packed tableau in device memory, applies the g
 solved test, writes reward / done / success / depth and the touched rows back.  Inputs (actions) are
 resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps (`ms_per_step`), writes the last step's outputs when --dump-outputs is
+given, and prints the line.  Everything else -- the CPU baseline, the oracle replay of the timed run, the roofline clocks,
+the legs of bench_legs.py and (N > 1) the collective cadences -- runs with --full only.
 
 N > 1: one rank per GPU; the data path is libqgym's own communicator (qg_comm_* of include/qgym.h: ncclAllGather of librccl.so.1
 called from C++, and the direct write into the peers' windows over xGMI) -- torch.distributed (gloo, CPU) only carries the control
@@ -82,11 +86,44 @@ def launch_ranks(n: int, argv) -> int:
     return 0
 
 
+DUMP_ENVS = 65536        # --dump-outputs: envs whose per-env outputs are written (all of them at the metric's batch size)
+DUMP_DENSE_ENVS = 4096   # ... and whose dense observation is written (16 MiB in float32)
+
+
+def dump_outputs(env, stream, out_dir: str):
+    """--dump-outputs: what env.step() hands its caller after the last timed step, as DIR/<name>.npy in float32 / float64 (exact for every
+    value), about 35 MB at any batch size: reward, done (is_final), success, depth and the bit-packed observation words (observe_packed) of
+    every env, or of a fixed seeded sample of DUMP_ENVS envs in larger batches; the dense observation (observe) of a fixed seeded sample of
+    DUMP_DENSE_ENVS envs.  The same arguments give the same inputs, so two builds can be compared file by file."""
+    B = env.batch
+    rows = np.arange(B) if B <= DUMP_ENVS else np.sort(np.random.default_rng(0).choice(B, DUMP_ENVS, replace=False))
+    dense_rows = np.sort(np.random.default_rng(1).choice(B, min(B, DUMP_DENSE_ENVS), replace=False))
+    with torch.cuda.stream(stream):
+        r, dr = torch.as_tensor(rows, device=env.device), torch.as_tensor(dense_rows, device=env.device)
+        arrays = {
+            "reward": env.reward[r].cpu().numpy().astype(np.float32),
+            "done": env.done[r].cpu().numpy().astype(np.float32),
+            "success": env.success[r].cpu().numpy().astype(np.float32),
+            "depth": env.depth[r].cpu().numpy().astype(np.float64),
+            "obs_packed": env.observe_packed()[r].cpu().numpy().view(np.uint32).astype(np.float64),
+            "obs_dense_sample": env.observe()[dr].cpu().numpy().astype(np.float32),
+        }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2048)
     ap.add_argument("--warmup", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (CPU baseline, oracle replay, roofline clocks, the bench_legs.py legs, "
+                         "N > 1 collective cadences); the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="rank 0: after the timed steps, write what the last step computed (reward, is_final, success, depth, packed observation; "
+                         "the dense observation of a fixed sample of envs) as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the CPU-oracle replay of the timed run")
     ap.add_argument("--no-large-batch", action="store_true", help="skip the 2^18 / 2^20 / 2^22-env legs (profiling runs: keeps the kernel statistics to one batch size)")
@@ -299,22 +336,25 @@ def main():
     else:
         run_steps = issue
 
-    def timed_region():
-        """EXACTLY K steps between two device-wide synchronisations (the caller has synchronised before): wall clock + HIP events on the launch stream."""
+    def timed_region(nsteps: int = K):
+        """EXACTLY nsteps (K) steps between two device-wide synchronisations (the caller has synchronised before): wall clock + HIP events on the launch stream."""
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t_start = time.perf_counter()
         with torch.cuda.stream(stream):
             e0.record(stream)
-            run_steps(K)
+            run_steps(nsteps)
             e1.record(stream)
         torch.cuda.synchronize()
         return time.perf_counter() - t_start, e0, e1
 
+    # one step of each launch shape the timed region uses (a CHUNK-launch graph, the remainder's graph or eager step) in the order it uses
+    # them, not K steps: the setup costs the same at any --steps (N > 1: the gather segments cut the chunks, so all K)
+    shape_steps = K if multi or K <= 2 * CHUNK else CHUNK + K % CHUNK
     with torch.cuda.stream(stream):
         env.reset(seed)
-        run_steps(K)  # builds and caches every graph the timed region replays (setup, not a step)
+        run_steps(shape_steps)  # builds and caches every graph the timed region replays (setup, not a step)
     torch.cuda.synchronize()
-    timed_region()  # dress rehearsal (setup): the first pass through this host code and the graph's second launch pay one-time costs
+    timed_region(shape_steps)  # dress rehearsal (setup): the first pass through this host code and the graph's second launch pay one-time costs
     with torch.cuda.stream(stream):
         if W:
             run_steps(W)
@@ -335,6 +375,8 @@ def main():
     torch.cuda.synchronize()
     gathers_before = gather_log["submitted"]
     elapsed, ev0, ev1 = timed_region()
+    if args.dump_outputs and rank == 0:  # before anything else steps the env
+        dump_outputs(env, stream, args.dump_outputs)
     if args.diag_repeat:  # diagnostics only: the same timed region again, to tell one-shot effects from steady state
         for _ in range(args.diag_repeat):
             td = time.perf_counter()
@@ -357,7 +399,7 @@ def main():
     snap = gshard = None
     ids = np.arange(B)
     idx = torch.as_tensor(ids, device=dev)
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         with torch.cuda.stream(stream):
             snap = {
                 "obs": env.observe()[idx].cpu().numpy(),
@@ -368,7 +410,7 @@ def main():
             }
         snap_trace = list(ring_trace)
     snap_actions = host_actions[:, ids].numpy()
-    if multi and rank == 0 and not args.no_gather and gatherer.latest() is not None:
+    if multi and rank == 0 and not args.no_gather and (args.full or args.dump_gathered) and gatherer.latest() is not None:
         # this rank's own part of the last all-gathered buffer, as the learner would read it
         g_obs, g_rew, g_done, g_succ = split_gathered(gatherer.latest(), layout, world, 4)
         lo = rank * B
@@ -394,7 +436,7 @@ def main():
             comm.check()  # a peer that missed a deadline during the run is an error, not a slow number
 
     def collective_cadences():
-        if not (multi and not args.no_gather and args.handover == "rccl"):
+        if not (args.full and multi and not args.no_gather and args.handover == "rccl"):
             return None
 
         def timed(fn, reps):
@@ -488,52 +530,56 @@ def main():
     # ---- roofline leg: duration of the step kernel, HIP events on the stream the kernel is launched on --------
     # (1) the timed region itself: events around the K timed launches (what `achieved` uses)
     timed_region_us = stream_ms * 1e3 / K
-    # (2) steady-state launch period inside one hipGraph of CHUNK launches (no host in the loop)
-    with torch.cuda.stream(stream):
-        env.rollout_ring(actions, CHUNK)
+    graph_period_us = eager_event_us = device_clock_us = kdurs = None  # plain run: the clocks below are --full figures
+    if args.full:
+        # (2) steady-state launch period inside one hipGraph of CHUNK launches (no host in the loop)
+        with torch.cuda.stream(stream):
+            env.rollout_ring(actions, CHUNK)
+            torch.cuda.synchronize()
+            g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            g0.record(stream)
+            for _ in range(4):
+                env.rollout_ring(actions, CHUNK)
+            g1.record(stream)
         torch.cuda.synchronize()
-        g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        g0.record(stream)
-        for _ in range(4):
-            env.rollout_ring(actions, CHUNK)
-        g1.record(stream)
-    torch.cuda.synchronize()
-    graph_period_us = g0.elapsed_time(g1) * 1e3 / (4 * CHUNK)
-    # (3) one eager launch between two events
-    reps = 200
-    starts = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-    stops = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
-    with torch.cuda.stream(stream):
-        for i in range(reps):
-            starts[i].record(stream)
-            env.step(actions[i % RING])
-            stops[i].record(stream)
-    torch.cuda.synchronize()
-    eager_event_us = float(np.median(sorted(s.elapsed_time(e) * 1e3 for s, e in zip(starts, stops))))
-    # (4) the kernel's own clock (qg_vec_set_kernel_clock): every wave stamps its entry and -- after waiting for its loads and stores -- its exit on
-    # the device's constant-rate counter; a launch's duration = last exit - first entry.  No host, no profiler, no launch boundary: this is the
-    # duration roofline.achieved divides by.  One slot per launch of a CHUNK-launch graph, four replays.
-    kslots = env.kernel_clock(CHUNK)
-    kdurs = []
-    with torch.cuda.stream(stream):
-        env.rollout_ring(actions, CHUNK)  # a fresh graph: its launches carry their slots
-        for _ in range(4):
-            torch.cuda.synchronize()
-            kslots.zero_()
-            torch.cuda.synchronize()
-            env.rollout_ring(actions, CHUNK)
-            torch.cuda.synchronize()
-            kdurs.append(env.kernel_durations_us(kslots))
-    env.kernel_clock(0)
-    kdurs = np.concatenate(kdurs)
-    if kdurs.size != 4 * CHUNK:
-        raise SystemExit(f"bench.py: {kdurs.size} of {4 * CHUNK} step launches stamped the kernel clock")
-    device_clock_us = float(kdurs.mean())
+        graph_period_us = g0.elapsed_time(g1) * 1e3 / (4 * CHUNK)
+        # (3) one eager launch between two events
+        reps = 200
+        starts = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
+        stops = [torch.cuda.Event(enable_timing=True) for _ in range(reps)]
+        with torch.cuda.stream(stream):
+            for i in range(reps):
+                starts[i].record(stream)
+                env.step(actions[i % RING])
+                stops[i].record(stream)
+        torch.cuda.synchronize()
+        eager_event_us = float(np.median(sorted(s.elapsed_time(e) * 1e3 for s, e in zip(starts, stops))))
+        # (4) the kernel's own clock (qg_vec_set_kernel_clock): every wave stamps its entry and -- after waiting for its loads and stores -- its exit on
+        # the device's constant-rate counter; a launch's duration = last exit - first entry.  No host, no profiler, no launch boundary: this is the
+        # duration roofline.achieved divides by.  One slot per launch of a CHUNK-launch graph, four replays.
+        kslots = env.kernel_clock(CHUNK)
+        kdurs = []
+        with torch.cuda.stream(stream):
+            env.rollout_ring(actions, CHUNK)  # a fresh graph: its launches carry their slots
+            for _ in range(4):
+                torch.cuda.synchronize()
+                kslots.zero_()
+                torch.cuda.synchronize()
+                env.rollout_ring(actions, CHUNK)
+                torch.cuda.synchronize()
+                kdurs.append(env.kernel_durations_us(kslots))
+        env.kernel_clock(0)
+        kdurs = np.concatenate(kdurs)
+        if kdurs.size != 4 * CHUNK:
+            raise SystemExit(f"bench.py: {kdurs.size} of {4 * CHUNK} step launches stamped the kernel clock")
+        device_clock_us = float(kdurs.mean())
     algo_bytes = ALGO_BYTES_PER_STEP * B
     needed_bytes = NEEDED_BYTES_PER_STEP * B
-    achieved = algo_bytes / (device_clock_us * 1e-6) / 1e9
-    rocprof = rocprof_kernel_avg_us(B)  # the committed rocprofv3 summary of this command: reported beside the live clock, never required
-    traffic = pmc_traffic(B)
+    achieved = rocprof = traffic = None
+    if args.full:
+        achieved = algo_bytes / (device_clock_us * 1e-6) / 1e9
+        rocprof = rocprof_kernel_avg_us(B)  # the committed rocprofv3 summary of this command: reported beside the live clock, never required
+        traffic = pmc_traffic(B)
 
     # ---- the legs beside the headline (bench_legs.py; N = 1 at the metric's batch size) --------
     import bench_legs
@@ -541,17 +587,19 @@ def main():
 
     ctx = SimpleNamespace(multi=multi, B=B, args=args, VecEnv=VecEnv, n=n, gateset=gateset, A=A, dev=dev, gen=gen, stream=stream, seed=seed, actions=actions,
                           host_actions=host_actions, env_base=env_base, rank=rank, env=env)
-    fused = bench_legs.fused_rollout(ctx)
-    default_cfg = bench_legs.default_config(ctx)
-    auto_reset = bench_legs.auto_reset(ctx)
-    obs_modes = bench_legs.observation_modes(ctx)
-    configs = bench_legs.other_configs(ctx)
-    large = bench_legs.large_batch(ctx)
-    collector = bench_legs.policy_in_loop(ctx)
+    fused = default_cfg = auto_reset = obs_modes = configs = large = collector = None
+    if args.full:
+        fused = bench_legs.fused_rollout(ctx)
+        default_cfg = bench_legs.default_config(ctx)
+        auto_reset = bench_legs.auto_reset(ctx)
+        obs_modes = bench_legs.observation_modes(ctx)
+        configs = bench_legs.other_configs(ctx)
+        large = bench_legs.large_batch(ctx)
+        collector = bench_legs.policy_in_loop(ctx)
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and not args.force_multi:  # the CPU leg runs at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.force_multi:  # the CPU leg runs at N = 1 only
             cpu = cpu_baseline(gateset, seed)
         parity = None
         if snap is not None:
@@ -624,7 +672,7 @@ def main():
                     "collectives_in_timed_region": gathers_timed,
                 },
             },
-            "roofline": {
+            "roofline": None if not args.full else {
                 "bound": "hbm",
                 "kernel": KERNEL,
                 "kernel_resources": "256 threads/block, 1 wave/SIMD at 65 536 envs; no LDS; thread per env",
@@ -678,7 +726,7 @@ def main():
         # the figures of the legs above once more, compact and LAST in the line: whoever keeps only the line's tail still has them
         out["summary"] = {
             "us_per_step": r2(elapsed * 1e6 / K), "launch_period_us": r2(timed_region_us), "kernel_us_device_clock": r2(device_clock_us),
-            "roofline_frac": round(achieved / HBM_PEAK_GBS, 3), "parity_envs": parity["envs"] if parity else None,
+            "roofline_frac": round(achieved / HBM_PEAK_GBS, 3) if achieved else None, "parity_envs": parity["envs"] if parity else None,
             "cpu_env_steps_per_s": cpu["value"] if cpu else None, "cpu_cores": cpu["cores"] if cpu else None,
             "default_config_us": r2(default_cfg["us_per_step"]) if default_cfg else None,
             "auto_reset_us_per_pair": None if not auto_reset else {

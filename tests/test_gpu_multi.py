@@ -75,7 +75,7 @@ def test_bench_rccl_path_gathered_shard_3_of_8_matches_oracle(tmp_path):
     rank 3 of 8, i.e. env ids [196 608, 262 144).  The gathered packed observation, rewards and flags of every env of the shard are
     replayed here on the oracle, independently of bench.py's own check."""
     dump = str(tmp_path / "gathered.npz")
-    res = _run_bench("--force-multi", "--shard", "3/8", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-large-batch",
+    res = _run_bench("--full", "--force-multi", "--shard", "3/8", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-large-batch",
                      "--no-default-config", "--dump-gathered", dump)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')][-1])
@@ -109,7 +109,7 @@ def test_bench_rccl_path_gathered_shard_3_of_8_matches_oracle(tmp_path):
 def test_bench_line_survives_a_failed_direct_write_leg():
     """The optional direct-write cadence leg fails on this rank (its hipIpcOpenMemHandle, injected): the line still goes out, complete, with
     the RCCL cadences measured and `direct_write: {error: ...}` naming the phase."""
-    res = _run_bench("--force-multi", "--shard", "3/8", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-large-batch",
+    res = _run_bench("--full", "--force-multi", "--shard", "3/8", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-large-batch",
                      "--no-default-config", "--no-configs", "--no-collector", "--no-dense-obs", "--inject-p2p-open-failure", "0")
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')][-1])
@@ -176,7 +176,7 @@ def test_bench_as_a_two_rank_job_on_one_gpu_with_the_direct_write_handover():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--handover", "direct", "--ranks-share-gpu0", "--steps", "20",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--handover", "direct", "--ranks-share-gpu0", "--steps", "20",
                           "--warmup", "5", "--no-cpu-baseline", "--no-large-batch", "--no-default-config", "--no-configs", "--no-collector"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -200,7 +200,7 @@ def test_bench_as_a_four_rank_job_on_one_gpu_every_window_offset_and_flag():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--handover", "direct", "--ranks-share-gpu0", "--envs", "8192",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--handover", "direct", "--ranks-share-gpu0", "--envs", "8192",
                           "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-large-batch", "--no-default-config", "--no-configs", "--no-collector",
                           "--no-dense-obs"], capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]

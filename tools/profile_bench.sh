@@ -15,7 +15,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/qg_prof && mkdir -p /tmp/qg_prof
 PART="${PART:-all}"   # A: the bench.py command and the configurations; B: dense observation, auto-reset, clocks, the bench lines (needs A's files); all: both
-BENCH_ARGS="--gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-large-batch --no-default-config --no-configs --no-collector --no-dense-obs --profiling-run"
+BENCH_ARGS="--full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-large-batch --no-default-config --no-configs --no-collector --no-dense-obs --profiling-run"
 pmc_pass() {  # name, counter, script args...
     local name="$1" counter="$2"; shift 2
     rocprofv3 --pmc "$counter" --kernel-trace -d "/tmp/qg_prof/${name}_$counter" -o pmc --output-format csv -- python3 "$@" > "$OUT/pmc_${name}_$counter.log" 2>&1
@@ -35,7 +35,7 @@ rocprofv3 --kernel-trace --stats -d /tmp/qg_prof/stats -o bench --output-format 
 cp /tmp/qg_prof/stats/*kernel_stats.csv "$OUT/bench_kernel_stats.csv" 2>/dev/null
 for C in FETCH_SIZE WRITE_SIZE; do
     echo "== bench.py pmc $C" && date
-    pmc_pass bench $C "$ROOT/bench.py" --gpus 1 --steps 512 --warmup 64 --no-cpu-baseline --no-parity --no-large-batch --no-default-config --no-configs --no-collector --no-dense-obs --profiling-run
+    pmc_pass bench $C "$ROOT/bench.py" --full --gpus 1 --steps 512 --warmup 64 --no-cpu-baseline --no-parity --no-large-batch --no-default-config --no-configs --no-collector --no-dense-obs --profiling-run
 done
 for CFG in "C2" "C5" "C3d" "C3 --envs 1048576" "C3 --envs 4194304" "C5 --envs 1048576" "C5 --envs 4194304" "C3d --envs 4194304"; do
     set -- $CFG
@@ -82,10 +82,10 @@ mkdir -p "$ROOT/profiles/$ROUND" && cp "$OUT/$ROUND/"* "$ROOT/profiles/$ROUND/" 
 echo "== the kernel device clock beside the rocprofv3 averages made above" && date
 python3 "$ROOT/tools/kernel_device_clock.py" --out "$OUT/$ROUND/kernel_device_clock" --profile-dir "$OUT/$ROUND" > "$OUT/kernel_device_clock.log" 2>&1
 cp "$OUT/$ROUND/kernel_device_clock."* "$ROOT/profiles/$ROUND/" 2>/dev/null
-echo "== bench.py plain (reads the summaries made above)" && date
-cd "$ROOT" && python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/$ROUND/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
-cd "$ROOT" && python3 bench.py > "$OUT/$ROUND/bench_n1.json" 2> "$OUT/bench_n1.err"
+echo "== bench.py --full (reads the summaries made above)" && date
+cd "$ROOT" && python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/$ROUND/bench_driver_args.json" 2> "$OUT/bench_driver_args.err"
+cd "$ROOT" && python3 bench.py --full > "$OUT/$ROUND/bench_n1.json" 2> "$OUT/bench_n1.err"
 echo "== the multi-GPU code path on one rank (qg_comm: RCCL + direct write cadences)" && date
-cd "$ROOT" && python3 bench.py --force-multi --shard 3/8 --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-default-config --no-configs --no-collector > "$OUT/$ROUND/bench_force_multi_rank3of8.json" 2> "$OUT/bench_force_multi.err"
-cd "$ROOT" && python3 bench.py --gpus 2 --handover direct --ranks-share-gpu0 --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-default-config --no-configs --no-collector > "$OUT/$ROUND/bench_two_ranks_one_gpu_direct.json" 2> "$OUT/bench_two_ranks.err"
+cd "$ROOT" && python3 bench.py --full --force-multi --shard 3/8 --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-default-config --no-configs --no-collector > "$OUT/$ROUND/bench_force_multi_rank3of8.json" 2> "$OUT/bench_force_multi.err"
+cd "$ROOT" && python3 bench.py --full --gpus 2 --handover direct --ranks-share-gpu0 --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-default-config --no-configs --no-collector > "$OUT/$ROUND/bench_two_ranks_one_gpu_direct.json" 2> "$OUT/bench_two_ranks.err"
 ls -la "$OUT" "$OUT/$ROUND"
