@@ -2093,9 +2093,9 @@ int ptile_reset_seeded(qg_vec *v, uint64_t seed, bool only_done, hipStream_t s, 
     ga.depth_value = (int32_t)std::min<int64_t>(d, v->cfg.max_depth);
     ga.only_done = only_done ? 1u : 0u;
     if (only_done && from_mask && v->done_mask[0]) {  // the step before left its finishers as bits: no compaction launch
-        ga.mask = v->done_mask[v->mask_cur];
-        ga.mask_words = (uint32_t)(4 * ((v->B + 255) / 256));
-        ga.mask_epoch = v->mask_epoch[v->mask_cur];
+        ga.mask = v->done_mask[v->dl.cur()];
+        ga.mask_words = (uint32_t)done_mask_words(v->B);
+        ga.mask_epoch = v->dl.epoch();
         ga.count_pub = v->mask_count;
         ga.tree = (ga.difficulty >= plan::TREE_MIN_DRAWS && v->B / 32u >= 1u && pauli_tree_takes(1u, ga.difficulty, v->B, ga.n_cx)) ? 1u : 0u;
     } else if (only_done && v->done_list && v->B > QG_COMPACT_MIN_ENVS) {  // pack the finished envs: full waves instead of one live lane in every wave

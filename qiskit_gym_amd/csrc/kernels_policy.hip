@@ -1774,11 +1774,10 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
     const bool small = mid_head_is_small(batch, in_features, cus);
     // the finished envs' indices are appended to the handle's list, unless the small kernel resets them itself
     const bool reset_in_kernel = small && step_of && reset_seed;
-    bool trusted = false;
-    if (step_of) trusted = done_list_session(step_of, s);
-    if (reset_in_kernel) fill_reset_done_args_public(step_of, *reset_seed, m.reset);
+    const bool trusted = step_of && step_of->dl.enter(session_of(s));
+    if (reset_in_kernel) fill_reset_done_args(step_of, *reset_seed, m.reset);
     else if (step_of)  // the kernel appends the envs it finishes: the list's length is zero when it starts
-        if (int rc = done_list_before_append(step_of, s)) return rc;
+        if (int rc = zero_list_length(step_of, step_of->done_list, step_of->dl.before_append(), s)) return rc;
     if (small) {
         const dim3 grid((unsigned)env_tiles), block(64 * MHS_WAVES);
 #define QG_MHS_CASE(TT)                                                        \
@@ -1789,7 +1788,7 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
         }
 #undef QG_MHS_CASE
         HIP_TRY(hipGetLastError());
-        if (step_of && !reset_in_kernel) done_list_appended(step_of, trusted);
+        if (step_of && !reset_in_kernel) step_of->dl.appended(trusted);
         return QG_OK;
     }
     // two tiles per wave (one workgroup of 256 envs per CU) once the batch gives every CU such a workgroup; below that, one tile per wave, two
@@ -1814,7 +1813,7 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
     }
 #undef QG_MH_CASE
     HIP_TRY(hipGetLastError());
-    if (step_of) done_list_appended(step_of, trusted);
+    if (step_of) step_of->dl.appended(trusted);
     return QG_OK;
 }
 

@@ -240,75 +240,8 @@ static int vec_free_buffers(qg_vec *v) {
 
 static int ensure_scratch(qg_vec *v, size_t bytes) { return qg::ensure_scratch_public(v, bytes); }
 
-}  // extern "C"
-namespace qg {
-// ---- the list of finished envs (done_list: [B] indices, then {length, reader ticket}) --------------------------------------------
-// Device-side facts: a LIST step kernel (and the sampling + step kernels) APPENDS to the list, so the length must be zero when it
-// starts; the reset kernel that consumes a list zeroes the length again (list_count_take); compact_done zeroes it itself.  What the
-// host knows about the length is exact only for launches it has enqueued eagerly, in order: anything captured into a caller's graph
-// runs later, any number of times, between whatever else the caller enqueues.  So the host's belief (done_list_fresh, list_zero_known)
-// is scoped to a SESSION -- one stream capture (its capture id), or eager execution on a handle none of whose list launches were
-// ever captured:
-//   * a new session starts with nothing known: its first appending launch is preceded by a memset of the length (captured with it),
-//     its first qg_vec_reset_done compacts the `done` flags itself;
-//   * once anything was captured (list_tainted), eager calls trust nothing: no LIST instantiations, every reset_done compacts;
-//   * inside a session the launches run in the order they were enqueued, so the belief is exact there.
-// Appends are clamped to the list's B entries on the device as well (done_list_append), so a misuse cannot write past the allocation.
-bool done_list_session(qg_vec *v, hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    unsigned long long id = 0;
-    if (s) (void)hipStreamGetCaptureInfo(s, &cs, &id);
-    const uint64_t cur = cs == hipStreamCaptureStatusNone ? 0ull : (id ? (uint64_t)id : ~0ull);
-    if (cur != v->list_session) {
-        v->list_session = cur;
-        v->done_list_fresh = false;
-        v->list_zero_known = false;
-        v->mask_fresh = false;
-        v->alt_zero_known = false;
-        if (cur) v->list_tainted = true;
-    }
-    return cur != 0 || !v->list_tainted;
-}
-
-// before a launch that appends: the length is zero when it runs
-int done_list_before_append(qg_vec *v, hipStream_t s) {
-    if (!v->list_zero_known || v->done_list_fresh) HIP_TRY(hipMemsetAsync(v->done_list + v->B, 0, 2 * sizeof(uint32_t), s));
-    v->done_list_fresh = false;
-    v->mask_fresh = false;
-    v->list_zero_known = true;
-    return QG_OK;
-}
-void done_list_appended(qg_vec *v, bool trusted) {
-    v->done_list_fresh = trusted;  // an untrusted list is never consumed: the next reset_done compacts
-    v->list_zero_known = false;
-    v->mask_fresh = false;  // (the step launches that left their finishers as a mask say so themselves: step_wrote_mask)
-}
-// the number a mask-writing launch stamps its buffer's hint word with (never 0, the buffers' initial content)
-static uint32_t mask_epoch_of(const qg_vec *v) { return ((uint32_t)v->step_index & 0x7FFFFFFFu) + 1u; }
-// TILE: a list-leaving step writes the mask that is not the current one (and appends nothing: the list stays empty)
-static void step_wrote_mask(qg_vec *v, const StepArgs &a, bool trusted) {
-    if (a.done_mask) {
-        v->mask_cur ^= 1;
-        v->mask_epoch[v->mask_cur] = a.done_epoch;
-        v->mask_fresh = trusted;
-        v->list_zero_known = true;  // (nothing was appended: the length is still the zero done_list_before_append made sure of)
-    }
-}
-
-}  // namespace qg
-extern "C" {
-// A list describes the `done` flags of the step that wrote it only: anything else that changes the flags first drops it (and re-zeroes
-// its length, which only the list's consumer would have done).
-static int drop_done_list(qg_vec *v, hipStream_t s) {
-    (void)done_list_session(v, s);
-    if (v->done_list_fresh) {
-        if (!(v->mask_fresh && v->list_zero_known)) HIP_TRY(hipMemsetAsync(v->done_list + v->B, 0, 2 * sizeof(uint32_t), s));
-        v->done_list_fresh = false;
-        v->list_zero_known = true;
-    }
-    v->mask_fresh = false;
-    return QG_OK;
-}
+// anything that changes the `done` flags other than a list-leaving step first drops the list
+static int drop_done_list(qg_vec *v, hipStream_t s) { return zero_list_length(v, v->done_list, v->dl.drop(), s); }
 
 // qg_vec_set_kernel_clock: the slot of the launch about to be enqueued (the k-th one after the call), or null
 static unsigned long long *kernel_clock_slot(const qg_vec *v) {
@@ -327,7 +260,7 @@ static uint32_t reset_tree_grid(const qg_vec *v, uint32_t most) {
     // after a reset, say -- must not bake a small grid in, or every later list is walked in many rounds.  TILE: the whole grid (its one-launch kernels fit
     // seven workgroups per CU since round 5: idle tree workgroups cost nothing measurable, 9.15 against 9.2 us a pair); TILE64 / PauliEnv (three per CU: the
     // whole grid costs 1.0 / 0.5 us a pair): at least half of it, all of it when the last launch saw nobody finish.
-    const bool captured = v->list_session != 0;
+    const bool captured = v->dl.captured();
     if (captured && (v->layout == LAYOUT_TILE || seen == 0)) return most;
     const uint64_t want = (uint64_t)seen + 4ull * (uint64_t)std::sqrt((double)seen) + 32ull;
     const uint64_t g = (want + 63ull) & ~63ull;
@@ -573,10 +506,9 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
             HIP_TRY_V(hipMalloc(&p->mask_count, 2 * sizeof(uint32_t)));
             HIP_TRY_V(hipMemset(p->mask_count, 0, 2 * sizeof(uint32_t)));
         }
-        const size_t mask_bytes = 10 * 4 * ((batch + 255) / 256) + 8;  // device_common.hpp done_mask_bytes: a word per wave of the step grid (whole workgroups of 256 envs), then a count byte per 32 envs
         for (auto &m : p->done_mask) {
-            HIP_TRY_V(hipMalloc(&m, mask_bytes));
-            HIP_TRY_V(hipMemset(m, 0, mask_bytes));
+            HIP_TRY_V(hipMalloc(&m, done_mask_bytes(batch)));
+            HIP_TRY_V(hipMemset(m, 0, done_mask_bytes(batch)));
         }
     }
     HIP_TRY_V(hipMalloc(&p->error, sizeof(uint32_t) * batch));
@@ -729,6 +661,7 @@ int qg_vec_set_state(qg_vec *v, const void *states, int format, size_t stride, i
     if (format < QG_FMT_I64 || format > QG_FMT_PACKED) return set_error(QG_ERR_INVALID, "unknown state format %d", format);
     QG_ON_DEVICE(v);
     hipStream_t s = (hipStream_t)stream;
+    (void)v->dl.enter(session_of(s));
     if (int rc = drop_done_list(v, s)) return rc;
     if (v->layout == LAYOUT_PAULI) return pauli_set_state(v, states, format, stride, on_device, s);
     if (stride < format_min_elems(v, format))
@@ -856,62 +789,45 @@ int qg_vec_get_state(qg_vec *v, void *out, int format, size_t stride, int on_dev
     return QG_OK;
 }
 
-static int do_reset(qg_vec *v, const int32_t *actions_dev, size_t n_draws, uint64_t seed, hipStream_t s, bool only_done = false) {
+// qg_vec_reset / qg_vec_reset_with / qg_vec_reset_done: `difficulty` draws per env (counter-RNG from `seed`, or the caller's actions_dev)
+static int do_reset(qg_vec *v, const int32_t *actions_dev, uint64_t seed, hipStream_t s, bool only_done = false) {
     QG_ON_DEVICE(v);
-    const bool trusted = done_list_session(v, s);
-    if (!only_done)
-        if (int rc = drop_done_list(v, s)) return rc;
-    if (only_done && v->layout == LAYOUT_PAULI) {
-        const bool from_mask = trusted && v->done_list_fresh && v->mask_fresh;  // the step before (ptile_step1c_kernel<LIST>) left its finishers as bits
-        v->done_list_fresh = v->mask_fresh = false;
-        v->auto_list = true;  // (from now on single steps leave their finishers themselves)
-        return ptile_reset_seeded(v, seed, true, s, from_mask);
-    }
+    const bool trusted = v->dl.enter(session_of(s));
+    if (int rc = only_done ? QG_OK : drop_done_list(v, s)) return rc;
+    if (only_done && v->layout == LAYOUT_PAULI) return ptile_reset_seeded(v, seed, true, s, v->dl.pauli_reset_consumes(trusted));
     if (v->layout == LAYOUT_PAULI) {
         if (actions_dev) return set_error(QG_ERR_UNSUPPORTED, "PauliEnv reset draws a whole target, not `difficulty` actions: use qg_vec_reset(seed) or qg_vec_pauli_reset_from");
         return pauli_reset_seeded(v, seed, s);
     }
-    if (v->gates.empty() && n_draws)  // Uniform::new(0, 0) panics in the reference
+    if (v->gates.empty() && v->difficulty)  // Uniform::new(0, 0) panics in the reference
         return set_error(QG_ERR_PANIC, "reset with an empty gateset (the reference panics in Uniform::new(0, 0))");
     InitArgs ia;
-    fill_init_args(v, ia);
-    ia.mode = 2;
+    fill_reset_done_args(v, seed, ia);
     ia.actions = actions_dev;
-    ia.n_draws = (uint32_t)n_draws;
-    ia.seed = seed;
     ia.only_done = only_done ? 1u : 0u;
     if (only_done && v->done_list) {
         // few, scattered finished envs: pack their indices first so that the scramble runs in full waves
-        // instead of in every wave that holds one finished env (the sampling + step kernel has already done it: done_list_fresh)
-        const bool left_by_step = trusted && v->done_list_fresh;  // the step before recorded its finishers itself (a list, or TILE: bits + a list)
-        if (!left_by_step) {
-            HIP_TRY(compact_done(v->done, v->B, v->done_list, v->done_list + v->B, s));
-            v->mask_fresh = false;
-        }
-        v->done_list_fresh = false;
-        v->list_zero_known = true;  // the reset kernel is the list's consumer: it zeroes the length (list_count_take)
-        v->auto_list = true;
+        // instead of in every wave that holds one finished env (unless the step before has already recorded them)
+        const DoneListState::Consume use = v->dl.reset_consumes(trusted);
+        if (use.compact) HIP_TRY(compact_done(v->done, v->B, v->done_list, v->done_list + v->B, s));
         ia.list = v->done_list;
         ia.list_count = v->done_list + v->B;
         if ((v->layout == LAYOUT_TILE || v->layout == LAYOUT_TILE64) && v->count_seen) {
             ia.count_out = v->count_seen;
             ia.tree_grid = reset_tree_grid(v, plan::tree_grid(v->B));
         }
-        if (left_by_step && v->mask_fresh && v->done_mask[0]) {  // TILE: the step before left its finishers as bits (the list holds what the fused launch added, if anything)
-            ia.mask = v->done_mask[v->mask_cur];
-            ia.mask_words = (uint32_t)(4 * ((v->B + 255) / 256));
-            ia.mask_epoch = v->mask_epoch[v->mask_cur];
+        if (use.mask && v->done_mask[0]) {  // TILE: the step before left its finishers as bits (the list holds what the fused launch added, if anything)
+            ia.mask = v->done_mask[v->dl.cur()];
+            ia.mask_words = (uint32_t)done_mask_words(v->B);
+            ia.mask_epoch = v->dl.epoch();
             ia.count_pub = v->mask_count;
         }
-        v->mask_fresh = false;
         ia.coop = plan::reset_coop_allowed(actions_dev != nullptr, v->B, v->d_rowops != nullptr) ? 1u : 0u;
         ia.flags_current = 1u;  // (this launch is the reset alone)
         if (v->layout == LAYOUT_TILE) ia.dense = v->dense;  // the listed envs' dense observations are rewritten by the reset itself
         if (v->done_list_spare) ia.zero_count = v->done_list_spare + v->B;
     }
     if (!only_done) v->maybe_nonsymplectic = false;  // identity + gates: every env is symplectic again
-    int64_t d = (int64_t)v->cfg.depth_slope * v->difficulty;  // clifford.rs:317
-    ia.depth_value = (int32_t)std::min<int64_t>(d, v->cfg.max_depth);
     HIP_TRY(launch_init(v, ia, s));
     if (ia.zero_count) std::swap(v->done_list, v->done_list_spare);  // the list just zeroed is the one the next step appends to; the consumed one idles
     if (v->dense && !ia.dense) return dense_refresh(v, s);
@@ -992,11 +908,11 @@ uint64_t qg_vec_get_env_base(const qg_vec *v) { return v ? v->env_base : 0; }
 
 int qg_vec_reset(qg_vec *v, uint64_t seed, void *stream) {
     if (!v) return set_error(QG_ERR_INVALID, "null argument");
-    return do_reset(v, nullptr, (size_t)v->difficulty, seed, (hipStream_t)stream);
+    return do_reset(v, nullptr, seed, (hipStream_t)stream);
 }
 int qg_vec_reset_done(qg_vec *v, uint64_t seed, void *stream) {
     if (!v) return set_error(QG_ERR_INVALID, "null argument");
-    return do_reset(v, nullptr, (size_t)v->difficulty, seed, (hipStream_t)stream, true);
+    return do_reset(v, nullptr, seed, (hipStream_t)stream, true);
 }
 
 int qg_vec_reset_with(qg_vec *v, const int32_t *actions_dev, size_t n_draws, void *stream) {
@@ -1004,23 +920,23 @@ int qg_vec_reset_with(qg_vec *v, const int32_t *actions_dev, size_t n_draws, voi
     if ((int64_t)n_draws != v->difficulty)
         return set_error(QG_ERR_INVALID, "reset_with: need exactly `difficulty` (%lld) draws per env, got %zu",
                          (long long)v->difficulty, n_draws);
-    return do_reset(v, actions_dev, n_draws, 0, (hipStream_t)stream);
+    return do_reset(v, actions_dev, 0, (hipStream_t)stream);
 }
 
 // A handle on which qg_vec_reset_done is in use: a single step of the TILE / TILE64 one-step kernels (qm_step1, qm_inv2, q64_step1, q64_inv2)
 // leaves the list of the envs it finished itself, and the reset that follows needs no compaction launch.
-static bool step_leaves_done_list(const qg_vec *v, StepArgs &a) {
+static bool step_leaves_done_list(const qg_vec *v, bool may_leave, StepArgs &a) {
     const bool tile32 = v->layout == LAYOUT_TILE, tile64 = v->layout == LAYOUT_TILE64;  // qm_step1 / qm_inv2 (N <= 16), q64_step1 / q64_inv2
     const bool pauli = v->layout == LAYOUT_PAULI && v->done_mask[0] && v->pt_nq <= 24 && v->pt_rm == 8 && v->B > QG_COMPACT_MIN_ENVS;  // ptile_step1c_kernel (compact layout)
-    const bool lists = v->auto_list && v->done_list &&
+    const bool lists = may_leave && v->done_list &&
                        (pauli || ((tile32 || tile64) && ((v->flags & F_INVERTS) ? (v->has_z && (tile64 || v->nxp <= 16) && !v->maybe_nonsymplectic) : v->bad != nullptr)));
     if (lists) {
         a.flags |= F_DONE_LIST;
         a.done_list = v->done_list;
         a.done_count = v->done_list + v->B;
         if (v->done_mask[0]) {  // one bit per env instead of an append (the list stays empty)
-            a.done_mask = v->done_mask[v->mask_cur ^ 1];
-            a.done_epoch = mask_epoch_of(v);
+            a.done_mask = v->done_mask[v->dl.cur() ^ 1];
+            a.done_epoch = DoneListState::epoch_for(v->step_index);
         }
     }
     return lists;
@@ -1030,22 +946,18 @@ int qg_vec_step(qg_vec *v, const void *actions_dev, int action_dtype, const uint
     if (!v || !actions_dev) return set_error(QG_ERR_INVALID, "null argument");
     if (action_dtype != QG_ACT_I32 && action_dtype != QG_ACT_I64) return set_error(QG_ERR_INVALID, "bad action dtype");
     QG_ON_DEVICE(v);
-    const bool trusted = done_list_session(v, (hipStream_t)stream);
-    if (v->done_list_fresh) v->auto_list = false;  // the last list was never consumed: this caller steps without qg_vec_reset_done
+    const bool may_leave = v->dl.step_enters(session_of((hipStream_t)stream));
     StepArgs a;
     fill_step_args(v, a);
-    const bool lists = trusted && step_leaves_done_list(v, a);
-    if (int rc = lists ? done_list_before_append(v, (hipStream_t)stream) : drop_done_list(v, (hipStream_t)stream)) return rc;
+    const bool lists = step_leaves_done_list(v, may_leave, a);
+    if (int rc = lists ? zero_list_length(v, v->done_list, v->dl.before_append(), (hipStream_t)stream) : drop_done_list(v, (hipStream_t)stream)) return rc;
     a.actions = actions_dev;
     a.coins = coins_dev;
     if (action_dtype == QG_ACT_I64) a.flags |= F_ACT64;
     if (dense_rides_in_step(v)) a.dense = v->dense;
     HIP_TRY(launch_step(v, a, (hipStream_t)stream));
     v->step_index += 1;
-    if (lists) {
-        done_list_appended(v, true);
-        step_wrote_mask(v, a, true);
-    }
+    if (lists) v->dl.step_left(a.done_mask != nullptr, a.done_epoch);
     if (v->dense && !a.dense) return dense_refresh(v, (hipStream_t)stream);
     return QG_OK;
 }
@@ -1112,59 +1024,23 @@ int qg_vec_reset_done_step(qg_vec *v, uint64_t reset_seed, const void *actions_d
     if (action_dtype != QG_ACT_I32 && action_dtype != QG_ACT_I64) return set_error(QG_ERR_INVALID, "bad action dtype");
     QG_ON_DEVICE(v);
     hipStream_t s = (hipStream_t)stream;
-    const bool trusted = done_list_session(v, s);
+    const bool trusted = v->dl.enter(session_of(s));
     // one launch when the list of finished envs and their is_final flags were left by this handle's own previous step (same session) and the
     // reset would take the list path with counter-RNG draws; otherwise the two calls, whose step leaves both for the next time
     // (add_inverts: the two-lanes-per-env launch has no Gauss-Jordan and no tracked-observation form)
     const bool inverts = v->flags & F_INVERTS;
     // ... and where the one launch is the faster form (qgym_plan.hpp reset_step_pays: from the configuration)
     const bool pays = plan::reset_step_pays(plan_of(v), v->difficulty, std::min<int64_t>((int64_t)v->cfg.depth_slope * v->difficulty, v->cfg.max_depth));
-    const bool fuse = v->done_list_alt && v->done_mask[0] && trusted && v->done_list_fresh && v->mask_fresh && v->auto_list && !v->gates.empty() &&
+    const bool fuse = v->done_list_alt && v->done_mask[0] && v->dl.fused_may_run(trusted) && !v->gates.empty() &&
                       plan::reset_coop_allowed(false, v->B, v->d_rowops != nullptr) && plan::reset_step_fuses(plan_of(v)) &&
                       !(inverts && (v->maybe_nonsymplectic || v->dense)) && pays;
-    if (plan::reset_step_in_word_kernel(plan_of(v), v->gates.size())) {
-        // one uint64 per env: no list -- every wave tests its envs' is_final flags, resets the finished ones (16 lanes each) and steps all of them
-        InitArgs ia;
-        fill_init_args(v, ia);
-        ia.mode = 2;
-        ia.n_draws = (uint32_t)v->difficulty;
-        ia.seed = reset_seed;
-        ia.only_done = 1u;
-        ia.depth_value = (int32_t)std::min<int64_t>((int64_t)v->cfg.depth_slope * v->difficulty, v->cfg.max_depth);  // linear_function.rs:296
-        StepArgs a;
-        fill_step_args(v, a);
-        a.actions = actions_dev;
-        a.coins = coins_dev;
-        a.rewards_seq = rewards_dev;
-        a.dones_seq = dones_dev;
-        if (action_dtype == QG_ACT_I64) a.flags |= F_ACT64;
-        a.kclk = kernel_clock_slot(v);
-        a.kclk_waves = v->kclk_waves;
-        HIP_TRY(word_reset_step(ia, a, v->layout == LAYOUT_PERM, s));
-        v->step_index += 1;
-        return QG_OK;
-    }
-    if (!fuse) {
+    const bool word = plan::reset_step_in_word_kernel(plan_of(v), v->gates.size());
+    if (!word && !fuse) {
         if (int rc = qg_vec_reset_done(v, reset_seed, stream)) return rc;
         return rollout_impl(v, actions_dev, action_dtype, 1, 1, coins_dev, rewards_dev, dones_dev, 0, stream);
     }
     InitArgs ia;
-    fill_init_args(v, ia);
-    ia.mode = 2;
-    ia.n_draws = (uint32_t)v->difficulty;
-    ia.seed = reset_seed;
-    ia.only_done = 1u;
-    ia.list = v->done_list;
-    ia.list_count = v->done_list + v->B;
-    ia.zero_count = v->done_list_spare + v->B;
-    ia.count_out = v->count_seen;
-    ia.tree_grid = reset_tree_grid(v, plan::tree_grid(v->B));
-    ia.mask = v->done_mask[v->mask_cur];  // the finishers of the step before: the reset's work, and the step workgroups' "not mine" test
-    ia.mask_words = (uint32_t)(4 * ((v->B + 255) / 256));
-    ia.mask_epoch = v->mask_epoch[v->mask_cur];
-    ia.coop = 1u;
-    ia.dense = v->dense;
-    ia.depth_value = (int32_t)std::min<int64_t>((int64_t)v->cfg.depth_slope * v->difficulty, v->cfg.max_depth);  // clifford.rs:317
+    fill_reset_done_args(v, reset_seed, ia);
     StepArgs a;
     fill_step_args(v, a);
     a.actions = actions_dev;
@@ -1172,12 +1048,31 @@ int qg_vec_reset_done_step(qg_vec *v, uint64_t reset_seed, const void *actions_d
     a.rewards_seq = rewards_dev;
     a.dones_seq = dones_dev;
     if (action_dtype == QG_ACT_I64) a.flags |= F_ACT64;
+    if (word) {
+        // one uint64 per env: no list -- every wave tests its envs' is_final flags, resets the finished ones (16 lanes each) and steps all of them
+        if (int rc = drop_done_list(v, s)) return rc;  // (enqueues nothing: these layouts hold no list)
+        a.kclk = kernel_clock_slot(v);
+        a.kclk_waves = v->kclk_waves;
+        HIP_TRY(word_reset_step(ia, a, v->layout == LAYOUT_PERM, s));
+        v->step_index += 1;
+        return QG_OK;
+    }
+    ia.list = v->done_list;
+    ia.list_count = v->done_list + v->B;
+    ia.zero_count = v->done_list_spare + v->B;
+    ia.count_out = v->count_seen;
+    ia.tree_grid = reset_tree_grid(v, plan::tree_grid(v->B));
+    ia.mask = v->done_mask[v->dl.cur()];  // the finishers of the step before: the reset's work, and the step workgroups' "not mine" test
+    ia.mask_words = (uint32_t)done_mask_words(v->B);
+    ia.mask_epoch = v->dl.epoch();
+    ia.coop = 1u;
+    ia.dense = v->dense;
     a.flags |= F_DONE_LIST;  // the envs that finish in this step go to the OTHER mask (a reset env that is final again after its first step: to the OTHER list)
     a.done_list = v->done_list_alt;
     a.done_count = v->done_list_alt + v->B;
-    a.done_mask = v->done_mask[v->mask_cur ^ 1];
-    a.done_epoch = mask_epoch_of(v);
-    if (!v->alt_zero_known) HIP_TRY(hipMemsetAsync(v->done_list_alt + v->B, 0, 2 * sizeof(uint32_t), s));
+    a.done_mask = v->done_mask[v->dl.cur() ^ 1];
+    a.done_epoch = DoneListState::epoch_for(v->step_index);
+    if (int rc = zero_list_length(v, v->done_list_alt, v->dl.alt_needs_zero(), s)) return rc;
     if (dense_rides_in_step(v)) a.dense = v->dense;
     a.kclk = kernel_clock_slot(v);
     a.kclk_waves = v->kclk_waves;
@@ -1186,12 +1081,7 @@ int qg_vec_reset_done_step(qg_vec *v, uint64_t reset_seed, const void *actions_d
     // the list just appended to is the current one, the idle list (zeroed by this launch) is the next launch's target, the one just consumed idles
     std::swap(v->done_list, v->done_list_alt);   // (current, alt, spare) <- (alt, spare, current)
     std::swap(v->done_list_alt, v->done_list_spare);
-    v->mask_cur ^= 1;
-    v->mask_epoch[v->mask_cur] = a.done_epoch;
-    v->done_list_fresh = true;
-    v->mask_fresh = true;
-    v->list_zero_known = false;
-    v->alt_zero_known = true;
+    v->dl.fused_ran(a.done_epoch);
     if (v->dense && !a.dense) return dense_refresh(v, s);
     return QG_OK;
 }
@@ -1214,12 +1104,11 @@ static int rollout_impl(qg_vec *v, const void *actions_dev, int action_dtype, si
     if (T > 0x7fffffffu) return set_error(QG_ERR_INVALID, "too many steps");
     QG_ON_DEVICE(v);
     hipStream_t s = (hipStream_t)stream;
-    const bool trusted = done_list_session(v, s);
-    if (v->done_list_fresh) v->auto_list = false;  // the last list was never consumed: this caller steps without qg_vec_reset_done
+    const bool may_leave = v->dl.step_enters(session_of(s));
     StepArgs a;
     fill_step_args(v, a);
-    const bool lists = trusted && T == 1 && !fused && step_leaves_done_list(v, a);
-    if (int rc = lists ? done_list_before_append(v, s) : drop_done_list(v, s)) return rc;
+    const bool lists = step_leaves_done_list(v, may_leave && T == 1 && !fused, a);
+    if (int rc = lists ? zero_list_length(v, v->done_list, v->dl.before_append(), s) : drop_done_list(v, s)) return rc;
     a.actions = actions_dev;
     a.coins = coins_dev;
     a.rewards_seq = rewards_dev;
@@ -1263,10 +1152,7 @@ static int rollout_impl(qg_vec *v, const void *actions_dev, int action_dtype, si
     if (cs != hipStreamCaptureStatusNone || rng_coins || T == 1) {
         HIP_TRY(enqueue_steps(s));
         v->step_index += T;
-        if (lists) {
-            done_list_appended(v, true);
-            step_wrote_mask(v, a, true);
-        }
+        if (lists) v->dl.step_left(a.done_mask != nullptr, a.done_epoch);
         return QG_OK;
     }
     GraphKey key{actions_dev, coins_dev, rewards_dev, dones_dev, T, action_dtype, period, a.flags, v->env_base, v->dense};
@@ -1570,6 +1456,17 @@ int qg_vec_solutions(qg_vec *v, uint64_t *out, size_t cap, int64_t *lens) {
 }  // extern "C"
 
 namespace qg {
+// the done-list session (qgym_done_list.hpp) a launch on `s` belongs to: 0 = eager execution, else the stream's capture id
+uint64_t session_of(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    unsigned long long id = 0;
+    if (s) (void)hipStreamGetCaptureInfo(s, &cs, &id);
+    return cs == hipStreamCaptureStatusNone ? 0ull : (id ? (uint64_t)id : ~0ull);
+}
+int zero_list_length(const qg_vec *v, uint32_t *list, bool needed, hipStream_t s) {
+    if (needed) HIP_TRY(hipMemsetAsync(list + v->B, 0, 2 * sizeof(uint32_t), s));
+    return QG_OK;
+}
 void fill_step_args_public(const qg_vec *v, StepArgs &a) { fill_step_args(v, a); }
 int bind_error(qg_vec *v, uint32_t *error_dev) {
     if (!v || !error_dev) return set_error(QG_ERR_INVALID, "null argument");
@@ -1593,15 +1490,14 @@ uint32_t reset_second_grid_public(const qg_vec *v, bool is_tree_list_of_that_len
 }
 
 int dense_refresh_public(qg_vec *v, hipStream_t s) { return dense_refresh(v, s); }
-// InitArgs of qg_vec_reset_done(v, seed) without a list: what a kernel that resets finished envs itself needs (qg_vec_mid_head_sample_step)
-void fill_reset_done_args_public(const qg_vec *v, uint64_t seed, InitArgs &ia) {
+// (also what a kernel that resets finished envs itself needs: qg_vec_mid_head_sample_step)
+void fill_reset_done_args(const qg_vec *v, uint64_t seed, InitArgs &ia) {
     fill_init_args(v, ia);
     ia.mode = 2;
     ia.n_draws = (uint32_t)v->difficulty;
     ia.seed = seed;
     ia.only_done = 1u;
-    const int64_t d = (int64_t)v->cfg.depth_slope * v->difficulty;  // clifford.rs:317
-    ia.depth_value = (int32_t)std::min<int64_t>(d, v->cfg.max_depth);
+    ia.depth_value = (int32_t)std::min<int64_t>((int64_t)v->cfg.depth_slope * v->difficulty, v->cfg.max_depth);  // clifford.rs:317, linear_function.rs:296
 }
 int reset_done_public(qg_vec *v, uint64_t seed, void *stream) { return qg_vec_reset_done(v, seed, stream); }
 }  // namespace qg

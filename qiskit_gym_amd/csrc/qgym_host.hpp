@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "qgym_done_list.hpp"
 #include "qgym_internal.hpp"
 #include "qgym_plan.hpp"
 
@@ -121,24 +122,13 @@ struct qg_vec {
     uint32_t *bad = nullptr;            // TILE / TILE64 without add_inverts: per-env "differs from identity" mask (one-step kernels)
     uint32_t *d_rowops = nullptr;       // TILE: gate table as pairs of row operations on slots (cooperative reset kernel)
     uint32_t *done_list = nullptr;      // reset_done: [B] indices of finished envs + {length, reader ticket} at [B], [B + 1]
-    // qg_vec_reset_done_step (TILE without add_inverts): the fused launch consumes done_list and appends to done_list_alt, then the two trade
-    // places
-    uint32_t *done_list_alt = nullptr;
+    uint32_t *done_list_alt = nullptr;  // qg_vec_reset_done_step as one launch: it consumes done_list and appends to this one, then they rotate
     uint32_t *done_list_spare = nullptr;  // TILE: the list no launch in flight reads or appends to; the reset that consumes done_list zeroes this one's length, then they rotate
     // TILE: the finished envs of a step as one bit per env (StepArgs::done_mask), two buffers -- a list-leaving step (or the fused reset + step
     // launch, which reads the current one) writes the other one, then they trade places.  Nothing to zero: a launch rewrites every word.
     uint64_t *done_mask[2] = {nullptr, nullptr};
     uint32_t *mask_count = nullptr;     // TILE64 / PauliEnv: a device word where a reset's first launch leaves the mask's count for its second
-    int mask_cur = 0;
-    uint32_t mask_epoch[2] = {0, 0};    // StepArgs::done_epoch of the launch that wrote each buffer (InitArgs::mask_epoch for its reader)
-    bool mask_fresh = false;            // done_mask[mask_cur] (+ the list in done_list: envs reset and final again inside the fused launch; else empty) holds
-                                        // the envs that are final, as the handle's own last step left them (believed within the session, like done_list_fresh)
-    bool alt_zero_known = true;         // done_list_alt's length is known to be zero
-    bool auto_list = false;             // qg_vec_reset_done is in use on this handle: single steps append the envs they finish to the list themselves
-    bool done_list_fresh = false;       // the list already holds the finished envs (written by the step that ended them); believed within the session only
-    bool list_zero_known = true;        // the list's length is known to be zero (creation, a memset, or its consumer ran) -- within the session
-    bool list_tainted = false;          // some launch that touches the list was captured into a caller's graph: eager calls trust nothing
-    uint64_t list_session = 0;          // 0 = eager execution, else the stream capture id the beliefs above belong to (qgym_api.cpp)
+    qg::DoneListState dl;               // what the host believes about the list and the masks (qgym_done_list.hpp)
     int8_t *dense = nullptr;            // qg_vec_track_dense: caller-owned [B][rows][cols] int8 observation kept equal to observe_dense() of the state
     uint32_t *d_nonsymp = nullptr;      // device word behind InitArgs::nonsymp_flag
     void *embed_dump = nullptr;         // qg_vec_embed: 1 KiB nobody reads (kernels_policy.hip), allocated by qg_vec_pack_embedding
@@ -168,10 +158,8 @@ struct qg_vec {
 
 namespace qg {
 int ensure_scratch_public(qg_vec *v, size_t bytes);
-// done-list protocol (qgym_api.cpp): session scoping of the host's beliefs, zeroing before an appending launch
-bool done_list_session(qg_vec *v, hipStream_t s);
-int done_list_before_append(qg_vec *v, hipStream_t s);
-void done_list_appended(qg_vec *v, bool trusted);
+uint64_t session_of(hipStream_t s);  // the done-list session (DoneListState::enter) a launch on `s` belongs to: 0 = eager, else the capture id
+int zero_list_length(const qg_vec *v, uint32_t *list, bool needed, hipStream_t s);  // enqueue what a DoneListState transition asked for
 void fill_step_args_public(const qg_vec *v, StepArgs &a);
 // the per-env fault words in caller-owned memory (device-visible, [B] uint32, current content carried over); not part of the C ABI: the scalar env's
 int bind_error(qg_vec *v, uint32_t *error_dev);
@@ -180,7 +168,8 @@ uint32_t reset_tree_grid_public(const qg_vec *v, uint32_t most);  // workgroups 
 unsigned long long *kernel_clock_slot_public(const qg_vec *v);  // qg_vec_set_kernel_clock: the slot of the launch about to be enqueued, or null
 // qg_vec_track_dense: rewrite the whole tracked observation from the state (after a launch that changed states without updating it)
 int dense_refresh_public(qg_vec *v, hipStream_t s);
-void fill_reset_done_args_public(const qg_vec *v, uint64_t seed, InitArgs &ia);
+// InitArgs of qg_vec_reset_done(v, seed) without a list (mode 2, `difficulty` draws, only the finished envs)
+void fill_reset_done_args(const qg_vec *v, uint64_t seed, InitArgs &ia);
 void compute_qubit_and_action_perms(uint32_t N, const std::vector<qg_gate> &gates, std::vector<std::vector<int64_t>> &qubit_perms,
                                     std::vector<std::vector<int64_t>> &act_perms);
 // PauliEnv host hooks (pauli_host.cpp)

@@ -53,9 +53,15 @@ enum : uint32_t {
     F_TRACK = 1u << 2,     // track_solution (clifford.rs:334-340)
     F_LAYERS = 1u << 3,    // non-zero n_layers / n_layers_cnots weights: track per-qubit layers
     F_GJ = 1u << 4,        // some env may hold a non-symplectic matrix: compile in the Gauss-Jordan inversion
-    F_DONE_LIST = 1u << 5  // the one-step kernel records the envs that finish for the qg_vec_reset_done that follows (no compaction launch): TILE stores
-                           // one bit per env in StepArgs::done_mask, TILE64 and the sampling + step kernels append indices to StepArgs::done_list
+    F_DONE_LIST = 1u << 5  // the one-step kernel records the envs that finish for the qg_vec_reset_done that follows (no compaction launch): TILE, TILE64
+                           // and PauliEnv's compact step store one bit per env in StepArgs::done_mask, the sampling + step kernels append indices to
+                           // StepArgs::done_list
 };
+
+// Layout of a done-mask buffer (StepArgs::done_mask, device_common.hpp done_mask_store) for a batch of B: W = 4 * ceil(B / 256) words (one per
+// wave of the step grid, whole workgroups of 256 envs), then 2 W count bytes (one per 32 envs), then the 8-byte hint word
+__host__ __device__ inline uint64_t done_mask_words(uint64_t B) { return 4ull * ((B + 255ull) / 256ull); }
+__host__ __device__ inline uint64_t done_mask_bytes(uint64_t B) { return done_mask_words(B) * 10ull + 8ull; }
 
 // counter RNG shared by host, device and the tests
 __host__ __device__ inline uint64_t splitmix64(uint64_t x) {
