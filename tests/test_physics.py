@@ -25,34 +25,7 @@ import pytest
 from oracle import OracleEnv
 from util import line_gateset
 
-I2 = np.eye(2, dtype=complex)
-X = np.array([[0, 1], [1, 0]], dtype=complex)
-Y = np.array([[0, -1j], [1j, 0]])
-Z = np.diag([1, -1]).astype(complex)
-ONE = {"h": (X + Z) / np.sqrt(2), "s": np.diag([1, 1j]), "sdg": np.diag([1, -1j]),
-       "sx": 0.5 * np.array([[1 + 1j, 1 - 1j], [1 - 1j, 1 + 1j]]), "sxdg": 0.5 * np.array([[1 - 1j, 1 + 1j], [1 + 1j, 1 - 1j]])}
-P1 = {"I": I2, "X": X, "Y": Y, "Z": Z}
-
-
-def op1(g, q, n):
-    m = np.array([[1]], dtype=complex)
-    for k in range(n - 1, -1, -1):  # qubit 0 is the least significant bit
-        m = np.kron(m, g if k == q else I2)
-    return m
-
-
-def two(kind, a, b, n):
-    d = 2 ** n
-    m = np.zeros((d, d), dtype=complex)
-    for i in range(d):
-        ba, bb = (i >> a) & 1, (i >> b) & 1
-        if kind == "cx":  # control a, target b
-            m[i ^ (1 << b) if ba else i, i] = 1
-        elif kind == "cz":
-            m[i, i] = -1 if ba and bb else 1
-        else:
-            m[i & ~((1 << a) | (1 << b)) | (bb << a) | (ba << b), i] = 1
-    return m
+from envmodel import I2, ONE, P1, X, Y, Z, op1, two  # noqa: F401  (the gate matrices, shared with the env model)
 
 
 def gate_matrix(name, qs, n):

@@ -3,7 +3,6 @@ from __future__ import annotations
 
 import numpy as np
 
-from oracle import OracleEnv, OracleVec
 from qiskit_gym_amd.envs.gateset import gateset_from_coupling_map, grid_edges, line_edges
 
 ALLOWED = {
@@ -31,6 +30,7 @@ def oracle_cfg(cfg: dict) -> dict:
 
 
 def make_pair(kind, num_qubits, gateset, batch, **cfg):
+    from oracle import OracleEnv, OracleVec
     from qiskit_gym_amd.vec import VecEnv
 
     proto = OracleEnv(kind, num_qubits, gateset, **oracle_cfg(cfg))
