@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
- * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear (additions only) */
+ * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -163,6 +163,19 @@ int qg_vec_set_state(qg_vec *v, const void *states, int format, size_t stride_el
 /* Inverse of the above for inspection / checkpointing (QG_FMT_I64 of a PauliEnv returns the
  * tableau only). */
 int qg_vec_get_state(qg_vec *v, void *out, int format, size_t stride_elems, int on_device, void *stream);
+/* Env::clone, batched (clifford.rs:179, linear_function.rs:154, permutation.rs:29 derive(Clone); pauli.rs:307-337): env dst_idx[i] of `dst`
+ * becomes a copy of env src_idx[i] of `src`, i < n.  Copied: everything a clone carries -- the state, depth, reward, is_final, success,
+ * inverted, the fault word, the incremental solved masks, both halves of the solution log and their lengths, the layer-metric records, and
+ * PauliEnv's rotations, DAG order, phases and current_perm_idx -- so a copy and its source step identically under the same actions and
+ * coins.  A tracked dense observation of `dst` (qg_vec_track_dense) gets the copied envs' rows rewritten.
+ * A copy carries state, not RNG position: later draws of dst env j (add_inverts coins, PauliEnv observe permutations, resets) come from
+ * j's own counter streams of the `dst` handle, as every batched draw does.
+ * `src` and `dst` (may be the same handle): same constructor arguments and device (the rule of qg_env_clone's pool), else QG_ERR_INVALID.
+ * src_idx_dev / dst_idx_dev: device arrays of n uint32; dst_idx_dev NULL = 0 .. n-1.  Sources may repeat; destinations may not; when
+ * dst == src no index may be both a destination and a source.  Entries with an index out of range are skipped (the host cannot see device
+ * indices without a synchronisation).  Afterwards the list of finished envs is what qg_vec_set_state leaves: the next qg_vec_reset_done
+ * resets exactly the envs whose flag is set.  Stream-ordered, one launch, capturable into a hipGraph. */
+int qg_vec_copy_envs(qg_vec *dst, const qg_vec *src, const uint32_t *src_idx_dev, const uint32_t *dst_idx_dev, uint64_t n, void *stream);
 
 /* Env::reset for every env (clifford.rs:306-319).  The reference draws `difficulty` uniform
  * actions from an unseedable RNG; here draw t of env e is
@@ -538,7 +551,8 @@ typedef enum {
     QG_PLAN_OBSERVE_PACKED = 5, /* qg_vec_observe_packed */
     QG_PLAN_STATE_I64 = 6,      /* qg_vec_get_state / set_state in QG_FMT_I64 */
     QG_PLAN_TRACK_DENSE = 7,    /* qg_vec_track_dense: "in-step", "refresh" (a full rewrite after every step) or unsupported */
-    QG_PLAN_RESET_DONE_STEP = 8 /* qg_vec_reset_done_step: the one-launch kernel, or "two launches" */
+    QG_PLAN_RESET_DONE_STEP = 8, /* qg_vec_reset_done_step: the one-launch kernel, or "two launches" */
+    QG_PLAN_COPY_ENVS = 9        /* qg_vec_copy_envs: "copy_envs_kernel [rows x w ...]", the state regions of a tile it walks */
 } qg_plan_op;
 int qg_plan_query(const qg_config *cfg, uint64_t batch, uint32_t num_actions, int op, uint64_t arg, int nonsymplectic, char *name_out, size_t cap);
 

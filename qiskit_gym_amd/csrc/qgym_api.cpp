@@ -1298,9 +1298,64 @@ int qg_plan_query(const qg_config *cfg, uint64_t batch, uint32_t num_actions, in
         if (!plan::dense_trackable(hp)) return set_error(QG_ERR_UNSUPPORTED, "track_dense: matrices of 16 or 32 rows held as 32-bit row words");
         name = plan::dense_rides_in_step(hp) ? "in-step" : "refresh";
         break;
+    case QG_PLAN_COPY_ENVS:
+        plan::copy_kernel_name(hp, name_out, cap);
+        return QG_OK;
     default: return set_error(QG_ERR_INVALID, "unknown plan op %d", op);
     }
     snprintf(name_out, cap, "%s", name);
+    return QG_OK;
+}
+
+int qg_vec_copy_envs(qg_vec *dst, const qg_vec *src, const uint32_t *src_idx_dev, const uint32_t *dst_idx_dev, uint64_t n, void *stream) {
+    if (!dst || !src || (n && !src_idx_dev)) return set_error(QG_ERR_INVALID, "null argument");
+    if (!same_ctor(dst, src)) return set_error(QG_ERR_INVALID, "copy_envs: source and destination need the same constructor arguments and device");
+    if (n > dst->B) return set_error(QG_ERR_INVALID, "copy_envs: %llu copies into %llu envs (destinations may not repeat)", (unsigned long long)n,
+                                     (unsigned long long)dst->B);
+    QG_ON_DEVICE(dst);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = zero_list_length(dst, dst->done_list, dst->dl.copied_into(session_of(s)), s)) return rc;
+    if (!n) return QG_OK;
+    dst->maybe_nonsymplectic = dst->maybe_nonsymplectic || src->maybe_nonsymplectic;  // the Gauss-Jordan step variant if a copied matrix may need it
+    CopyArgs a{};
+    auto add = [&a](void *d, const void *sp, uint64_t tile_bytes, uint64_t pitch_dst, uint64_t pitch_src, uint32_t rows, uint32_t w) {
+        if (!d || !sp || !rows) return;
+        a.r[a.n_regions++] = CopyRegionArgs{(char *)d, (const char *)sp, tile_bytes, pitch_dst, pitch_src, rows, w};
+    };
+    plan::HandlePlan hp;
+    const char *why = "";
+    (void)plan::handle_plan(dst->cfg, dst->B, hp, why);
+    const plan::CopyLayout cl = plan::copy_layout(hp);
+    const size_t covered = hp.stride_bytes ? hp.stride_bytes * dst->B : (size_t)cl.tile_bytes * ((dst->B + 63) / 64);
+    if (!cl.n || covered != dst->state_bytes)  // the regions must be exactly the layout the allocation was sized for
+        return set_error(QG_ERR_UNSUPPORTED, "copy_envs: no region list for this layout");
+    for (uint32_t k = 0; k < cl.n; ++k)  // the state first: region 0 is the one the tracked dense observation is written from
+        add((char *)dst->state + cl.r[k].offset, (const char *)src->state + cl.r[k].offset, cl.tile_bytes, 64u * cl.r[k].w, 64u * cl.r[k].w, cl.r[k].rows,
+            cl.r[k].w);
+    auto per_env = [&add](void *d, const void *sp, uint32_t w) { add(d, sp, 64u * w, 0, 0, 1, w); };
+    per_env(dst->depth, src->depth, 4);
+    per_env(dst->reward, src->reward, 4);
+    per_env(dst->error, src->error, 4);
+    per_env(dst->done, src->done, 1);
+    per_env(dst->success, src->success, 1);
+    per_env(dst->inverted, src->inverted, 1);
+    per_env(dst->sol_len, src->sol_len, 8);  // {solution, solution_inv} lengths
+    per_env(dst->bad, src->bad, dst->layout == LAYOUT_LFD ? 16u : dst->layout == LAYOUT_TILE64 ? 8u : 4u);  // incremental solved masks
+    per_env(dst->perm_idx, src->perm_idx, 4);  // PauliEnv current_perm_idx (pauli.rs:661)
+    add(dst->sol, src->sol, 256, 4 * dst->B, 4 * src->B, dst->sol_cap, 4);  // [sol_cap][B]: both halves of the log
+    add(dst->layers, src->layers, 256ull * dst->layers_len, 256, 256, dst->layers_len, 4);  // [B / 64][2N + 2][64] (layer_rec)
+    a.src_idx = src_idx_dev;
+    a.dst_idx = dst_idx_dev;
+    a.n = n;
+    a.B_src = src->B;
+    a.B_dst = dst->B;
+    if (dst->dense && plan::dense_trackable(hp)) {
+        a.dense = dst->dense;
+        a.D = dst->D;
+        a.N = dst->N;
+        a.has_z = hp.has_z ? 1u : 0u;
+    }
+    HIP_TRY(copy_envs(a, s));
     return QG_OK;
 }
 

@@ -65,6 +65,12 @@ public:
         fresh_ = mask_fresh_ = false;
         return zero;
     }
+    // qg_vec_copy_envs into this handle: the copied envs' `done` flags are their sources', so the list and the masks describe nothing any
+    // more -- what qg_vec_set_state leaves (enter the stream's session, drop).  Whether the list's length must be zeroed.
+    bool copied_into(uint64_t session) {
+        (void)enter(session);
+        return drop();
+    }
     // qg_vec_reset_done on TILE / TILE64: its kernel consumes the list and zeroes the length (list_count_take)
     Consume reset_consumes(bool trusted) {
         const bool left_by_step = trusted && fresh_;  // the step before recorded its finishers itself (a list, or bits + a list)

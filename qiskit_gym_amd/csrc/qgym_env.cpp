@@ -193,11 +193,6 @@ constexpr size_t POOL_CAP = 256;         // a few per host thread (rl/configs.py
 constexpr size_t POOL_CAP_PER_KEY = 64;  // ... and at most this many with the same constructor arguments (a trainer that destroys thousands of
                                          // clones of one prototype does not push every other configuration's handles out, nor pin 256 of its own)
 
-bool same_ctor(const qg_vec *a, const qg_vec *b) {
-    return a->device == b->device && memcmp(&a->cfg, &b->cfg, sizeof a->cfg) == 0 && a->gates.size() == b->gates.size() &&
-           (a->gates.empty() || memcmp(a->gates.data(), b->gates.data(), a->gates.size() * sizeof(qg_gate)) == 0);
-}
-
 void env_free(qg_env *e) {
     if (!e) return;
     if (e->v) {

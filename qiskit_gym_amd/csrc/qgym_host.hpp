@@ -1,6 +1,7 @@
 // qgym_host.hpp -- host-side handle of a batched env (private to libqgym).
 #pragma once
 
+#include <string.h>
 #include <string>
 #include <vector>
 
@@ -157,6 +158,11 @@ struct qg_vec {
 };
 
 namespace qg {
+// built with the same constructor arguments on the same device (qg_env_clone's pool, qg_vec_copy_envs)
+inline bool same_ctor(const qg_vec *a, const qg_vec *b) {
+    return a->device == b->device && memcmp(&a->cfg, &b->cfg, sizeof a->cfg) == 0 && a->gates.size() == b->gates.size() &&
+           (a->gates.empty() || memcmp(a->gates.data(), b->gates.data(), a->gates.size() * sizeof(qg_gate)) == 0);
+}
 int ensure_scratch_public(qg_vec *v, size_t bytes);
 uint64_t session_of(hipStream_t s);  // the done-list session (DoneListState::enter) a launch on `s` belongs to: 0 = eager, else the capture id
 int zero_list_length(const qg_vec *v, uint32_t *list, bool needed, hipStream_t s);  // enqueue what a DoneListState transition asked for

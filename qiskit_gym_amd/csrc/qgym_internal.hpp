@@ -270,6 +270,28 @@ hipError_t expand_rows(const void *words_dev, int word_bytes, uint64_t n_rows, u
 hipError_t expand_rows_i64(const void *words_dev, int word_bytes, uint64_t n_rows, uint32_t cols, int64_t *out_dev, hipStream_t s);
 hipError_t pack_bitstream(const void *src, int elem_bytes, uint64_t n_entries, uint64_t *out_words, hipStream_t s);
 hipError_t compact_done(const uint8_t *done, uint64_t B, uint32_t *list, uint32_t *count, hipStream_t s);
+
+// qg_vec_copy_envs (kernels_copy.hip): env dst_idx[i] of one handle becomes a copy of env src_idx[i] of another, i < n.  Every per-env buffer
+// is a region of rows of 64 lanes: env e's `w` bytes of row r lie at base + (e >> 6) * tile_bytes + r * pitch + (e & 63) * w (the state's
+// regions: qgym_plan.hpp copy_layout; a [B] array of w-byte elements: one row; the step-major solution log: rows of pitch 4 B).
+constexpr uint32_t COPY_MAX_REGIONS = 16;
+struct CopyRegionArgs {
+    char *dst;
+    const char *src;
+    uint64_t tile_bytes;
+    uint64_t pitch_dst, pitch_src;  // bytes between rows
+    uint32_t rows, w;               // w: 1, 4, 8, 12 or 16 bytes
+};
+struct CopyArgs {
+    CopyRegionArgs r[COPY_MAX_REGIONS];
+    uint32_t n_regions;
+    const uint32_t *src_idx;
+    const uint32_t *dst_idx;  // or null: i
+    uint64_t n, B_src, B_dst;  // entries whose indices are out of range are skipped
+    int8_t *dense;            // qg_vec_track_dense on the destination (TILE, no padding slots; region 0 is the state): its rows rewritten, or null
+    uint32_t D, N, has_z;
+};
+hipError_t copy_envs(const CopyArgs &a, hipStream_t s);
 hipError_t masks_fill(const uint8_t *success, uint8_t *out, uint64_t B, uint32_t num_actions, hipStream_t s);
 hipError_t fault_any(const uint32_t *error, uint64_t B, uint32_t *scratch, uint32_t *out_host, hipStream_t s);
 hipError_t step_outputs(const float *reward, const uint8_t *done, const uint8_t *success, float *rewards_out, uint8_t *dones_out, uint8_t *success_out,

@@ -7,6 +7,7 @@
 #pragma once
 
 #include <stdint.h>
+#include <stdio.h>
 
 #include "qgym_internal.hpp"
 
@@ -119,6 +120,57 @@ inline int handle_plan(const qg_config &cfg, uint64_t batch, HandlePlan &p, cons
     p.has_done_list = p.layout == LAYOUT_TILE || p.layout == LAYOUT_TILE64 || p.layout == LAYOUT_PAULI;
     if (!p.state_bytes) p.state_bytes = p.stride_bytes * batch;
     return QG_OK;
+}
+
+// ---- qg_vec_copy_envs: where one env's resident state lies (kernels_copy.hip) -------------------------------------------------------
+// Every resident layout is tiles of 64 envs; a tile is a sequence of regions, each `rows` rows of 64 lanes x `w` bytes, env e at lane e & 63
+// of tile e >> 6.  LF8 / PERM (8 bytes per env) are tiles of one row of 8-byte lanes.
+struct CopyRegion {
+    uint32_t offset;  // bytes from the start of the tile
+    uint32_t rows;
+    uint32_t w;       // bytes per lane in every row (4, 8, 12 or 16)
+};
+constexpr uint32_t COPY_MAX_STATE_REGIONS = 3;
+struct CopyLayout {
+    CopyRegion r[COPY_MAX_STATE_REGIONS];
+    uint32_t n = 0;
+    uint32_t tile_bytes = 0;
+};
+inline CopyLayout copy_layout(const HandlePlan &p) {
+    CopyLayout c;
+    auto add = [&c](uint32_t rows, uint32_t w) {
+        c.r[c.n++] = CopyRegion{c.tile_bytes, rows, w};
+        c.tile_bytes += rows * 64u * w;
+    };
+    switch (p.layout) {
+    case LAYOUT_TILE: add((p.has_z ? 2 * p.nxp : p.nxp) / 4u, 16); break;  // R / 4 groups of four uint32 row slots (kernels_qm.hip)
+    case LAYOUT_TILE64: add(p.nxp / 2u, 16); break;                        // two uint64 rows per group (kernels_qm64.hip)
+    case LAYOUT_PERMB: add(p.nxp, 16); break;                              // 16 entries per group (kernels_perm.hip)
+    case LAYOUT_LFD: add(2 * p.nxp, 16); break;                            // matrix, then inverse (kernels_lfd.hip)
+    case LAYOUT_LF8:
+    case LAYOUT_PERM: add(1, 8); break;
+    case LAYOUT_PAULI: {  // PTLayout (kernels_pauli_tile.hip): qubit records, rotation records, DAG bookkeeping
+        const uint32_t meta = p.pt_rm > 16 ? 3u : 1u;
+        if (p.pauli_compact) {
+            add(p.pt_nq, 12);
+            add(p.pt_rm, 8);
+            add(meta, 16);
+        } else {
+            add(p.pt_nq + p.pt_rm + meta, 16);
+        }
+        break;
+    }
+    default: break;
+    }
+    return c;
+}
+// what qg_plan_query(QG_PLAN_COPY_ENVS) answers: the kernel and the state regions it walks, "rows x w" each
+inline void copy_kernel_name(const HandlePlan &p, char *out, size_t cap) {
+    const CopyLayout c = copy_layout(p);
+    int at = snprintf(out, cap, "copy_envs_kernel [");
+    for (uint32_t i = 0; i < c.n && at >= 0 && (size_t)at < cap; ++i)
+        at += snprintf(out + at, cap - (size_t)at, "%s%ux%u", i ? " " : "", c.r[i].rows, c.r[i].w);
+    if (at >= 0 && (size_t)at < cap) snprintf(out + at, cap - (size_t)at, "]");
 }
 
 // ---- step kernels ------------------------------------------------------------------------------------------------------------------

@@ -137,6 +137,49 @@ class VecEnv:
         _lib.check(self._L.qg_vec_get_state(self._h, out.data_ptr(), code, n, 1, self._stream()))
         return out
 
+    def copy_envs(self, src: "VecEnv", src_idx, dst_idx=None):
+        """Env::clone, batched (`qg_vec_copy_envs`): env dst_idx[i] of this batch becomes a copy of env src_idx[i] of `src` (which may be
+        `self`) -- state, flags, depth, reward, solution log, layer records, PauliEnv bookkeeping.  `dst_idx=None` means 0 .. n-1.  Sources may
+        repeat, destinations may not, and within one handle no index may be both.  The copy carries no RNG position: later draws of env j
+        come from this handle's stream for j.  Indices given as CPU tensors / arrays are checked here; device tensors are used as they are
+        (stream-ordered, capturable; out-of-range entries are skipped on the device)."""
+        if not isinstance(src, VecEnv):
+            raise TypeError("copy_envs: `src` must be a VecEnv")
+        idx = []
+        for name, t, bound in (("src_idx", src_idx, src.batch), ("dst_idx", dst_idx, self.batch)):
+            if t is None:
+                idx.append(None)
+                continue
+            if isinstance(t, torch.Tensor) and t.is_cuda:
+                if t.device != self.device:
+                    raise ValueError(f"copy_envs: {name} must live on the env's device")
+                if t.dtype not in (torch.int32, torch.int64):
+                    raise TypeError(f"copy_envs: {name} must be int32 or int64")
+                idx.append(t.reshape(-1).to(torch.int32).contiguous())
+                continue
+            a = np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t).reshape(-1)
+            if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() >= bound):
+                raise ValueError(f"copy_envs: {name} must hold integers in [0, {bound})")
+            idx.append(a.astype(np.int64))
+        s, d = idx
+        n = int(s.numel() if isinstance(s, torch.Tensor) else s.size)
+        if d is not None and int(d.numel() if isinstance(d, torch.Tensor) else d.size) != n:
+            raise ValueError("copy_envs: src_idx and dst_idx differ in length")
+        if n > self.batch:
+            raise ValueError(f"copy_envs: {n} copies into {self.batch} envs")
+        if not isinstance(s, torch.Tensor) and not isinstance(d, torch.Tensor):
+            dst_host = np.arange(n) if d is None else d
+            if np.unique(dst_host).size != n:
+                raise ValueError("copy_envs: a destination repeats")
+            if src is self and np.intersect1d(dst_host, s).size:
+                raise ValueError("copy_envs: within one handle no env may be both a source and a destination")
+        dev = [None if t is None else t if isinstance(t, torch.Tensor) else torch.as_tensor(t.astype(np.int32), device=self.device)
+               for t in (s, d)]
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qg_vec_copy_envs(self._h, src._h, dev[0].data_ptr() if n else None,
+                                                dev[1].data_ptr() if dev[1] is not None and n else None, n, self._stream()))
+        self._copy_idx = dev  # the device copies are read by the launch in flight
+
     def reset(self, seed: int = 0):
         _lib.check(self._L.qg_vec_reset(self._h, int(seed) & (2**64 - 1), self._stream()))
 
