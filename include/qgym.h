@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
- * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs (additions only) */
+ * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -366,6 +366,25 @@ int qg_widen_dense(const int8_t *obs_dev, uint64_t n_elems, void *out_dev, int o
 int qg_sample_actions(const void *logits_dev, int logits_dtype, uint64_t ld, uint64_t batch, uint32_t num_actions, const uint8_t *mask_dev,
                       uint64_t seed, uint64_t counter, const uint64_t *clock_dev, void *actions_dev, int action_dtype, float *logp_dev,
                       float *entropy_dev, int32_t value_col, float *values_dev, void *stream);
+/* The selection step of a beam search: from the `width` beams x num_actions actions of every group keep the `width` best continuations as
+ * (parent env, action) pairs -- src_idx_dev of qg_vec_copy_envs and actions_dev of qg_vec_step.  Group g owns the `width` consecutive slots
+ * g*width .. g*width + width-1 of a batch of n_groups*width envs.  logp_dev: [batch, ld] of `logp_dtype` (f32 / bf16 / f16), ld >= num_actions,
+ * the per-action score of each slot (normally log_softmax of the policy's logits); cum_dev f32[batch]: each slot's score so far; live_dev
+ * u8[batch]: != 0 where the slot holds a beam.  The rules (tests/beammodel.py restates them in numpy; results agree bit for bit):
+ *   - A candidate is (live slot b, action a < num_actions) with score cum[b] + (float)logp[b, a]: one f32 addition, round to nearest, not
+ *     contracted with anything.  A candidate whose score is NaN or -inf does not exist (a caller masks an action by scoring it -inf).
+ *   - The candidates of a group are ordered by score descending (-0 = +0), ties by slot ascending, then by action ascending.  No randomness;
+ *     the result does not depend on the launch geometry.
+ *   - Output slot j of the group (env g*width + j) receives candidate j: parent_dev = the BATCH-WIDE env index of its slot, actions_dev = its
+ *     action, cum_out_dev = its score (the sum's own bits), live_out_dev = 1.  Slots past the number of candidates get parent = their own
+ *     index, action = num_actions (out of range: "no gate", clifford.rs:324), cum_out = -inf, live_out = 0.
+ *   - Inputs and outputs may not alias.
+ * Limits: width <= 64 and width * num_actions <= 14 336 (64 beams x 224 actions: a group's candidates live in 56 KiB of one workgroup's LDS),
+ * n_groups * width < 2^32; QG_ERR_UNSUPPORTED beyond, QG_ERR_INVALID for null pointers, zero sizes, ld < num_actions or an unknown dtype.
+ * Stream-ordered on `stream`, one launch (one workgroup per group), no synchronisation, capturable into a hipGraph. */
+int qg_beam_select(const void *logp_dev, int logp_dtype, uint64_t ld, uint32_t num_actions, uint64_t n_groups, uint32_t width,
+                   const float *cum_dev, const uint8_t *live_dev, uint32_t *parent_dev, void *actions_dev, int action_dtype,
+                   float *cum_out_dev, uint8_t *live_out_dev, void *stream);
 /* Generalised advantage estimation over a [n_steps, batch] rollout (f32, done_t = the episode ended
  * with step t): delta_t = r_t + gamma*V_{t+1}*(1-done_t) - V_t, A_t = delta_t +
  * gamma*lambda*(1-done_t)*A_{t+1}, returns = A + V.  last_values_dev: V after the last step

@@ -66,6 +66,39 @@ def sample_actions(logits: torch.Tensor, seed: int, counter: int, num_actions: O
     return actions, logp, entropy, values
 
 
+def beam_select(logp: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, width: int, num_actions: Optional[int] = None,
+                parent: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None, cum_out: Optional[torch.Tensor] = None,
+                live_out: Optional[torch.Tensor] = None):
+    """The selection step of a beam search (`qg_beam_select`): the batch is groups of `width` consecutive envs; from every group's live
+    slots x actions keep the `width` best continuations by `cum[b] + logp[b, a]` (f32; ties by slot, then action; NaN / -inf = no such
+    candidate).  logp: [B, >= num_actions] f32 / bf16 / f16 with unit column stride; cum: f32 [B]; live: uint8 / bool [B].
+    Returns (parent int32 [B] -- batch-wide env indices, for `VecEnv.copy_envs`; actions int32 [B] -- num_actions where a slot stays empty;
+    cum_out f32 [B]; live_out uint8 [B]).  Preallocated outputs may be passed (actions int32 or int64); they may not alias the inputs."""
+    if logp.dim() != 2 or logp.stride(1) != 1:
+        raise ValueError("logp must be [B, >=num_actions] with unit column stride")
+    B, dev, W = logp.shape[0], logp.device, int(width)
+    A = int(num_actions) if num_actions is not None else logp.shape[1]
+    if W < 1 or B % W:
+        raise ValueError(f"beam_select: {B} envs do not divide into groups of {W}")
+    if live.dtype == torch.bool:
+        live = live.view(torch.uint8)
+    for name, t, dt in (("cum", cum, torch.float32), ("live", live, torch.uint8)):
+        if t.dtype != dt or t.numel() != B or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"beam_select: {name} must be a contiguous [B] {dt} tensor on logp's device")
+    parent = torch.empty(B, dtype=torch.int32, device=dev) if parent is None else parent
+    actions = torch.empty(B, dtype=torch.int32, device=dev) if actions is None else actions
+    cum_out = torch.empty(B, dtype=torch.float32, device=dev) if cum_out is None else cum_out
+    live_out = torch.empty(B, dtype=torch.uint8, device=dev) if live_out is None else live_out
+    for name, t, dts in (("parent", parent, (torch.int32,)), ("actions", actions, (torch.int32, torch.int64)), ("cum_out", cum_out, (torch.float32,)),
+                         ("live_out", live_out, (torch.uint8,))):
+        if t.dtype not in dts or t.numel() != B or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"beam_select: {name} must be a contiguous [B] tensor of {' / '.join(str(d) for d in dts)} on logp's device")
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_beam_select(logp.data_ptr(), _DT[logp.dtype], logp.stride(0), A, B // W, W, cum.data_ptr(), live.data_ptr(), parent.data_ptr(),
+                                          actions.data_ptr(), act_dt, cum_out.data_ptr(), live_out.data_ptr(), _stream_ptr()))
+    return parent, actions, cum_out, live_out
+
+
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,
         gae_lambda: float, advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None):
     """GAE(lambda) over a [T, B] rollout; `dones[t]` = the episode ended with step t.  Returns (advantages, returns)."""

@@ -1,0 +1,187 @@
+// kernels_search.hip -- qg_beam_select: the selection step of a beam search over a policy's log-probabilities.  From the W beams x A actions
+// of one target pick the W best continuations as (parent env, action) pairs, the operands of qg_vec_copy_envs and qg_vec_step, without
+// leaving the device.  The rules are stated in include/qgym.h; tests/beammodel.py restates them in numpy.
+//
+// One workgroup per group.  A candidate is the flat index i = slot * A + action of its group; its rank is decided by ONE 64-bit key
+//   key(i) = order(score) << 32 | (0xFFFFFFFF - i)       order: f32 -> uint32, monotone, -0 = +0, 0 = "no such candidate"
+// so "score descending, then slot, then action ascending" is "key descending", and keys of different candidates differ: whatever way the
+// candidates are dealt to lanes and waves, the W largest keys are the same W candidates in the same order.
+//   1. every thread computes order(score) of its candidates (i = tid, tid + NT, ...: consecutive lanes, consecutive LDS words) into LDS and
+//      keeps its largest key;
+//   2. every wave extracts the W largest keys of ITS candidates: W rounds of a 64-lane max (cross-lane, no LDS, no barrier); the lane that
+//      owned the round's winner looks for its next key below it (its own LDS words only);
+//   3. one barrier, then the NW sorted lists (NW * W <= NT keys) are merged by counting: the thread that holds key k writes output slot
+//      #{keys > k} if that is below W.
+// Plain vector loads and stores only.
+#include <hip/hip_fp16.h>
+
+#include "device_common.hpp"
+#include "qgym_host.hpp"
+
+namespace qg {
+
+constexpr uint32_t BEAM_MAX_WIDTH = 64;      // one lane of a wave per output slot
+constexpr uint32_t BEAM_MAX_CAND = 14336;    // width * num_actions: 56 KiB of order words (64 beams x 224 actions)
+constexpr uint32_t BEAM_MAX_WAVES = 8;
+
+struct BeamArgs {
+    const void *logp;
+    const float *cum;
+    const uint8_t *live;
+    uint32_t *parent;
+    void *actions;
+    float *cum_out;
+    uint8_t *live_out;
+    uint64_t ld;
+    uint32_t A, W, n;  // n = W * A
+    int32_t act64;
+};
+
+template <typename LT>
+__device__ inline float beam_to_float(LT v);
+template <>
+__device__ inline float beam_to_float<float>(float v) { return v; }
+template <>
+__device__ inline float beam_to_float<uint16_t>(uint16_t v) { return __uint_as_float((uint32_t)v << 16); }  // bf16
+template <>
+__device__ inline float beam_to_float<__half>(__half v) { return __half2float(v); }
+
+// larger score <=> larger word; NaN and -inf (a masked action) have no word; every other score's word is >= 0x00800000
+__device__ inline uint32_t beam_order(float score) {
+    if (score != score || score == -__builtin_huge_valf()) return 0u;
+    uint32_t u = __float_as_uint(score);
+    if (u == 0x80000000u) u = 0u;  // -0 ties with +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline uint64_t beam_key(uint32_t order, uint32_t i) { return ((uint64_t)order << 32) | (uint64_t)(0xFFFFFFFFu - i); }
+
+__device__ inline uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64), lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+template <typename LT>
+__global__ __launch_bounds__(64 * BEAM_MAX_WAVES) void beam_select_kernel(const BeamArgs a) {
+    extern __shared__ uint64_t beam_lds[];
+    const uint32_t tid = threadIdx.x, NT = blockDim.x, lane = tid & (QG_WAVE - 1), wave = tid >> 6, NW = NT >> 6;
+    uint64_t *merged = beam_lds;                                         // [NW][W] each wave's keys, descending, 0 = none
+    uint32_t *order = reinterpret_cast<uint32_t *>(beam_lds + NW * a.W);  // [n]
+    const uint64_t slot0 = (uint64_t)blockIdx.x * a.W;                    // the group's first env
+    const LT *logp = reinterpret_cast<const LT *>(a.logp);
+
+    // 1. scores.  (slot, action) of candidate i without a division per candidate: i advances by NT = qs * A + qa
+    uint32_t s = tid / a.A, act = tid - s * a.A;
+    const uint32_t qs = NT / a.A, qa = NT - qs * a.A;
+    uint64_t cur = 0;  // this thread's largest key not yet extracted
+    for (uint32_t i = tid; i < a.n; i += NT) {
+        uint32_t o = 0;
+        if (a.live[slot0 + s]) o = beam_order(a.cum[slot0 + s] + beam_to_float<LT>(logp[(slot0 + s) * a.ld + act]));
+        order[i] = o;
+        if (o) {
+            const uint64_t k = beam_key(o, i);
+            cur = k > cur ? k : cur;
+        }
+        act += qa;
+        s += qs;
+        if (act >= a.A) {
+            act -= a.A;
+            s += 1;
+        }
+    }
+
+    // 2. the wave's W largest keys; lane r keeps the r-th.  A thread's keys leave in descending order, so "not yet extracted" = "below the
+    // last one extracted from this thread"
+    uint64_t mine = 0;
+    for (uint32_t r = 0; r < a.W; ++r) {
+        const uint64_t m = wave_max_u64(cur);
+        if (m == 0) break;  // (the same in every lane)
+        if (lane == r) mine = m;
+        if (cur == m) {
+            uint64_t next = 0;
+            for (uint32_t i = tid; i < a.n; i += NT) {
+                const uint32_t o = order[i];
+                const uint64_t k = beam_key(o, i);
+                if (o && k < m && k > next) next = k;
+            }
+            cur = next;
+        }
+    }
+    if (lane < a.W) merged[wave * a.W + lane] = mine;
+    __syncthreads();
+
+    // 3. merge by counting
+    const uint32_t L = NW * a.W;  // <= NT
+    const uint64_t k = tid < L ? merged[tid] : 0;
+    uint32_t rank = 0, n_cand = 0;
+    for (uint32_t j = 0; j < L; ++j) {
+        const uint64_t o = merged[j];
+        n_cand += o != 0;
+        rank += o > k;
+    }
+    if (k && rank < a.W) {
+        const uint32_t i = 0xFFFFFFFFu - (uint32_t)k;
+        const uint32_t ps = i / a.A, pa = i - ps * a.A;
+        const uint64_t p = slot0 + ps, out = slot0 + rank;
+        a.parent[out] = (uint32_t)p;
+        if (a.act64) reinterpret_cast<int64_t *>(a.actions)[out] = (int64_t)pa;
+        else reinterpret_cast<int32_t *>(a.actions)[out] = (int32_t)pa;
+        a.cum_out[out] = a.cum[p] + beam_to_float<LT>(logp[p * a.ld + pa]);  // the same single f32 addition as in 1.
+        a.live_out[out] = 1;
+    }
+    if (tid < a.W && tid >= n_cand) {  // fewer candidates than slots: the rest hold no beam
+        const uint64_t out = slot0 + tid;
+        a.parent[out] = (uint32_t)out;
+        if (a.act64) reinterpret_cast<int64_t *>(a.actions)[out] = (int64_t)a.A;
+        else reinterpret_cast<int32_t *>(a.actions)[out] = (int32_t)a.A;  // out of range: "no gate" (clifford.rs:324)
+        a.cum_out[out] = -__builtin_huge_valf();
+        a.live_out[out] = 0;
+    }
+}
+
+}  // namespace qg
+
+using namespace qg;
+
+extern "C" int qg_beam_select(const void *logp_dev, int logp_dtype, uint64_t ld, uint32_t num_actions, uint64_t n_groups, uint32_t width,
+                              const float *cum_dev, const uint8_t *live_dev, uint32_t *parent_dev, void *actions_dev, int action_dtype,
+                              float *cum_out_dev, uint8_t *live_out_dev, void *stream) {
+    if (!logp_dev || !cum_dev || !live_dev || !parent_dev || !actions_dev || !cum_out_dev || !live_out_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (num_actions == 0 || width == 0 || ld < num_actions) return set_error(QG_ERR_INVALID, "bad shape: width and num_actions must be positive, ld >= num_actions");
+    if (action_dtype != QG_ACT_I32 && action_dtype != QG_ACT_I64) return set_error(QG_ERR_INVALID, "bad action dtype");
+    if (logp_dtype != QG_DT_F32 && logp_dtype != QG_DT_BF16 && logp_dtype != QG_DT_F16) return set_error(QG_ERR_INVALID, "logp dtype must be f32, bf16 or f16");
+    if (cum_out_dev == cum_dev || live_out_dev == live_dev) return set_error(QG_ERR_INVALID, "input and output arrays may not alias");
+    if (width > BEAM_MAX_WIDTH || (uint64_t)width * num_actions > BEAM_MAX_CAND)
+        return set_error(QG_ERR_UNSUPPORTED, "beam_select: width <= %u and width * num_actions <= %u supported", BEAM_MAX_WIDTH, BEAM_MAX_CAND);
+    if (n_groups > 0x7FFFFFFFull || n_groups * width > 0xFFFFFFFFull) return set_error(QG_ERR_UNSUPPORTED, "beam_select: too many envs for 32-bit parent indices");
+    if (n_groups == 0) return QG_OK;
+    BeamArgs a;
+    a.logp = logp_dev;
+    a.cum = cum_dev;
+    a.live = live_dev;
+    a.parent = parent_dev;
+    a.actions = actions_dev;
+    a.cum_out = cum_out_dev;
+    a.live_out = live_out_dev;
+    a.ld = ld;
+    a.A = num_actions;
+    a.W = width;
+    a.n = width * num_actions;
+    a.act64 = action_dtype == QG_ACT_I64;
+    // about 16 candidates per lane before another wave joins (each of the W rounds rescans one lane's share); the result does not depend on it
+    const uint32_t waves = a.n <= 1024u ? 1u : a.n <= 2048u ? 2u : a.n <= 6144u ? 4u : BEAM_MAX_WAVES;
+    const dim3 grid((unsigned)n_groups), block(64u * waves);
+    const size_t lds = (size_t)waves * width * sizeof(uint64_t) + (size_t)a.n * sizeof(uint32_t);  // <= 4 KiB + 56 KiB
+    hipStream_t s = (hipStream_t)stream;
+    switch (logp_dtype) {
+    case QG_DT_F32: hipLaunchKernelGGL(beam_select_kernel<float>, grid, block, lds, s, a); break;
+    case QG_DT_BF16: hipLaunchKernelGGL(beam_select_kernel<uint16_t>, grid, block, lds, s, a); break;
+    default: hipLaunchKernelGGL(beam_select_kernel<__half>, grid, block, lds, s, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}

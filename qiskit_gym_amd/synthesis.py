@@ -13,6 +13,9 @@ The search batch runs without inversions and observation permutations (both are 
 augmentations: clifford.rs:262-270, pauli.rs:653-665), so a solution is the winner's action sequence;
 PauliGym solutions also carry the rotations each gate released (pauli.rs:612-626), which are
 recovered by replaying the winners on a `track_solution` batch.
+
+`solve(..., beam_width=W)` searches differently: a deterministic beam search over the policy's log-probabilities, W beams per target, on
+the batched clone (`VecEnv.copy_envs`) and the device-side selection kernel (`collector.beam_select`); see `solve`.
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .collector import BasicPolicy, embed, embed_words, mid_head_sample, pack_embed_words, pack_embedding, pack_head, pack_mid, sample_actions
+from .collector import BasicPolicy, beam_select, embed, embed_words, mid_head_sample, pack_embed_words, pack_embedding, pack_head, pack_mid, sample_actions
 from .envs.gyms import ROTATION_MARKER
 from .vec import VecEnv
 
@@ -51,6 +54,7 @@ class BatchedSynthesis:
         self.device = device
         self._policy = policy
         self._vecs: Dict[tuple, VecEnv] = {}
+        self._beam = None  # ((targets, width), (two search batches, the winners)): the beam search's handles
         self._packed = None  # (vec, packed first layer, its f32 bias, packed middle layer, packed head): the policy-layer kernels' operands
         self.last_stats: dict = {}
 
@@ -104,14 +108,86 @@ class BatchedSynthesis:
         else:
             vec.set_state(np.repeat(np.asarray(states, dtype=np.int64), repeat, axis=0), fmt="i64")
 
+    def _beam_vecs(self, M: int, W: int):
+        """The beam search's handles: two batches of M * W envs that take turns as source and destination of the per-step copy, and the M
+        winners.  All three have the same constructor arguments (the rule of `copy_envs`; no layout choice depends on the batch size)."""
+        if self._beam is None or self._beam[0] != (M, W):
+            if self._beam is not None:
+                for v in self._beam[1]:
+                    v.close()
+            mk = lambda batch: self.env.vec(batch, device=self.device, add_inverts=False, add_perms=False, track_solution=True)  # noqa: E731
+            self._beam = ((M, W), (mk(M * W), mk(M * W), mk(M)))
+            self._policy = self._policy.to(device=self._beam[1][0].device, dtype=self.dtype)
+        return self._beam[1]
+
+    def _solve_beam(self, states: Sequence[Sequence[int]], W: int) -> List[Optional[List[int]]]:
+        M = len(states)
+        cur, oth, win = self._beam_vecs(M, W)
+        B, A, dev = cur.batch, cur.num_actions(), cur.device
+        T = int(cur._cfg.max_depth)
+        self._load(win, states, 1)  # the targets once; a target nobody solves keeps its slot, a solved one is overwritten by its winner
+        group = torch.arange(M, dtype=torch.int32, device=dev)
+        cur.copy_envs(win, group.repeat_interleave(W))
+        found = win.success.bool().clone()  # a target that is already solved needs no gates: its winner is the target itself
+        best = torch.where(found, 0.0, -float("inf")).to(torch.float32)
+        live = torch.zeros((M, W), dtype=torch.uint8, device=dev)
+        live[:, 0] = (~found).to(torch.uint8)
+        live = live.view(B)
+        cum = torch.zeros(B, dtype=torch.float32, device=dev)
+        ret = torch.zeros(B, dtype=torch.float32, device=dev)
+        nowhere = torch.full((M,), B, dtype=torch.int32, device=dev)  # out of range as a copy source: that entry is skipped
+        steps = 0
+        for t in range(T):
+            logits = self._policy(cur.observe_as(self.dtype))[0]
+            logp = torch.log_softmax(logits.float(), dim=1)
+            parent, act, cum, live = beam_select(logp, cum, live, W, A)
+            oth.copy_envs(cur, parent)
+            oth.step(act)
+            ret = ret[parent.long()] + oth.reward  # the return `solve` ranks by: the parent's plus this step's reward
+            solved = (live.bool() & oth.success.bool()).view(M, W)
+            live = live & (1 - oth.done)
+            score = torch.where(solved, ret.view(M, W), torch.full((M, W), -float("inf"), device=dev))
+            j = score.argmax(dim=1)  # the first of equal maxima: the lowest slot
+            val = score.gather(1, j.view(M, 1)).view(M)
+            better = val > best
+            win.copy_envs(oth, torch.where(better, group * W + j.to(torch.int32), nowhere))
+            best = torch.where(better, val, best)
+            found |= better
+            cur, oth = oth, cur
+            steps = t + 1
+            if t % 8 == 7 and not bool(live.any()):
+                break
+        for v in (cur, oth, win):
+            v.sync()
+        sols, lens = win.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
+        ok = found.cpu().numpy()
+        out = [[int(x) for x in sols[m, : lens[m]]] if ok[m] else None for m in range(M)]
+        gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
+        self.last_stats = {"beam_width": W, "targets": M, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0}
+        return out
+
     @torch.no_grad()
-    def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None) -> List[Optional[List[int]]]:
+    def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
+              beam_width: Optional[int] = None) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         fast: run the sampled searches' forward pass and draw on the policy-layer kernels (bf16 products; default: when they apply and the
-        batch has at least 4 096 envs); solutions are valid either way -- the env decides what solves a target, the policy only proposes."""
+        batch has at least 4 096 envs); solutions are valid either way -- the env decides what solves a target, the policy only proposes.
+
+        beam_width=W >= 1: beam search over the policy's log-probabilities instead (`deterministic`, `num_searches` and `fast` are then
+        ignored; no randomness).  Every target keeps up to W partial gate sequences ("beams"), at first the empty one.  Per step every beam is
+        scored `cum + log_softmax(logits)[a]` for each action a (f32), the W best continuations of a target survive (`collector.beam_select`:
+        ties by slot, then action), each as a copy of its parent env (`VecEnv.copy_envs`) stepped with its action.  A beam that ends
+        (`is_final`) leaves the search; if it ended with `success` it is a result, valued by its return like the sampled searches, and the
+        first result of the highest return seen so far (lowest slot among equals in one step) is the target's winner.  The search ends when
+        no beam is left or after max_depth steps.  The winner's own solution log is returned, so a PauliGym solution carries its rotation
+        markers without a replay.  Known limit: beams that reach the same state through commuting gates are not merged; they occupy a slot each."""
         M = len(states)
         if M == 0:
             return []
+        if beam_width is not None:
+            if int(beam_width) < 1:
+                raise ValueError("beam_width must be at least 1")
+            return self._solve_beam(states, int(beam_width))
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
         vec = self._vec(M * S, False)
         B, A, dev = vec.batch, vec.num_actions(), vec.device
@@ -182,9 +258,9 @@ class BatchedSynthesis:
             out.append([v for v in rep.solution(m) if v >= ROTATION_MARKER or v < A] if found[m] else None)
         return out
 
-    def synth(self, inputs, deterministic: bool = False, num_searches: int = 100):
+    def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
-        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches)
+        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, beam_width=beam_width)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):

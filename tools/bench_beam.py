@@ -1,0 +1,97 @@
+"""Beam search beside the sampled and the greedy search of BatchedSynthesis, with the reference's trained policies (tests/golden/policies):
+solved targets and mean gate count for beam_width 1 / 4 / 16, deterministic=True and num_searches=16 on the same targets; then the time of
+the selection kernel (`collector.beam_select`) beside the torch expression it replaces, alternating, on device events.  A record, not a gate.
+Run on the GPU box: python tools/bench_beam.py [--targets 1024]"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from test_reference_policies import MODELS, load  # noqa: E402
+
+import qiskit_gym_amd.envs as envs  # noqa: E402
+from qiskit_gym_amd.collector import beam_select  # noqa: E402
+from qiskit_gym_amd.synthesis import BatchedSynthesis, policy_from_reference_state_dict  # noqa: E402
+
+GYMS = {"clifford": "CliffordGym", "linear_function": "LinearFunctionGym", "permutation": "PermutationGym"}
+
+
+def search_table(M: int, difficulty: int):
+    for name in ("clifford_3q_custom", "lf_5_line", "perm_square_3x3"):
+        cfg, gateset, w = load(name)
+        kind = MODELS[name]
+        gym = getattr(envs, GYMS[kind])(cfg["num_qubits"], gateset, depth_slope=cfg["depth_slope"], max_depth=cfg["max_depth"])
+        syn = BatchedSynthesis(gym, policy_from_reference_state_dict(w), seed=1)
+        v = gym.vec(M, add_inverts=False, add_perms=False, track_solution=False, difficulty=difficulty)
+        v.reset(3)  # targets: random scrambles made on the device, read back in the set_state wire format
+        states = v.get_state("i64").cpu().numpy()
+        v.close()
+        runs = [("deterministic=True", dict(deterministic=True)), ("num_searches=16", dict(num_searches=16))]
+        runs += [(f"beam_width={W}", dict(beam_width=W)) for W in (1, 4, 16)]
+        for label, kw in runs:
+            syn.solve(states[:8], **kw)  # warm-up (library handles, the handles of this batch shape are built in the timed call)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            syn.solve(states, **kw)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            st = syn.last_stats
+            print(f"{name} x {M} targets (scrambles of {difficulty} gates), {label}: solved {st['solved']}/{M}, mean gates {st['mean_gates']:.2f}, "
+                  f"{st['steps']} steps, {dt * 1e3:.1f} ms incl. handle creation", flush=True)
+
+
+def torch_select(logp, cum, live, W, A):
+    """The tensor-library expression of the same selection (without the tie rule: topk's order among equal scores is unspecified)."""
+    B = logp.shape[0]
+    M = B // W
+    score = torch.where(live.bool()[:, None], cum[:, None] + logp[:, :A].float(), torch.full((), -float("inf"), device=logp.device)).view(M, W * A)
+    val, idx = score.topk(W, dim=1)
+    ok = val > -float("inf")
+    slot = idx // A
+    base = torch.arange(M, device=logp.device)[:, None] * W
+    own = base + torch.arange(W, device=logp.device)[None, :]
+    parent = torch.where(ok, base + slot, own).to(torch.int32).view(B)
+    act = torch.where(ok, idx - slot * A, torch.full_like(idx, A)).to(torch.int32).view(B)
+    return parent, act, val.reshape(B), ok.to(torch.uint8).view(B)
+
+
+def select_times(reps: int = 200):
+    for M, W, A in ((1024, 16, 27), (1024, 16, 170), (1024, 64, 170), (4096, 16, 170), (64, 64, 222)):
+        B = M * W
+        g = torch.Generator(device="cuda").manual_seed(M + W + A)
+        logp = torch.log_softmax(torch.randn((B, A), device="cuda", generator=g), dim=1)
+        cum = -torch.rand(B, device="cuda", generator=g) * 5
+        live = (torch.rand(B, device="cuda", generator=g) < 0.9).to(torch.uint8)
+        a, b = beam_select(logp, cum, live, W, A), torch_select(logp, cum, live, W, A)
+        torch.cuda.synchronize()
+        same = all(bool((x.to(torch.float32) == y.to(torch.float32)).all()) for x, y in zip(a, b))  # continuous scores: no ties
+        fns = {"beam_select": lambda: beam_select(logp, cum, live, W, A), "torch topk": lambda: torch_select(logp, cum, live, W, A)}
+        best = {k: float("inf") for k in fns}
+        for _ in range(5):  # alternate the two; the best of five windows each
+            for k, fn in fns.items():
+                fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                best[k] = min(best[k], e0.elapsed_time(e1) * 1e3 / reps)
+        print(f"select {M} targets x {W} beams x {A} actions (f32, eager, {reps} calls per window): beam_select {best['beam_select']:.1f} us, "
+              f"torch expression {best['torch topk']:.1f} us per call; same result: {same}", flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--targets", type=int, default=1024)
+    ap.add_argument("--difficulty", type=int, default=32)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the GPU"
+    search_table(args.targets, args.difficulty)
+    select_times()
