@@ -362,7 +362,14 @@ int qg_widen_dense(const int8_t *obs_dev, uint64_t n_elems, void *out_dev, int o
  * logits_dev: [batch, ld] of `logits_dtype` (f32 / bf16 / f16), ld >= num_actions.  mask_dev:
  * [batch, num_actions] (1 = allowed; Env::masks) or NULL.  Outputs (each may be NULL except
  * actions): action, log-prob of it, entropy of the row, and values_dev[e] = logits[e, value_col]
- * (value_col >= 0: a value head computed by the same GEMM as the logits). */
+ * (value_col >= 0: a value head computed by the same GEMM as the logits).
+ * Logits: every finite value of the dtype (f16 up to +-65504, bf16 / f32 up to their largest: a logit - max that overflows counts as
+ * probability 0), any num_actions >= 1.  A -inf logit is a masked action, exactly as a 0 in mask_dev: probability 0, never drawn, p log p
+ * = 0 in the entropy.  A row without a live action (mask all 0, or every logit -inf) gives action 0, log-prob 0, entropy 0.  exp(logit - max)
+ * is the hardware's: it is 0 from about 87 below the maximum on, and such an action is not drawn either (its probability is below 2e-38).
+ * Ties of the race keys go to the lower action index.  Outside the contract: a row that holds NaN or +inf.  The call still terminates
+ * and writes an action in [0, num_actions) -- an action whose key is NaN is never the winner, a row in which no key is an ordered
+ * finite number gives action 0 -- but log-prob and entropy of such a row are unspecified (NaN, or the 0 of the empty row). */
 int qg_sample_actions(const void *logits_dev, int logits_dtype, uint64_t ld, uint64_t batch, uint32_t num_actions, const uint8_t *mask_dev,
                       uint64_t seed, uint64_t counter, const uint64_t *clock_dev, void *actions_dev, int action_dtype, float *logp_dev,
                       float *entropy_dev, int32_t value_col, float *values_dev, void *stream);
@@ -429,7 +436,14 @@ int qg_policy_embed_words(const uint64_t *words_dev, uint64_t batch, uint32_t ro
  * head W[value_row] . h[e] + b[value_row].  h_dev: bf16 [batch, ld_h], 16-byte aligned, ld_h % 8 == 0.  Limits
  * (qg_policy_head_packed_bytes returns 0 outside them): num_actions <= 222, in_features % 64 == 0, <= 512, packed head
  * <= 144 KiB.  qg_policy_pack_head re-orders W ([rows, ld] f32 / bf16) and the bias ([rows], same dtype, or NULL)
- * into MFMA fragment order: rows 0..num_actions-1 are the actions, row value_row (>= 0, any index) the value head. */
+ * into MFMA fragment order: rows 0..num_actions-1 are the actions, row value_row (>= 0, any index) the value head.
+ * Logits (this call and the qg_policy_mid_head_sample / qg_vec_mid_head_sample_step family): finite, |logit| <= 1e37 so that logit - max
+ * stays finite.  The padding rows that fill the last 32-action tile carry a bias of -1e30, and a logit below -1e29 is a MASKED action, as
+ * -inf is for qg_sample_actions: qg_policy_pack_head stores a bias at or below -1e30 (-inf, the dtype's lowest value used as a mask) as
+ * -1e30 -- -inf itself has no two-term bf16 form -- and a row whose largest logit lies below -1e29 has no live action: action 0, log-prob 0,
+ * entropy 0.  The bias is carried as two bf16 terms (16 significant bits); weights are bf16.  NaN and +inf (in W, the bias or h) are
+ * outside the contract, with the rule of qg_sample_actions: the call terminates, the action lies in [0, num_actions), a NaN logit never
+ * wins, log-prob and entropy of such a row are unspecified. */
 size_t qg_policy_head_packed_bytes(uint32_t num_actions, uint32_t in_features);
 /* after_mid != 0: pack for qg_policy_mid_head_sample (whose head fragments come out of an accumulator tile in a permuted k order) */
 int qg_policy_pack_head(const void *weight_dev, const void *bias_dev, int dtype, uint64_t ld, uint32_t in_features, uint32_t num_actions,

@@ -463,9 +463,9 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         // same constant), the sums feed a log-prob quoted to 1e-5
         const float ex = __builtin_amdgcn_exp2f(d * 1.44269504088896340736f);
         ssum += ex;
-        wsum += ex * d;
+        wsum += ex == 0.0f ? 0.0f : ex * d;  // a -inf logit (masked by value) has p log p = 0, not 0 * -inf
         const float q = -__builtin_amdgcn_logf(sample_uniform(base, i)) * __builtin_amdgcn_rcpf(ex);  // ex == 0 (logit far below the max): q = inf, never wins
-        if (q < best_q || best_a == 0xFFFFFFFFu) {
+        if (q < best_q) {  // as in head_draw: a key of inf (ex == 0) or NaN never wins, a row without a winner takes the `none` branch
             best_q = q;
             best_a = i;
             best_d = d;
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         }
     }
     if (!live || sl != 0) return;
-    const bool none = best_a == 0xFFFFFFFFu;  // every action masked: the env is finished (clifford.rs:349-351)
+    const bool none = best_a == 0xFFFFFFFFu;  // every action masked (by the mask or by -inf logits): the env is finished (clifford.rs:349-351)
     const int64_t act = none ? 0 : (int64_t)best_a;
     if (a.act64) reinterpret_cast<int64_t *>(a.actions)[env] = act;
     else reinterpret_cast<int32_t *>(a.actions)[env] = (int32_t)act;

@@ -441,6 +441,10 @@ __global__ __launch_bounds__(128) void embed_small_kernel(EmbedArgs a) {
 // =================================================================================================
 constexpr uint32_t HEAD_WAVES = 8;
 constexpr float HEAD_PAD_BIAS = -1.0e30f;
+// A bias at or below the padding value (-inf, the dtype's lowest: an action masked by value) is stored AS the padding value -- -inf has no
+// two-term bf16 split -- and a row whose maximum lies below HEAD_MASKED has no live action: action 0, log-prob 0, entropy 0, the `none`
+// branch of sample_kernel (kernels_collect.hip).
+constexpr float HEAD_MASKED = -1.0e29f;
 
 // Packed head: [k-step s <= K/16][tile t][lane][8] bf16; lane (r, h) element e of k-step s < K/16 = W[row(32t + r)][16s + 8h + e];
 // k-step K/16: element 0 / 1 of the h = 0 lanes = bias hi / lo.  row(p) = p for p < A, value_row for p = 32 tiles - 1, else padding.
@@ -462,7 +466,7 @@ __global__ __launch_bounds__(256) void pack_head_kernel(const WT *w, const WT *b
         const uint32_t k = xorder ? 32u * (s >> 1) + 16u * (s & 1u) + 8u * (e >> 2) + 4u * h + (e & 3u) : 16u * s + 8u * h + e;
         if (src >= 0) v = (float)w[(uint64_t)src * ld + k];
     } else if (s == ks && h == 0 && e < 2) {
-        const float b = src >= 0 ? (bias ? (float)bias[src] : 0.0f) : HEAD_PAD_BIAS;
+        const float b = src >= 0 ? (bias ? fmaxf((float)bias[src], HEAD_PAD_BIAS) : 0.0f) : HEAD_PAD_BIAS;
         const float hi = __bfloat162float(__float2bfloat16(b));
         v = e == 0 ? hi : b - hi;
     }
@@ -568,13 +572,14 @@ __device__ __forceinline__ int64_t head_draw(f32x16 (&acc)[TILES], const HeadArg
         best_d = take ? od : best_d;
     }
     const float v_other = head_xhalf(value);
-    const int64_t act = best_a == 0xFFFFFFFFu ? 0 : (int64_t)best_a;  // the env's action on both lane halves
+    const bool none = best_a == 0xFFFFFFFFu || m < HEAD_MASKED;  // no live action: the race ran among masked and padding rows
+    const int64_t act = none ? 0 : (int64_t)best_a;  // the env's action on both lane halves
     if (live && h == 0) {
         if (a.act64) reinterpret_cast<int64_t *>(a.actions)[env] = act;
         else reinterpret_cast<int32_t *>(a.actions)[env] = (int32_t)act;
         const float log_s = logf(ssum);
-        if (a.logp) a.logp[env] = best_d - log_s;
-        if (a.entropy) a.entropy[env] = log_s - wsum / ssum;
+        if (a.logp) a.logp[env] = none ? 0.0f : best_d - log_s;
+        if (a.entropy) a.entropy[env] = none ? 0.0f : log_s - wsum / ssum;
         if (a.values) a.values[env] = v_other;
     }
     return act;
@@ -1020,13 +1025,14 @@ __global__ __launch_bounds__(64 * MHS_WAVES, 1) void mid_head_small_kernel(MidHe
         best_a = take ? oa : best_a;
         best_d = take ? od : best_d;
     }
-    const int64_t act = best_a == 0xFFFFFFFFu ? 0 : (int64_t)best_a;
+    const bool none = best_a == 0xFFFFFFFFu || m < HEAD_MASKED;  // no live action (head_draw)
+    const int64_t act = none ? 0 : (int64_t)best_a;
     if (live && h == 0) {
         if (a.act64) reinterpret_cast<int64_t *>(a.actions)[env] = act;
         else reinterpret_cast<int32_t *>(a.actions)[env] = (int32_t)act;
         const float log_s = logf(ssum);
-        if (a.logp) a.logp[env] = best_d - log_s;
-        if (a.entropy) a.entropy[env] = log_s - wsum / ssum;
+        if (a.logp) a.logp[env] = none ? 0.0f : best_d - log_s;
+        if (a.entropy) a.entropy[env] = none ? 0.0f : log_s - wsum / ssum;
         if (a.values) a.values[env] = part[0][5][c];
     }
     if (ma.step.state) {  // wave-uniform
