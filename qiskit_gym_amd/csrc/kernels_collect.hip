@@ -544,7 +544,7 @@ int qg_vec_observe_dense_as(qg_vec *v, void *out_dev, int out_dtype, void *strea
     if (rc != QG_OK) return rc;
     QG_ON_DEVICE(v);
     const uint64_t obs = (uint64_t)info.obs_rows * info.obs_cols;
-    if (v->layout == LAYOUT_PAULI && (uint32_t)info.obs_cols <= 64u) {
+    if (v->plan.layout == LAYOUT_PAULI && (uint32_t)info.obs_cols <= 64u) {
         v->perm_draw = true;  // PauliEnv::observe draws a new qubit permutation (pauli.rs:657-662)
         const hipError_t e = ptile_observe_typed(v, out_dev, out_dtype, (hipStream_t)stream);
         v->perm_draw = false;
@@ -552,8 +552,8 @@ int qg_vec_observe_dense_as(qg_vec *v, void *out_dev, int out_dtype, void *strea
         HIP_TRY(e);
         return QG_OK;
     }
-    if (v->layout == LAYOUT_PAULI) {  // lane-group family or more than 64 columns: int8 observation, then widen
-        rc = ensure_scratch_public(v, v->B * obs);
+    if (v->plan.layout == LAYOUT_PAULI) {  // lane-group family or more than 64 columns: int8 observation, then widen
+        rc = ensure_scratch(v, v->B * obs);
         if (rc != QG_OK) return rc;
         rc = qg_vec_observe_dense(v, reinterpret_cast<int8_t *>(v->scratch), stream);
         if (rc != QG_OK) return rc;
@@ -561,12 +561,12 @@ int qg_vec_observe_dense_as(qg_vec *v, void *out_dev, int out_dtype, void *strea
     }
     uint32_t es = 0, one = 0;
     if (!dtype_info(out_dtype, es, one)) return set_error(QG_ERR_INVALID, "unknown output dtype %d", out_dtype);
-    if (v->layout == LAYOUT_TILE && v->D % (16 / es) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 15u) == 0) {
+    if (v->plan.layout == LAYOUT_TILE && v->plan.D % (16 / es) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 15u) == 0) {
         // hot layout: expand straight from the resident tiles, no packed intermediate
-        HIP_TRY(qm_export_typed(v->state, v->B, v->N, v->D, v->nxp, v->has_z, out_dev, es, one, (hipStream_t)stream));
+        HIP_TRY(qm_export_typed(v->state, v->B, v->N, v->plan.D, v->plan.nxp, v->plan.has_z, out_dev, es, one, (hipStream_t)stream));
         return QG_OK;
     }
-    rc = ensure_scratch_public(v, v->B * (uint64_t)info.packed_words_per_env * info.packed_word_bytes);
+    rc = ensure_scratch(v, v->B * (uint64_t)info.packed_words_per_env * info.packed_word_bytes);
     if (rc != QG_OK) return rc;
     rc = qg_vec_observe_packed(v, v->scratch, stream);
     if (rc != QG_OK) return rc;

@@ -1877,7 +1877,7 @@ static hipError_t pt_launch_init(const PTArgs &pa, hipStream_t s) {
 }
 
 #define PT_DISPATCH(FN)                                  \
-    switch (v->pt_nq * 100 + v->pt_rm) {                 \
+    switch (v->plan.pt_nq * 100 + v->plan.pt_rm) {       \
     case 408: return FN<4, 8>(pa, s);                    \
     case 416: return FN<4, 16>(pa, s);                   \
     case 808: return FN<8, 8>(pa, s);                    \
@@ -1916,8 +1916,8 @@ static hipError_t ptile_init(const qg_vec *v, const PTArgs &pa, hipStream_t s) {
 
 static void fill_obs(const qg_vec *v, const ObsArgs &a, PTObsArgs &pa) {
     pa.o = a;
-    pa.nq = v->pt_nq;
-    pa.rm = v->pt_rm;
+    pa.nq = v->plan.pt_nq;
+    pa.rm = v->plan.pt_rm;
     pa.max_rot = (uint32_t)v->cfg.max_rotations;
     pa.qubit_perms = v->d_qubit_perms;
     pa.perm_idx = v->perm_idx;
@@ -1933,7 +1933,7 @@ static void fill_obs(const qg_vec *v, const ObsArgs &a, PTObsArgs &pa) {
 // dense observation in `out_dtype`: row words into the handle's scratch, then the write-bound expansion
 static hipError_t ptile_dense_via_words(qg_vec *v, const ObsArgs &a, void *out, int out_dtype, hipStream_t s) {
     const uint64_t n_rows = a.B * 2ull * a.N;
-    if (ensure_scratch_public(v, n_rows * sizeof(uint64_t)) != QG_OK) return hipErrorOutOfMemory;
+    if (ensure_scratch(v, n_rows * sizeof(uint64_t)) != QG_OK) return hipErrorOutOfMemory;
     PTObsArgs pa;
     fill_obs(v, a, pa);
     pa.o.format = QG_FMT_U8;
@@ -1953,7 +1953,7 @@ hipError_t ptile_export(const qg_vec *v, const ObsArgs &a, hipStream_t s) {
         // same for the other bit-matrix layouts); 839 MB for 20 qubits x 65 536 envs, which the row-per-thread kernel below writes at 1.8 TB/s
         qg_vec *mv = const_cast<qg_vec *>(v);  // the scratch buffer is a cache, not state
         const uint64_t n_rows = a.B * 2ull * a.N;
-        if (ensure_scratch_public(mv, n_rows * sizeof(uint64_t)) != QG_OK) return hipErrorOutOfMemory;
+        if (ensure_scratch(mv, n_rows * sizeof(uint64_t)) != QG_OK) return hipErrorOutOfMemory;
         PTObsArgs pa;
         fill_obs(v, a, pa);
         hipLaunchKernelGGL(ptile_rowwords_kernel, dim3(grid_for(n_rows / 2, 256)), dim3(256), 0, s, pa, reinterpret_cast<uint64_t *>(mv->scratch));
@@ -2087,7 +2087,7 @@ int ptile_reset_seeded(qg_vec *v, uint64_t seed, bool only_done, hipStream_t s, 
     a.env_base = v->env_base;
     ga.difficulty = (uint32_t)v->difficulty;
     ga.pauli_difficulty = (uint32_t)(v->difficulty / std::max(v->cfg.pauli_diff_scale, 1));  // pauli.rs:557,392
-    ga.max_paulis = v->rmax_generate;
+    ga.max_paulis = v->plan.rmax_generate;
     ga.decay = v->cfg.num_qubits_decay;
     const int64_t d = (int64_t)v->cfg.depth_slope * v->difficulty;  // pauli.rs:578
     ga.depth_value = (int32_t)std::min<int64_t>(d, v->cfg.max_depth);
@@ -2105,14 +2105,14 @@ int ptile_reset_seeded(qg_vec *v, uint64_t seed, bool only_done, hipStream_t s, 
         ga.tree = (ga.difficulty >= plan::TREE_MIN_DRAWS && v->B / 32u >= 1u && pauli_tree_takes(1u, ga.difficulty, v->B, ga.n_cx)) ? 1u : 0u;
     }
     if (ga.tree) {
-        ga.tree_grid = reset_tree_grid_public(v, (uint32_t)(v->B / 32u));
-        ga.gen_grid = reset_second_grid_public(v, [](uint32_t count, const qg_vec *h) -> bool {
+        ga.tree_grid = reset_tree_grid(v, (uint32_t)(v->B / 32u));
+        ga.gen_grid = reset_second_grid(v, [](uint32_t count, const qg_vec *h) -> bool {
             return pauli_tree_takes(count, (uint32_t)h->difficulty, h->B, h->gen_ncx);
         });
         ga.count_out = v->count_seen;
-        ga.tree_kclk = kernel_clock_slot_public(v);
+        ga.tree_kclk = kernel_clock_slot(v);
     }
-    a.kclk = kernel_clock_slot_public(v);
+    a.kclk = kernel_clock_slot(v);
     a.kclk_waves = v->kclk_waves;
     HIP_TRY(ptile_generate(v, ga, s));
     return QG_OK;
@@ -2120,10 +2120,10 @@ int ptile_reset_seeded(qg_vec *v, uint64_t seed, bool only_done, hipStream_t s, 
 
 // scatter the per-env records into the tiled layout, upload, run the init kernel
 int ptile_upload(qg_vec *v, const HostNet &h, bool do_clean, int32_t depth_value, hipStream_t s) {
-    const uint32_t N = v->N, NQ = v->pt_nq, RM = v->pt_rm;
-    const bool compact = NQ <= 24 && RM == 8;  // PTLayout::COMPACT
+    const uint32_t N = v->N, NQ = v->plan.pt_nq, RM = v->plan.pt_rm;
+    const bool compact = v->plan.pauli_compact;  // PTLayout::COMPACT
     const size_t QB = compact ? 768 : 1024, RB = compact ? 512 : 1024, tile_bytes = NQ * QB + RM * RB + (RM > 16 ? 3072 : 1024);
-    std::vector<uint8_t> img(v->state_bytes, 0);
+    std::vector<uint8_t> img(v->plan.state_bytes, 0);
     for (uint64_t e = 0; e < v->B; ++e) {
         uint8_t *tile = img.data() + (e >> 6) * tile_bytes;
         const uint32_t lane = (uint32_t)(e & 63);
@@ -2141,8 +2141,8 @@ int ptile_upload(qg_vec *v, const HostNet &h, bool do_clean, int32_t depth_value
             uint8_t *rb = tile + NQ * QB;
             auto byte_at = [&](uint32_t b) -> uint8_t & { return rb[(b >> 3) * RB + lane * 8 + (b & 7u)]; };
             uint32_t wp[5] = {0, 0, 0, 0, 0}, plo = 0, phi = 0;
-            for (uint32_t k = 0; k < v->rmax; ++k) {
-                const PauliRot &r = h.rot[e * v->rmax + k];
+            for (uint32_t k = 0; k < v->plan.rmax; ++k) {
+                const PauliRot &r = h.rot[e * v->plan.rmax + k];
                 for (uint32_t q = 0; q < N; ++q) {
                     byte_at(2 * q) |= (uint8_t)(((r.x >> q) & 1u) << k);
                     byte_at(2 * q + 1) |= (uint8_t)(((r.z >> q) & 1u) << k);
@@ -2157,8 +2157,8 @@ int ptile_upload(qg_vec *v, const HostNet &h, bool do_clean, int32_t depth_value
             byte_at(57) = (uint8_t)phi;
             for (int j = 0; j < 5; ++j) byte_at(58 + j) = (uint8_t)wp[j];
         } else {
-            for (uint32_t k = 0; k < v->rmax; ++k) {
-                const PauliRot &r = h.rot[e * v->rmax + k];
+            for (uint32_t k = 0; k < v->plan.rmax; ++k) {
+                const PauliRot &r = h.rot[e * v->plan.rmax + k];
                 uint32_t g[4] = {r.x, r.z, r.phase, r.pred};
                 memcpy(tile + NQ * QB + k * RB + lane * 16, g, 16);
             }
@@ -2177,7 +2177,7 @@ int ptile_upload(qg_vec *v, const HostNet &h, bool do_clean, int32_t depth_value
             memcpy(mt + lane * 16, g, 16);
         }
     }
-    HIP_TRY(hipMemcpyAsync(v->state, img.data(), v->state_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(v->state, img.data(), v->plan.state_bytes, hipMemcpyHostToDevice, s));
     StepArgs a;
     memset(&a, 0, sizeof a);
     a.state = v->state;

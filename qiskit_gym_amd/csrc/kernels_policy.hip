@@ -1407,8 +1407,8 @@ using namespace qg;
 extern "C" {
 
 // Layouts whose resident rows are uint32 words in 16-byte groups of four, tiles of 64 envs: TILE, and LFD with N <= 32 (two regions per tile)
-static bool emb_layout(const qg_vec *v) { return v->layout == LAYOUT_TILE || (v->layout == LAYOUT_LFD && !v->w64); }
-static uint32_t emb_rows(const qg_vec *v) { return v->layout == LAYOUT_LFD ? 4u * v->nxp : (v->has_z ? 2 * v->nxp : v->nxp); }  // row slots per matrix
+static bool emb_layout(const qg_vec *v) { return v->plan.layout == LAYOUT_TILE || (v->plan.layout == LAYOUT_LFD && !v->plan.w64); }
+static uint32_t emb_rows(const qg_vec *v) { return v->plan.layout == LAYOUT_LFD ? 4u * v->plan.nxp : plan::row_slots(v->plan); }  // row slots per matrix
 #define QG_EMB_LAYOUTS "the bit-consuming first layer needs uint32 rows resident in tiles (CliffordEnv N <= 16, LinearFunctionEnv 8 < N <= 32)"
 
 size_t qg_vec_embed_packed_bytes(const qg_vec *v, uint32_t hidden) {
@@ -1420,7 +1420,7 @@ int qg_vec_pack_embedding(qg_vec *v, const void *weight_dev, int weight_dtype, u
     if (!v || !weight_dev || !packed_dev) return set_error(QG_ERR_INVALID, "null argument");
     if (!emb_layout(v)) return set_error(QG_ERR_UNSUPPORTED, QG_EMB_LAYOUTS);
     if (hidden == 0 || hidden % EMB_SLAB) return set_error(QG_ERR_INVALID, "hidden size must be a multiple of %u", EMB_SLAB);
-    if (ld < (uint64_t)v->D * v->D) return set_error(QG_ERR_INVALID, "weight rows are shorter than the observation (%u x %u)", v->D, v->D);
+    if (ld < (uint64_t)v->plan.D * v->plan.D) return set_error(QG_ERR_INVALID, "weight rows are shorter than the observation (%u x %u)", v->plan.D, v->plan.D);
     QG_ON_DEVICE(v);
     const uint32_t R = emb_rows(v);
     if (!v->embed_dump) HIP_TRY(hipMalloc(&v->embed_dump, 1024));  // see EmbedArgs::dump
@@ -1430,11 +1430,11 @@ int qg_vec_pack_embedding(qg_vec *v, const void *weight_dev, int weight_dtype, u
     __hip_bfloat16 *out = reinterpret_cast<__hip_bfloat16 *>(packed_dev);
     switch (weight_dtype) {
     case QG_DT_F32:
-        hipLaunchKernelGGL(pack_embed_kernel<float>, grid, block, 0, s, reinterpret_cast<const float *>(weight_dev), ld, hidden, R, v->N, v->D, (uint32_t)v->has_z, out);
+        hipLaunchKernelGGL(pack_embed_kernel<float>, grid, block, 0, s, reinterpret_cast<const float *>(weight_dev), ld, hidden, R, v->N, v->plan.D, (uint32_t)v->plan.has_z, out);
         break;
     case QG_DT_BF16:
-        hipLaunchKernelGGL(pack_embed_kernel<__hip_bfloat16>, grid, block, 0, s, reinterpret_cast<const __hip_bfloat16 *>(weight_dev), ld, hidden, R, v->N, v->D,
-                           (uint32_t)v->has_z, out);
+        hipLaunchKernelGGL(pack_embed_kernel<__hip_bfloat16>, grid, block, 0, s, reinterpret_cast<const __hip_bfloat16 *>(weight_dev), ld, hidden, R, v->N, v->plan.D,
+                           (uint32_t)v->plan.has_z, out);
         break;
     default: return set_error(QG_ERR_INVALID, "weight dtype must be f32 or bf16");
     }
@@ -1464,11 +1464,11 @@ static int embed_impl(qg_vec *v, const void *packed_dev, const float *bias_dev, 
     a.relu = relu ? 1u : 0u;
     a.obs = nullptr;
     a.N = v->N;
-    a.D = v->has_z ? 2u * v->N : v->N;
-    a.has_z = v->has_z ? 1u : 0u;
+    a.D = v->plan.has_z ? 2u * v->N : v->N;
+    a.has_z = v->plan.has_z ? 1u : 0u;
     const uint32_t G = R / 4;
-    a.region = v->layout == LAYOUT_LFD ? v->inverted : nullptr;
-    a.tile_groups = v->layout == LAYOUT_LFD ? 2u * G : G;
+    a.region = v->plan.layout == LAYOUT_LFD ? v->inverted : nullptr;
+    a.tile_groups = v->plan.layout == LAYOUT_LFD ? 2u * G : G;
     const size_t lds = (size_t)emb_groups(R) * 8u * 2u * 64u * 16u;  // <= 128 KiB (R <= 32)
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v->device);
@@ -1756,11 +1756,11 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
     m.K1 = in_features;
     if (step_of) {  // Env::step with the drawn action in the same launch
         qg_vec *v = step_of;
-        fill_step_args_public(v, m.step);
+        fill_step_args(v, m.step);
         m.step.rewards_seq = step_rewards;
         m.step.dones_seq = step_dones;
-        m.step_groups = (v->has_z ? 2u * v->nxp : v->nxp) / 4u;
-        m.step_has_z = v->has_z ? 1u : 0u;
+        m.step_groups = plan::row_slots(v->plan) / 4u;
+        m.step_has_z = v->plan.has_z ? 1u : 0u;
         m.done_list = v->done_list;
         m.done_count = v->done_list + v->B;
     } else {
@@ -1834,8 +1834,8 @@ static int mid_head_step_impl(qg_vec *v, const void *h_dev, uint64_t ld_h, uint3
                               const void *packed_head_dev, uint64_t seed, uint64_t counter, void *actions_dev, int action_dtype, float *logp_dev,
                               float *entropy_dev, float *values_dev, float *rewards_dev, uint8_t *dones_dev, const uint64_t *reset_seed, void *stream) {
     if (!v) return set_error(QG_ERR_INVALID, "null argument");
-    const bool inverts = v->flags & F_INVERTS;
-    if (v->layout != LAYOUT_TILE || (!inverts && !v->bad) || !v->done_list)
+    const bool inverts = v->plan.flags & F_INVERTS;
+    if (v->plan.layout != LAYOUT_TILE || (!inverts && !v->bad) || !v->done_list)
         return set_error(QG_ERR_UNSUPPORTED, "the sampling kernel steps TILE-layout handles (CliffordEnv N <= 16; LinearFunctionEnv 8 < N <= 32 without add_inverts)");
     if (reset_seed && v->gates.empty() && v->difficulty)  // Uniform::new(0, 0) panics in the reference
         return set_error(QG_ERR_PANIC, "reset with an empty gateset (the reference panics in Uniform::new(0, 0))");
@@ -1844,7 +1844,7 @@ static int mid_head_step_impl(qg_vec *v, const void *h_dev, uint64_t ld_h, uint3
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v->device);
     // add_inverts (CliffordEnv's default): the step is the two-lanes-per-env kernel's, which the small-batch sampling kernel can run on its
     // own lanes (qm_inv2_body) when every env is symplectic; otherwise the sampling kernel and the env's own step launch
-    if (inverts && !(mid_head_is_small(v->B, in_features, cus) && v->has_z && !v->maybe_nonsymplectic)) {
+    if (inverts && !(mid_head_is_small(v->B, in_features, cus) && v->plan.has_z && !v->maybe_nonsymplectic)) {
         int rc = mid_head_impl(h_dev, ld_h, v->B, in_features, packed_mid_dev, mid_features, packed_head_dev, (uint32_t)v->gates.size(), seed, counter,
                                v->clock_dev, actions_dev, action_dtype, logp_dev, entropy_dev, values_dev, nullptr, nullptr, nullptr, nullptr, v->env_base, stream);
         if (rc == QG_OK) rc = qg_vec_rollout(v, actions_dev, action_dtype, 1, nullptr, rewards_dev, dones_dev, 0, stream);
@@ -1856,7 +1856,7 @@ static int mid_head_step_impl(qg_vec *v, const void *h_dev, uint64_t ld_h, uint3
     if (rc != QG_OK) return rc;
     v->step_index += 1;
     if (v->dense)  // qg_vec_track_dense: the sampling kernel's step does not write the dense observation (its policy reads the bits)
-        if (int rc2 = dense_refresh_public(v, (hipStream_t)stream)) return rc2;
+        if (int rc2 = dense_refresh(v, (hipStream_t)stream)) return rc2;
     // larger batches: the kernel left the list of finished envs, the reset is its own launch
     if (reset_seed && !mid_head_is_small(v->B, in_features, cus)) return qg_vec_reset_done(v, *reset_seed, stream);
     return QG_OK;

@@ -1360,7 +1360,7 @@ static hipError_t launch_step(const StepArgs &a, hipStream_t s) {
     const bool feat = a.flags & (F_TRACK | F_LAYERS);
     const bool seq = a.T != 1 || a.rewards_seq || a.dones_seq;
     const bool list = a.flags & F_DONE_LIST;
-    switch (plan::tile_step(a.flags, a.T, a.bad != nullptr, a.rewards_seq || a.dones_seq, a.num_actions, HAS_Z, NXP)) {  // qgym_plan.hpp
+    switch (plan::tile_step(false, plan::tile_inv_kernels(false, HAS_Z, NXP), a.flags, a.T, a.bad != nullptr, a.rewards_seq || a.dones_seq, a.num_actions)) {  // qgym_plan.hpp
     case plan::SK_QM_STEP1: {  // the env.step() path
         const dim3 lgrid = grid, lblock = block;
         if constexpr (QmRows<NXP, HAS_Z>::R % 16 == 0) {

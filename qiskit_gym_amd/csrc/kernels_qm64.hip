@@ -919,7 +919,7 @@ static hipError_t q64_launch_step(const StepArgs &a, hipStream_t s) {
     const dim3 grid(grid_for(a.B, 256)), block(256);
     const bool feat = a.flags & (F_TRACK | F_LAYERS), list = a.flags & F_DONE_LIST;
     const bool extra = feat || a.T != 1 || a.rewards_seq || a.dones_seq;
-    switch (plan::tile64_step(a.flags, a.T, a.bad != nullptr, a.rewards_seq || a.dones_seq, a.num_actions, HAS_Z)) {  // qgym_plan.hpp
+    switch (plan::tile_step(true, plan::tile_inv_kernels(true, HAS_Z, NS), a.flags, a.T, a.bad != nullptr, a.rewards_seq || a.dones_seq, a.num_actions)) {  // qgym_plan.hpp
     case plan::SK_Q64_STEP1:  // the env.step() path
         if (list && !a.done_mask) return hipErrorInvalidValue;  // (qgym_api.cpp step_leaves_done_list gives every list-leaving step a mask)
         if (feat && list) hipLaunchKernelGGL((q64_step1_kernel<NS, HAS_Z, true, true>), grid, block, 0, s, a);

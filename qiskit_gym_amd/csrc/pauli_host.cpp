@@ -82,7 +82,7 @@ static bool anticommute(const PauliRot &a, const PauliRot &b) { return (__builti
 
 static void host_net_init(const qg_vec *v, HostNet &h) {
     h.tab.assign((size_t)v->B * v->N * 2, 0);
-    h.rot.assign((size_t)v->B * v->rmax, PauliRot{0, 0, 0, 0});
+    h.rot.assign((size_t)v->B * v->plan.rmax, PauliRot{0, 0, 0, 0});
     h.meta.assign(v->B, PauliMeta{});
 }
 // PauliNetwork::new (pauli_network.rs:37-77) for env e
@@ -101,10 +101,10 @@ static int host_net_build(const qg_vec *v, HostNet &h, uint64_t e, const uint8_t
     const size_t R = labels.size();
     for (size_t k = 0; k < R; ++k) {
         std::string why;
-        PauliRot &r = h.rot[e * v->rmax + k];
+        PauliRot &r = h.rot[e * v->plan.rmax + k];
         if (!parse_label(labels[k], N, r, why)) return set_error(QG_ERR_PANIC, "env %llu rotation %zu: %s", (unsigned long long)e, k, why.c_str());
         for (size_t k2 = 0; k2 < k; ++k2)  // PauliDag::new (pauli_dag.rs:35-41): edge k -> k2 iff they do not commute
-            if (anticommute(r, h.rot[e * v->rmax + k2])) r.pred |= 1u << k2;
+            if (anticommute(r, h.rot[e * v->plan.rmax + k2])) r.pred |= 1u << k2;
     }
     PauliMeta &m = h.meta[e];
     m.alive = R >= 32 ? ~0u : ((1u << R) - 1u);
@@ -182,8 +182,8 @@ int pauli_reset_from(qg_vec *v, const uint8_t *tableaus, const char *labels, con
     host_net_init(v, h);
     size_t lp = 0;
     for (uint64_t e = 0; e < v->B; ++e) {
-        if (n_rot[e] < 0 || (uint32_t)n_rot[e] > v->rmax)
-            return set_error(QG_ERR_INVALID, "env %llu: %d rotations, this batch was planned for at most %u", (unsigned long long)e, n_rot[e], v->rmax);
+        if (n_rot[e] < 0 || (uint32_t)n_rot[e] > v->plan.rmax)
+            return set_error(QG_ERR_INVALID, "env %llu: %d rotations, this batch was planned for at most %u", (unsigned long long)e, n_rot[e], v->plan.rmax);
         std::vector<std::string> labs;
         for (int32_t k = 0; k < n_rot[e]; ++k) {
             if (!labels) return set_error(QG_ERR_INVALID, "labels is null");

@@ -36,12 +36,6 @@ int set_error(int code, const char *fmt, ...) {
     return code;
 }
 
-static uint32_t pow2ceil_log2(uint32_t x) {
-    uint32_t l = 0;
-    while ((1u << l) < x) ++l;
-    return l;
-}
-
 // ---- per-gate metric deltas (metrics.rs:64-123 with its guards) -----------------------------
 static void gate_deltas(const qg_gate &g, uint32_t N, int &dc, int &dg) {
     dc = dg = 0;
@@ -96,7 +90,7 @@ static uint32_t gate_ops(int env_kind, const qg_gate &g, uint32_t N) {
     return 0u;
 }
 
-int ensure_scratch_public(qg_vec *v, size_t bytes) {
+int ensure_scratch(qg_vec *v, size_t bytes) {
     if (bytes <= v->scratch_bytes) return QG_OK;
     if (v->scratch) {
         if (hipDeviceSynchronize() != hipSuccess || hipFree(v->scratch) != hipSuccess) {
@@ -140,6 +134,64 @@ static uint32_t tile_ops(int env_kind, const qg_gate &g, bool wide) {
     }
     if (wide) return (a & 63u) | ((q1 & 63u) << 6) | (m << 12);  // TILE64 (kernels_qm64.hip)
     return (a & 31u) | ((q1 & 31u) << 5) | (m << 10);
+}
+
+// qg_vec_set_kernel_clock: the slot of the launch about to be enqueued (the k-th one after the call), or null
+unsigned long long *kernel_clock_slot(const qg_vec *v) {
+    if (!v->kclk || v->kclk_next >= v->kclk_cap) return nullptr;
+    return v->kclk + 2ull * v->kclk_waves * (v->kclk_next++);
+}
+
+// Workgroups a reset_done launch sets aside for trees (InitArgs::tree_grid).  Every one of them costs a dispatch slot and ~2 us of a CU's third of its
+// LDS whether or not the list reaches it, and at three workgroups per CU whatever is dispatched late waits -- so the grid follows the list lengths
+// this handle's resets have reported (InitArgs::count_out: the latest launch that has finished; read without waiting): the length, four standard
+// deviations of a count that size and a margin, in steps of 64.  A longer list is walked in rounds: the grid's size never changes a result.
+uint32_t reset_tree_grid(const qg_vec *v, uint32_t most) {
+    const uint32_t seen = v->count_seen ? *(volatile const uint32_t *)v->count_seen : 0xFFFFFFFFu;
+    if (seen == 0xFFFFFFFFu) return most;
+    // A launch being CAPTURED keeps its grid for every replay (eager calls correct themselves at the next call): a capture made while few envs finish -- right
+    // after a reset, say -- must not bake a small grid in, or every later list is walked in many rounds.  TILE: the whole grid (its one-launch kernels fit
+    // seven workgroups per CU since round 5: idle tree workgroups cost nothing measurable, 9.15 against 9.2 us a pair); TILE64 / PauliEnv (three per CU: the
+    // whole grid costs 1.0 / 0.5 us a pair): at least half of it, all of it when the last launch saw nobody finish.
+    const bool captured = v->dl.captured();
+    if (captured && (v->plan.layout == LAYOUT_TILE || seen == 0)) return most;
+    const uint64_t want = (uint64_t)seen + 4ull * (uint64_t)std::sqrt((double)seen) + 32ull;
+    const uint64_t g = (want + 63ull) & ~63ull;
+    return (uint32_t)std::min<uint64_t>(most, std::max<uint64_t>(captured ? std::max<uint64_t>(64ull, most / 2) : 64ull, g));
+}
+
+void fill_step_args(const qg_vec *v, StepArgs &a) {
+    memset(&a, 0, sizeof a);
+    a.state = v->state;
+    a.gates = v->d_gates;
+    a.descs = v->d_descs;
+    a.depth = v->depth;
+    a.reward = v->reward;
+    a.done = v->done;
+    a.success = v->success;
+    a.inverted = v->inverted;
+    a.error = v->error;
+    a.sol = v->sol;
+    a.sol_len = v->sol_len;
+    a.layers = v->layers;
+    a.B = v->B;
+    a.seed = v->coin_seed;
+    a.step_index = v->step_index;
+    a.clock = v->clock_dev;
+    a.env_base = v->env_base;
+    a.bad = v->bad;
+    a.D = v->plan.D;
+    a.N = v->N;
+    a.num_actions = (uint32_t)v->gates.size();
+    a.T = 1;
+    a.flags = v->plan.flags | (v->maybe_nonsymplectic ? F_GJ : 0u);
+    a.sol_cap = v->sol_cap;
+    a.w[0] = v->cfg.w_n_cnots;
+    a.w[1] = v->cfg.w_n_layers_cnots;
+    a.w[2] = v->cfg.w_n_layers;
+    a.w[3] = v->cfg.w_n_gates;
+    a.pauli_layer_reward = v->cfg.pauli_layer_reward;
+    a.max_rotations = (uint32_t)v->cfg.max_rotations;
 }
 
 }  // namespace qg
@@ -227,46 +279,15 @@ static int vec_free_buffers(qg_vec *v) {
                     v->d_qubit_perms, v->d_act_perms, v->perm_idx, v->d_gen_tables, v->d_nonsymp, v->bad, v->done_list, v->done_list_alt, v->done_list_spare, v->done_mask[0], v->done_mask[1], v->mask_count, v->d_rowops, v->embed_dump, v->host_in, v->host_obs, v->fault_scratch};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    for (auto &g : v->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    v->graphs.clear();
+    drop_graphs(v);
     if (v->capture_stream) (void)hipStreamDestroy(v->capture_stream);
     if (v->fault_word) (void)hipHostFree(v->fault_word);
     if (v->count_seen) (void)hipHostFree(v->count_seen);
     return 0;
 }
 
-static int ensure_scratch(qg_vec *v, size_t bytes) { return qg::ensure_scratch_public(v, bytes); }
-
 // anything that changes the `done` flags other than a list-leaving step first drops the list
 static int drop_done_list(qg_vec *v, hipStream_t s) { return zero_list_length(v, v->done_list, v->dl.drop(), s); }
-
-// qg_vec_set_kernel_clock: the slot of the launch about to be enqueued (the k-th one after the call), or null
-static unsigned long long *kernel_clock_slot(const qg_vec *v) {
-    if (!v->kclk || v->kclk_next >= v->kclk_cap) return nullptr;
-    return v->kclk + 2ull * v->kclk_waves * (v->kclk_next++);
-}
-
-// Workgroups a reset_done launch sets aside for trees (InitArgs::tree_grid).  Every one of them costs a dispatch slot and ~2 us of a CU's third of its
-// LDS whether or not the list reaches it, and at three workgroups per CU whatever is dispatched late waits -- so the grid follows the list lengths
-// this handle's resets have reported (InitArgs::count_out: the latest launch that has finished; read without waiting): the length, four standard
-// deviations of a count that size and a margin, in steps of 64.  A longer list is walked in rounds: the grid's size never changes a result.
-static uint32_t reset_tree_grid(const qg_vec *v, uint32_t most) {
-    const uint32_t seen = v->count_seen ? *(volatile const uint32_t *)v->count_seen : 0xFFFFFFFFu;
-    if (seen == 0xFFFFFFFFu) return most;
-    // A launch being CAPTURED keeps its grid for every replay (eager calls correct themselves at the next call): a capture made while few envs finish -- right
-    // after a reset, say -- must not bake a small grid in, or every later list is walked in many rounds.  TILE: the whole grid (its one-launch kernels fit
-    // seven workgroups per CU since round 5: idle tree workgroups cost nothing measurable, 9.15 against 9.2 us a pair); TILE64 / PauliEnv (three per CU: the
-    // whole grid costs 1.0 / 0.5 us a pair): at least half of it, all of it when the last launch saw nobody finish.
-    const bool captured = v->dl.captured();
-    if (captured && (v->layout == LAYOUT_TILE || seen == 0)) return most;
-    const uint64_t want = (uint64_t)seen + 4ull * (uint64_t)std::sqrt((double)seen) + 32ull;
-    const uint64_t g = (want + 63ull) & ~63ull;
-    return (uint32_t)std::min<uint64_t>(most, std::max<uint64_t>(captured ? std::max<uint64_t>(64ull, most / 2) : 64ull, g));
-}
-
 
 static void fill_init_args(const qg_vec *v, InitArgs &a) {
     memset(&a, 0, sizeof a);
@@ -283,80 +304,44 @@ static void fill_init_args(const qg_vec *v, InitArgs &a) {
     a.layers_len = v->layers_len;
     a.gates = v->d_gates;
     a.B = v->B;
-    a.D = v->D;
+    a.D = v->plan.D;
     a.N = v->N;
-    a.log2L = v->log2L;
     a.num_actions = (uint32_t)v->gates.size();
     a.clock = v->clock_dev;
     a.env_base = v->env_base;
     a.bad = v->bad;
     a.rowops = v->d_rowops;
-    a.inverts = (v->flags & F_INVERTS) ? 1u : 0u;
-    a.check_symplectic = ((v->layout == LAYOUT_TILE || v->layout == LAYOUT_TILE64) && (v->flags & F_INVERTS)) ? 1u : 0u;
+    a.inverts = (v->plan.flags & F_INVERTS) ? 1u : 0u;
+    a.check_symplectic = (plan::is_tile(v->plan) && (v->plan.flags & F_INVERTS)) ? 1u : 0u;
 }
 
 static hipError_t launch_init(const qg_vec *v, const InitArgs &a_in, hipStream_t s) {
     InitArgs a = a_in;
     a.kclk = kernel_clock_slot(v);
     a.kclk_waves = v->kclk_waves;
-    switch (v->layout) {
-    case LAYOUT_LFD: return lfd_init(a, v->w64, v->nxp, v->d_descs, s);
+    switch (v->plan.layout) {
+    case LAYOUT_LFD: return lfd_init(a, v->plan.w64, v->plan.nxp, v->d_descs, s);
     case LAYOUT_LF8: return lf8_init(a, s);
     case LAYOUT_PERM: return perm_init(a, s);
-    case LAYOUT_PERMB: return permb_init(a, v->nxp, v->d_descs, s);
-    case LAYOUT_TILE: return qm_init(a, v->nxp, v->has_z, s);
-    case LAYOUT_TILE64: return q64_init(a, v->nxp, v->has_z, s);
+    case LAYOUT_PERMB: return permb_init(a, v->plan.nxp, v->d_descs, s);
+    case LAYOUT_TILE: return qm_init(a, v->plan.nxp, v->plan.has_z, s);
+    case LAYOUT_TILE64: return q64_init(a, v->plan.nxp, v->plan.has_z, s);
     default: return hipErrorInvalidValue;
     }
-}
-
-static void fill_step_args(const qg_vec *v, StepArgs &a) {
-    memset(&a, 0, sizeof a);
-    a.state = v->state;
-    a.gates = v->d_gates;
-    a.descs = v->d_descs;
-    a.depth = v->depth;
-    a.reward = v->reward;
-    a.done = v->done;
-    a.success = v->success;
-    a.inverted = v->inverted;
-    a.error = v->error;
-    a.sol = v->sol;
-    a.sol_len = v->sol_len;
-    a.layers = v->layers;
-    a.B = v->B;
-    a.seed = v->coin_seed;
-    a.step_index = v->step_index;
-    a.clock = v->clock_dev;
-    a.env_base = v->env_base;
-    a.bad = v->bad;
-    a.D = v->D;
-    a.N = v->N;
-    a.log2L = v->log2L;
-    a.num_actions = (uint32_t)v->gates.size();
-    a.T = 1;
-    a.flags = v->flags | (v->maybe_nonsymplectic ? F_GJ : 0u);
-    a.sol_cap = v->sol_cap;
-    a.w[0] = v->cfg.w_n_cnots;
-    a.w[1] = v->cfg.w_n_layers_cnots;
-    a.w[2] = v->cfg.w_n_layers;
-    a.w[3] = v->cfg.w_n_gates;
-    a.pauli_layer_reward = v->cfg.pauli_layer_reward;
-    a.max_rotations = (uint32_t)v->cfg.max_rotations;
 }
 
 static hipError_t launch_step(const qg_vec *v, const StepArgs &a_in, hipStream_t s) {
     StepArgs a = a_in;
     a.kclk = kernel_clock_slot(v);
     a.kclk_waves = v->kclk_waves;
-    switch (v->layout) {
-    case LAYOUT_LFD: return lfd_step(a, v->w64, v->nxp, s);
+    switch (v->plan.layout) {
+    case LAYOUT_LFD: return lfd_step(a, v->plan.w64, v->plan.nxp, s);
     case LAYOUT_LF8: return lf8_step(a, a.T > 1, s);
     case LAYOUT_PERM: return perm_step(a, a.T > 1, s);
-    case LAYOUT_PERMB: return permb_step(a, v->nxp, s);
+    case LAYOUT_PERMB: return permb_step(a, v->plan.nxp, s);
     case LAYOUT_PAULI: return pauli_step(v, a, s);
-    case LAYOUT_TILE: return qm_step(a, v->nxp, v->has_z, s);
-    case LAYOUT_TILE64: return q64_step(a, v->nxp, v->has_z, s);
+    case LAYOUT_TILE: return qm_step(a, v->plan.nxp, v->plan.has_z, s);
+    case LAYOUT_TILE64: return q64_step(a, v->plan.nxp, v->plan.has_z, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -364,28 +349,10 @@ static hipError_t launch_step(const qg_vec *v, const StepArgs &a_in, hipStream_t
 // qg_vec_track_dense.  The one-step kernel without add_inverts (qm_step1_kernel) rewrites the rows its gate changed in the same launch;
 // every other launch that changes states is followed by a full rewrite (dense_refresh), except resets of a list of finished envs, which
 // rewrite those envs' observations themselves.
-static plan::HandlePlan plan_of(const qg_vec *v) {  // the handle's fields that the planner's predicates read
-    plan::HandlePlan hp;
-    hp.layout = v->layout;
-    hp.D = v->D;
-    hp.nxp = v->nxp;
-    hp.has_z = v->has_z;
-    hp.w64 = v->w64;
-    hp.flags = v->flags;
-    hp.has_bad = v->bad != nullptr;
-    hp.has_done_list = v->done_list != nullptr;
-    hp.pt_nq = v->pt_nq;
-    hp.pt_rm = v->pt_rm;
-    hp.pauli_compact = v->pt_nq <= 24 && v->pt_rm == 8;
-    return hp;
-}
 // env.step() (one step per launch) of this handle keeps the tracked observation current itself
 static bool dense_rides_in_step(const qg_vec *v) {
-    if (!v->dense) return false;
-    const plan::HandlePlan hp = plan_of(v);
-    return plan::dense_in_kernel(hp, plan::step_kernel_of(hp, 1, false, false, v->maybe_nonsymplectic, (uint32_t)v->gates.size(), false));
+    return v->dense && plan::dense_in_kernel(v->plan, plan::step_kernel_of(v->plan, 1, false, false, v->maybe_nonsymplectic, (uint32_t)v->gates.size(), false));
 }
-static int dense_refresh(qg_vec *v, hipStream_t s);
 
 int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, uint64_t batch, int device, qg_vec **out) {
     if (!cfg || !out || (!gates && n_gates)) return set_error(QG_ERR_INVALID, "null argument");
@@ -427,25 +394,11 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
     v->coin_seed = 0x5EED0000C01Full;
 
     // layout, size class and behaviour flags: qgym_plan.hpp (the same function answers qg_plan_query without a GPU)
-    plan::HandlePlan hp;
     const char *why = "";
-    if (int rc = plan::handle_plan(*cfg, batch, hp, why)) return set_error(rc, "%s (num_qubits = %u)", why, N);
-    v->layout = hp.layout;
-    v->D = hp.D;
-    v->nxp = hp.nxp;
-    v->has_z = hp.has_z;
-    v->w64 = hp.w64;
-    v->flags = hp.flags;
-    v->stride_bytes = hp.stride_bytes;
-    v->state_bytes = hp.state_bytes;
-    if (hp.layout == LAYOUT_PAULI) {
-        v->rmax = hp.rmax;
-        v->rmax_generate = hp.rmax_generate;
-        v->cfg.max_rotations = hp.max_rotations;
-        v->pt_nq = hp.pt_nq;
-        v->pt_rm = hp.pt_rm;
-    }
-    const bool layers = v->flags & F_LAYERS;
+    if (int rc = plan::handle_plan(*cfg, batch, v->plan, why)) return set_error(rc, "%s (num_qubits = %u)", why, N);
+    const plan::HandlePlan &hp = v->plan;
+    if (hp.layout == LAYOUT_PAULI) v->cfg.max_rotations = hp.max_rotations;
+    const bool layers = hp.flags & F_LAYERS;
 
     // gate table
     std::vector<GateEntry> table(std::max<size_t>(n_gates, 1));
@@ -455,8 +408,8 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
         int dc, dg;
         gate_deltas(gates[i], N, dc, dg);
         table[i].ops = cfg->env_kind == QG_PAULI ? 0u
-                       : v->layout == LAYOUT_TILE ? tile_ops(cfg->env_kind, gates[i], false)
-                       : v->layout == LAYOUT_TILE64 ? tile_ops(cfg->env_kind, gates[i], true)
+                       : hp.layout == LAYOUT_TILE ? tile_ops(cfg->env_kind, gates[i], false)
+                       : hp.layout == LAYOUT_TILE64 ? tile_ops(cfg->env_kind, gates[i], true)
                                                   : gate_ops(cfg->env_kind, gates[i], N);
         table[i].penalty = table_penalty(w, dc, dg);
         descs[i] = make_desc((uint32_t)gates[i].kind, (uint32_t)gates[i].q0, (uint32_t)gates[i].q1);
@@ -476,8 +429,8 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
         }                                                                                          \
     } while (0)
 
-    HIP_TRY_V(hipMalloc(&p->state, p->state_bytes));
-    HIP_TRY_V(hipMemset(p->state, 0, p->state_bytes));
+    HIP_TRY_V(hipMalloc(&p->state, hp.state_bytes));
+    HIP_TRY_V(hipMemset(p->state, 0, hp.state_bytes));
     HIP_TRY_V(hipMalloc(&p->depth, sizeof(int32_t) * batch));
     HIP_TRY_V(hipMalloc(&p->reward, sizeof(float) * batch));
     HIP_TRY_V(hipMalloc(&p->done, batch));
@@ -486,12 +439,12 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
     // TILE / TILE64 layouts without add_inverts: the one-step kernel keeps `solved` as a per-env mask; PERMB: the number of entries with
     // state[i] != i; LFD: row masks of the state's and the inverse's region
     if (hp.has_bad)
-        HIP_TRY_V(hipMalloc(&p->bad, (v->layout == LAYOUT_LFD ? 2 * sizeof(uint64_t) : v->layout == LAYOUT_TILE64 ? sizeof(uint64_t) : sizeof(uint32_t)) * batch));
+        HIP_TRY_V(hipMalloc(&p->bad, plan::bad_word_bytes(hp) * batch));
     if (hp.has_done_list) {
         HIP_TRY_V(hipMalloc(&p->done_list, sizeof(uint32_t) * (batch + 2)));
         HIP_TRY_V(hipMemset(p->done_list + batch, 0, 2 * sizeof(uint32_t)));
     }
-    if (hp.has_done_list && (v->layout == LAYOUT_TILE || v->layout == LAYOUT_TILE64)) {  // the init kernel zeroes the idle list's length instead of taking reader tickets on its own
+    if (hp.has_done_list && plan::is_tile(hp)) {  // the init kernel zeroes the idle list's length instead of taking reader tickets on its own
         HIP_TRY_V(hipMalloc(&p->done_list_spare, sizeof(uint32_t) * (batch + 2)));
         HIP_TRY_V(hipMemset(p->done_list_spare + batch, 0, 2 * sizeof(uint32_t)));
     }
@@ -499,10 +452,10 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
         HIP_TRY_V(hipMalloc(&p->done_list_alt, sizeof(uint32_t) * (batch + 2)));
         HIP_TRY_V(hipMemset(p->done_list_alt + batch, 0, 2 * sizeof(uint32_t)));
     }
-    if (hp.has_done_list && (v->layout == LAYOUT_TILE || v->layout == LAYOUT_TILE64 || v->layout == LAYOUT_PAULI)) {  // the finished envs of a step as one bit each (qm_step1 / qm_inv2 / q64_step1 / q64_inv2 / ptile_step1c <LIST>)
+    if (hp.has_done_list) {  // the finished envs of a step as one bit each (qm_step1 / qm_inv2 / q64_step1 / q64_inv2 / ptile_step1c <LIST>)
         HIP_TRY_V(hipHostMalloc((void **)&p->count_seen, sizeof(uint32_t), hipHostMallocMapped));
         *p->count_seen = 0xFFFFFFFFu;
-        if (v->layout != LAYOUT_TILE) {
+        if (hp.layout != LAYOUT_TILE) {
             HIP_TRY_V(hipMalloc(&p->mask_count, 2 * sizeof(uint32_t)));
             HIP_TRY_V(hipMemset(p->mask_count, 0, 2 * sizeof(uint32_t)));
         }
@@ -516,7 +469,7 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
     if (cfg->track_solution) {
         // Clifford/LF/Permutation push one entry per step; PauliEnv one per step plus one per removed rotation
         p->sol_cap = (uint32_t)std::max(cfg->max_depth, 1);
-        if (v->layout == LAYOUT_PAULI) p->sol_cap += p->rmax;
+        if (hp.layout == LAYOUT_PAULI) p->sol_cap += hp.rmax;
         HIP_TRY_V(hipMalloc(&p->sol, sizeof(uint32_t) * (size_t)p->sol_cap * batch));
     }
     if (layers) {
@@ -527,9 +480,9 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
     HIP_TRY_V(hipMalloc(&p->d_descs, sizeof(uint32_t) * descs.size()));
     HIP_TRY_V(hipMemcpy(p->d_gates, table.data(), sizeof(GateEntry) * table.size(), hipMemcpyHostToDevice));
     HIP_TRY_V(hipMemcpy(p->d_descs, descs.data(), sizeof(uint32_t) * descs.size(), hipMemcpyHostToDevice));
-    if (v->layout == LAYOUT_TILE || v->layout == LAYOUT_TILE64) {  // the same gates as <= 2 row operations on tile slots (clifford.rs:89-133)
+    if (plan::is_tile(hp)) {  // the same gates as <= 2 row operations on tile slots (clifford.rs:89-133)
         std::vector<uint32_t> rowops(table.size(), 0u);
-        auto slot = [&](uint32_t row) { return v->has_z ? (row < N ? 2 * row : 2 * (row - N) + 1) : row; };
+        auto slot = [&](uint32_t row) { return hp.has_z ? (row < N ? 2 * row : 2 * (row - N) + 1) : row; };
         for (size_t i = 0; i < n_gates; ++i) {
             const uint32_t ops = gate_ops(cfg->env_kind, gates[i], N);
             uint32_t out = 0;
@@ -542,20 +495,19 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
         HIP_TRY_V(hipMalloc(&p->d_rowops, sizeof(uint32_t) * rowops.size()));
         HIP_TRY_V(hipMemcpy(p->d_rowops, rowops.data(), sizeof(uint32_t) * rowops.size(), hipMemcpyHostToDevice));
     }
-    if (v->layout == LAYOUT_PAULI) {
+    if (hp.layout == LAYOUT_PAULI) {
         int rc = pauli_alloc(p);
         if (rc) return fail(rc);
     }
 
     // observe_dense of the 64-bit-row / lane-group / PauliEnv layouts goes through row words in the handle's scratch buffer: sized here, so
     // that the call never allocates (it may be made inside a stream capture)
-    if (v->layout == LAYOUT_TILE64 || v->layout == LAYOUT_LFD || v->layout == LAYOUT_PAULI) {
-        const size_t word = (v->layout == LAYOUT_LFD && !v->w64) ? 4 : 8;
-        int rc = ensure_scratch(p, (size_t)batch * v->D * word);
+    if (hp.layout == LAYOUT_TILE64 || hp.layout == LAYOUT_LFD || hp.layout == LAYOUT_PAULI) {
+        int rc = ensure_scratch(p, (size_t)batch * hp.D * plan::packed_word_bytes(hp));
         if (rc) return fail(rc);
     }
     // constructor state: identity, depth 1, success, reward 1.0 (clifford.rs:214-245)
-    if (v->layout == LAYOUT_PAULI) {
+    if (hp.layout == LAYOUT_PAULI) {
         int rc = pauli_init_identity(p, nullptr);
         if (rc) return fail(rc);
     } else {
@@ -597,9 +549,9 @@ int qg_vec_get_info(const qg_vec *v, qg_vec_info *o) {
     }
     o->device = v->device;
     o->batch = v->B;
-    o->packed_word_bytes = (v->layout == LAYOUT_PERM || v->layout == LAYOUT_PERMB) ? 1 : ((v->layout == LAYOUT_TILE64 || v->layout == LAYOUT_PAULI || (v->layout == LAYOUT_LFD && v->w64)) ? 8 : 4);
-    o->packed_words_per_env = v->D;
-    o->packed_env_stride_bytes = v->stride_bytes;
+    o->packed_word_bytes = plan::packed_word_bytes(v->plan);
+    o->packed_words_per_env = v->plan.D;
+    o->packed_env_stride_bytes = v->plan.stride_bytes;
     o->state_dev = v->state;
     o->reward_dev = v->reward;
     o->done_dev = v->done;
@@ -607,14 +559,6 @@ int qg_vec_get_info(const qg_vec *v, qg_vec_info *o) {
     o->depth_dev = v->depth;
     o->error_dev = v->error;
     return QG_OK;
-}
-
-static void drop_graphs(qg_vec *v) {
-    for (auto &g : v->graphs) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    v->graphs.clear();
 }
 
 int qg_vec_bind_outputs(qg_vec *v, float *reward_dev, uint8_t *done_dev, uint8_t *success_dev, int32_t *depth_dev) {
@@ -648,12 +592,12 @@ int64_t qg_vec_get_difficulty(const qg_vec *v) { return v ? v->difficulty : -1; 
 static size_t format_elem_bytes(const qg_vec *v, int format) {
     if (format == QG_FMT_I64) return 8;
     if (format == QG_FMT_U8) return 1;
-    return (v->layout == LAYOUT_PERM || v->layout == LAYOUT_PERMB) ? 1 : ((v->layout == LAYOUT_TILE64 || v->layout == LAYOUT_PAULI || (v->layout == LAYOUT_LFD && v->w64)) ? 8 : 4);
+    return plan::packed_word_bytes(v->plan);
 }
 static size_t format_min_elems(const qg_vec *v, int format) {
-    if (v->layout == LAYOUT_PERM || v->layout == LAYOUT_PERMB) return v->N;
-    if (format == QG_FMT_PACKED) return v->D;
-    return (size_t)v->D * v->D;
+    if (v->plan.layout == LAYOUT_PERM || v->plan.layout == LAYOUT_PERMB) return v->N;
+    if (format == QG_FMT_PACKED) return v->plan.D;
+    return (size_t)v->plan.D * v->plan.D;
 }
 
 int qg_vec_set_state(qg_vec *v, const void *states, int format, size_t stride, int on_device, void *stream) {
@@ -663,7 +607,7 @@ int qg_vec_set_state(qg_vec *v, const void *states, int format, size_t stride, i
     hipStream_t s = (hipStream_t)stream;
     (void)v->dl.enter(session_of(s));
     if (int rc = drop_done_list(v, s)) return rc;
-    if (v->layout == LAYOUT_PAULI) return pauli_set_state(v, states, format, stride, on_device, s);
+    if (v->plan.layout == LAYOUT_PAULI) return pauli_set_state(v, states, format, stride, on_device, s);
     if (stride < format_min_elems(v, format))
         return set_error(QG_ERR_INVALID, "set_state: %zu elements per env, need %zu (the reference would index out of bounds)",
                          stride, format_min_elems(v, format));
@@ -671,7 +615,7 @@ int qg_vec_set_state(qg_vec *v, const void *states, int format, size_t stride, i
     // entry formats (the trait's Vec<i64>, dense bytes) of the bit-matrix layouts: the flat entry stream becomes a bit stream first (64 entries
     // per wave instruction, coalesced), the init kernel cuts its row words out of it -- no thread walks rows of 8-byte entries
     // (a handful of envs -- the scalar qg_env_* handles are batches of one -- keep the single launch)
-    const bool as_bits = format != QG_FMT_PACKED && plan::entry_formats_stream(v->layout, v->B);
+    const bool as_bits = format != QG_FMT_PACKED && plan::entry_formats_stream(v->plan.layout, v->B);
     const size_t in_bytes = format_elem_bytes(v, format) * stride * v->B;
     const size_t staged = on_device ? 0 : (in_bytes + 15) & ~(size_t)15;
     const size_t stream_words = as_bits ? (stride * v->B + 63) / 64 + 2 : 0;  // + the word bits_window may read past the end
@@ -720,14 +664,14 @@ static hipError_t launch_export(const qg_vec *v, const ObsArgs &a_in, hipStream_
     ObsArgs a = a_in;
     a.kclk = kernel_clock_slot(v);
     a.kclk_waves = v->kclk_waves;
-    switch (v->layout) {
-    case LAYOUT_LFD: return lfd_export(a, v->w64, v->nxp, v->inverted, s);
+    switch (v->plan.layout) {
+    case LAYOUT_LFD: return lfd_export(a, v->plan.w64, v->plan.nxp, v->inverted, s);
     case LAYOUT_LF8: return lf8_export(a, s);
     case LAYOUT_PERM: return perm_export(a, s);
-    case LAYOUT_PERMB: return permb_export(a, v->nxp, s);
+    case LAYOUT_PERMB: return permb_export(a, v->plan.nxp, s);
     case LAYOUT_PAULI: return pauli_export(v, a, s);
-    case LAYOUT_TILE: return qm_export(a, v->nxp, v->has_z, s);
-    case LAYOUT_TILE64: return q64_export(a, v->nxp, v->has_z, s);
+    case LAYOUT_TILE: return qm_export(a, v->plan.nxp, v->plan.has_z, s);
+    case LAYOUT_TILE64: return q64_export(a, v->plan.nxp, v->plan.has_z, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -738,9 +682,8 @@ static void fill_obs_args(const qg_vec *v, ObsArgs &a, void *out, int format, si
     a.out = out;
     a.B = v->B;
     a.out_stride = stride;
-    a.D = v->D;
+    a.D = v->plan.D;
     a.N = v->N;
-    a.log2L = v->log2L;
     a.format = (uint32_t)format;
     qg_vec_info info;
     qg_vec_get_info(v, &info);
@@ -760,10 +703,10 @@ int qg_vec_get_state(qg_vec *v, void *out, int format, size_t stride, int on_dev
     // stores are wave-contiguous -- 537 MB at streaming rate (the export kernels' row-per-thread, entry-by-entry stores reached 0.6 TB/s)
     qg_vec_info info;
     qg_vec_get_info(v, &info);
-    const bool two_stage = format == QG_FMT_I64 && plan::entry_formats_stream(v->layout, v->B) && stride == (size_t)v->D * v->D && !((uintptr_t)out & 15u) &&
-                           info.packed_words_per_env == v->D;
+    const bool two_stage = format == QG_FMT_I64 && plan::entry_formats_stream(v->plan.layout, v->B) && stride == (size_t)v->plan.D * v->plan.D && !((uintptr_t)out & 15u) &&
+                           info.packed_words_per_env == v->plan.D;
     const size_t staged = on_device ? 0 : (bytes + 15) & ~(size_t)15;
-    const size_t words_bytes = two_stage ? (size_t)v->B * v->D * info.packed_word_bytes : 0;
+    const size_t words_bytes = two_stage ? (size_t)v->B * v->plan.D * info.packed_word_bytes : 0;
     if (staged + words_bytes) {
         int rc = ensure_scratch(v, staged + words_bytes);
         if (rc) return rc;
@@ -772,12 +715,12 @@ int qg_vec_get_state(qg_vec *v, void *out, int format, size_t stride, int on_dev
     ObsArgs oa;
     if (two_stage) {
         void *words = (char *)v->scratch + staged;
-        fill_obs_args(v, oa, words, QG_FMT_PACKED, v->D);
+        fill_obs_args(v, oa, words, QG_FMT_PACKED, v->plan.D);
         HIP_TRY(launch_export(v, oa, s));
-        HIP_TRY(expand_rows_i64(words, (int)info.packed_word_bytes, v->B * (uint64_t)v->D, v->D, reinterpret_cast<int64_t *>(dst), s));
+        HIP_TRY(expand_rows_i64(words, (int)info.packed_word_bytes, v->B * (uint64_t)v->plan.D, v->plan.D, reinterpret_cast<int64_t *>(dst), s));
     } else {
         fill_obs_args(v, oa, dst, format, stride);
-        if (v->layout == LAYOUT_PAULI) {  // tableau only, square
+        if (v->plan.layout == LAYOUT_PAULI) {  // tableau only, square
             oa.obs_cols = oa.obs_rows;
         }
         HIP_TRY(launch_export(v, oa, s));
@@ -794,8 +737,8 @@ static int do_reset(qg_vec *v, const int32_t *actions_dev, uint64_t seed, hipStr
     QG_ON_DEVICE(v);
     const bool trusted = v->dl.enter(session_of(s));
     if (int rc = only_done ? QG_OK : drop_done_list(v, s)) return rc;
-    if (only_done && v->layout == LAYOUT_PAULI) return ptile_reset_seeded(v, seed, true, s, v->dl.pauli_reset_consumes(trusted));
-    if (v->layout == LAYOUT_PAULI) {
+    if (only_done && v->plan.layout == LAYOUT_PAULI) return ptile_reset_seeded(v, seed, true, s, v->dl.pauli_reset_consumes(trusted));
+    if (v->plan.layout == LAYOUT_PAULI) {
         if (actions_dev) return set_error(QG_ERR_UNSUPPORTED, "PauliEnv reset draws a whole target, not `difficulty` actions: use qg_vec_reset(seed) or qg_vec_pauli_reset_from");
         return pauli_reset_seeded(v, seed, s);
     }
@@ -812,7 +755,7 @@ static int do_reset(qg_vec *v, const int32_t *actions_dev, uint64_t seed, hipStr
         if (use.compact) HIP_TRY(compact_done(v->done, v->B, v->done_list, v->done_list + v->B, s));
         ia.list = v->done_list;
         ia.list_count = v->done_list + v->B;
-        if ((v->layout == LAYOUT_TILE || v->layout == LAYOUT_TILE64) && v->count_seen) {
+        if (plan::is_tile(v->plan) && v->count_seen) {
             ia.count_out = v->count_seen;
             ia.tree_grid = reset_tree_grid(v, plan::tree_grid(v->B));
         }
@@ -824,7 +767,7 @@ static int do_reset(qg_vec *v, const int32_t *actions_dev, uint64_t seed, hipStr
         }
         ia.coop = plan::reset_coop_allowed(actions_dev != nullptr, v->B, v->d_rowops != nullptr) ? 1u : 0u;
         ia.flags_current = 1u;  // (this launch is the reset alone)
-        if (v->layout == LAYOUT_TILE) ia.dense = v->dense;  // the listed envs' dense observations are rewritten by the reset itself
+        if (v->plan.layout == LAYOUT_TILE) ia.dense = v->dense;  // the listed envs' dense observations are rewritten by the reset itself
         if (v->done_list_spare) ia.zero_count = v->done_list_spare + v->B;
     }
     if (!only_done) v->maybe_nonsymplectic = false;  // identity + gates: every env is symplectic again
@@ -839,12 +782,7 @@ int qg_vec_set_clock(qg_vec *v, const uint64_t *clock_dev) {
     QG_ON_DEVICE(v);
     HIP_TRY(hipDeviceSynchronize());
     v->clock_dev = clock_dev;
-    // cached rollout graphs bake the old pointer in
-    for (auto &g : v->graphs) {
-        (void)hipGraphExecDestroy(g.exec);
-        (void)hipGraphDestroy(g.graph);
-    }
-    v->graphs.clear();
+    drop_graphs(v);  // cached rollout graphs bake the old pointer in
     return QG_OK;
 }
 
@@ -923,13 +861,11 @@ int qg_vec_reset_with(qg_vec *v, const int32_t *actions_dev, size_t n_draws, voi
     return do_reset(v, actions_dev, 0, (hipStream_t)stream);
 }
 
-// A handle on which qg_vec_reset_done is in use: a single step of the TILE / TILE64 one-step kernels (qm_step1, qm_inv2, q64_step1, q64_inv2)
+// A handle on which qg_vec_reset_done is in use: a single step of the kernels that qgym_plan.hpp step_leaves_done_list names
 // leaves the list of the envs it finished itself, and the reset that follows needs no compaction launch.
 static bool step_leaves_done_list(const qg_vec *v, bool may_leave, StepArgs &a) {
-    const bool tile32 = v->layout == LAYOUT_TILE, tile64 = v->layout == LAYOUT_TILE64;  // qm_step1 / qm_inv2 (N <= 16), q64_step1 / q64_inv2
-    const bool pauli = v->layout == LAYOUT_PAULI && v->done_mask[0] && v->pt_nq <= 24 && v->pt_rm == 8 && v->B > QG_COMPACT_MIN_ENVS;  // ptile_step1c_kernel (compact layout)
-    const bool lists = may_leave && v->done_list &&
-                       (pauli || ((tile32 || tile64) && ((v->flags & F_INVERTS) ? (v->has_z && (tile64 || v->nxp <= 16) && !v->maybe_nonsymplectic) : v->bad != nullptr)));
+    const bool lists = may_leave && v->done_list && (v->plan.layout != LAYOUT_PAULI || v->done_mask[0]) &&  // (ptile_step1c_kernel leaves bits only)
+                       plan::step_leaves_done_list(v->plan, v->B, v->maybe_nonsymplectic);
     if (lists) {
         a.flags |= F_DONE_LIST;
         a.done_list = v->done_list;
@@ -1028,13 +964,13 @@ int qg_vec_reset_done_step(qg_vec *v, uint64_t reset_seed, const void *actions_d
     // one launch when the list of finished envs and their is_final flags were left by this handle's own previous step (same session) and the
     // reset would take the list path with counter-RNG draws; otherwise the two calls, whose step leaves both for the next time
     // (add_inverts: the two-lanes-per-env launch has no Gauss-Jordan and no tracked-observation form)
-    const bool inverts = v->flags & F_INVERTS;
+    const bool inverts = v->plan.flags & F_INVERTS;
     // ... and where the one launch is the faster form (qgym_plan.hpp reset_step_pays: from the configuration)
-    const bool pays = plan::reset_step_pays(plan_of(v), v->difficulty, std::min<int64_t>((int64_t)v->cfg.depth_slope * v->difficulty, v->cfg.max_depth));
+    const bool pays = plan::reset_step_pays(v->plan, v->difficulty, std::min<int64_t>((int64_t)v->cfg.depth_slope * v->difficulty, v->cfg.max_depth));
     const bool fuse = v->done_list_alt && v->done_mask[0] && v->dl.fused_may_run(trusted) && !v->gates.empty() &&
-                      plan::reset_coop_allowed(false, v->B, v->d_rowops != nullptr) && plan::reset_step_fuses(plan_of(v)) &&
+                      plan::reset_coop_allowed(false, v->B, v->d_rowops != nullptr) && plan::reset_step_fuses(v->plan) &&
                       !(inverts && (v->maybe_nonsymplectic || v->dense)) && pays;
-    const bool word = plan::reset_step_in_word_kernel(plan_of(v), v->gates.size());
+    const bool word = plan::reset_step_in_word_kernel(v->plan, v->gates.size());
     if (!word && !fuse) {
         if (int rc = qg_vec_reset_done(v, reset_seed, stream)) return rc;
         return rollout_impl(v, actions_dev, action_dtype, 1, 1, coins_dev, rewards_dev, dones_dev, 0, stream);
@@ -1053,7 +989,7 @@ int qg_vec_reset_done_step(qg_vec *v, uint64_t reset_seed, const void *actions_d
         if (int rc = drop_done_list(v, s)) return rc;  // (enqueues nothing: these layouts hold no list)
         a.kclk = kernel_clock_slot(v);
         a.kclk_waves = v->kclk_waves;
-        HIP_TRY(word_reset_step(ia, a, v->layout == LAYOUT_PERM, s));
+        HIP_TRY(word_reset_step(ia, a, v->plan.layout == LAYOUT_PERM, s));
         v->step_index += 1;
         return QG_OK;
     }
@@ -1076,7 +1012,7 @@ int qg_vec_reset_done_step(qg_vec *v, uint64_t reset_seed, const void *actions_d
     if (dense_rides_in_step(v)) a.dense = v->dense;
     a.kclk = kernel_clock_slot(v);
     a.kclk_waves = v->kclk_waves;
-    HIP_TRY(v->layout == LAYOUT_TILE64 ? q64_reset_step(ia, a, v->nxp, v->has_z, s) : qm_reset_step(ia, a, v->nxp, v->has_z, s));
+    HIP_TRY(v->plan.layout == LAYOUT_TILE64 ? q64_reset_step(ia, a, v->plan.nxp, v->plan.has_z, s) : qm_reset_step(ia, a, v->plan.nxp, v->plan.has_z, s));
     v->step_index += 1;
     // the list just appended to is the current one, the idle list (zeroed by this launch) is the next launch's target, the one just consumed idles
     std::swap(v->done_list, v->done_list_alt);   // (current, alt, spare) <- (alt, spare, current)
@@ -1114,7 +1050,7 @@ static int rollout_impl(qg_vec *v, const void *actions_dev, int action_dtype, si
     a.rewards_seq = rewards_dev;
     a.dones_seq = dones_dev;
     if (action_dtype == QG_ACT_I64) a.flags |= F_ACT64;
-    if (v->layout == LAYOUT_LFD) fused = 0;  // its step kernel spreads an env over four lanes; T steps = T launches (one graph)
+    if (v->plan.layout == LAYOUT_LFD) fused = 0;  // its step kernel spreads an env over four lanes; T steps = T launches (one graph)
     if (dense_rides_in_step(v) && (!fused || T == 1)) a.dense = v->dense;  // single-step launches keep the tracked observation current themselves
     if (fused) {
         if (period != T) return set_error(QG_ERR_INVALID, "fused rollouts read actions[t] for every t");
@@ -1139,7 +1075,7 @@ static int rollout_impl(qg_vec *v, const void *actions_dev, int action_dtype, si
         }
         if (v->dense && !a.dense) {  // kernels that do not track it (add_inverts, other layouts): one full rewrite after the last step
             ObsArgs oa;
-            fill_obs_args(v, oa, v->dense, QG_FMT_U8, (size_t)v->D * v->D);
+            fill_obs_args(v, oa, v->dense, QG_FMT_U8, (size_t)v->plan.D * v->plan.D);
             return launch_export(v, oa, st);
         }
         return hipSuccess;
@@ -1148,7 +1084,7 @@ static int rollout_impl(qg_vec *v, const void *actions_dev, int action_dtype, si
     // that is already being captured by the caller must not be captured again.
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (s) (void)hipStreamIsCapturing(s, &cs);
-    const bool rng_coins = (v->flags & F_INVERTS) && !coins_dev;
+    const bool rng_coins = (v->plan.flags & F_INVERTS) && !coins_dev;
     if (cs != hipStreamCaptureStatusNone || rng_coins || T == 1) {
         HIP_TRY(enqueue_steps(s));
         v->step_index += T;
@@ -1173,8 +1109,7 @@ static int rollout_impl(qg_vec *v, const void *actions_dev, int action_dtype, si
         }
         HIP_TRY(hipGraphInstantiate(&ng.exec, ng.graph, nullptr, nullptr, 0));
         if (v->graphs.size() >= 8) {  // small LRU-less cache: drop the oldest
-            (void)hipGraphExecDestroy(v->graphs.front().exec);
-            (void)hipGraphDestroy(v->graphs.front().graph);
+            destroy_graph(v->graphs.front());
             v->graphs.erase(v->graphs.begin());
         }
         v->graphs.push_back(ng);
@@ -1190,7 +1125,7 @@ static int observe_dense_impl(qg_vec *v, int8_t *out_dev, const int32_t *perm_id
     ObsArgs oa;
     qg_vec_info info;
     qg_vec_get_info(v, &info);
-    if ((v->layout == LAYOUT_TILE64 || v->layout == LAYOUT_LFD) && info.packed_words_per_env == info.obs_rows && !((uintptr_t)out_dev & 15u)) {
+    if ((v->plan.layout == LAYOUT_TILE64 || v->plan.layout == LAYOUT_LFD) && info.packed_words_per_env == info.obs_rows && !((uintptr_t)out_dev & 15u)) {
         // 64-bit-row and lane-group layouts: the packed rows (one word per observation row) first, then the shared expansion kernel, whose
         // stores are 16 bytes wide -- the export kernels' byte-at-a-time rows reach 0.9 TB/s (CliffordEnv 24q x 65 536: 168 us for 151 MB)
         const uint64_t n_words = v->B * (uint64_t)info.packed_words_per_env;
@@ -1217,13 +1152,6 @@ int qg_vec_observe_dense(qg_vec *v, int8_t *out_dev, void *stream) {
     return observe_dense_impl(v, out_dev, nullptr, stream);
 }
 
-static int dense_refresh(qg_vec *v, hipStream_t s) {
-    ObsArgs oa;
-    fill_obs_args(v, oa, v->dense, QG_FMT_U8, (size_t)v->D * v->D);
-    HIP_TRY(launch_export(v, oa, s));
-    return QG_OK;
-}
-
 int qg_vec_track_dense(qg_vec *v, int8_t *dense_dev, void *stream) {
     if (!v) return set_error(QG_ERR_INVALID, "null argument");
     QG_ON_DEVICE(v);
@@ -1231,7 +1159,7 @@ int qg_vec_track_dense(qg_vec *v, int8_t *dense_dev, void *stream) {
         v->dense = nullptr;
         return QG_OK;
     }
-    if (!plan::dense_trackable(plan_of(v)))
+    if (!plan::dense_trackable(v->plan))
         return set_error(QG_ERR_UNSUPPORTED, "track_dense: matrices of 16 or 32 rows held as 32-bit row words (CliffordEnv N = 8, 16; LinearFunctionEnv N = 16, 32)");
     if ((uintptr_t)dense_dev & 15u) return set_error(QG_ERR_INVALID, "track_dense: the buffer must be 16-byte aligned");
     v->dense = dense_dev;
@@ -1247,7 +1175,7 @@ int qg_plan_query(const qg_config *cfg, uint64_t batch, uint32_t num_actions, in
     const char *name = "(none)";
     static const char *layouts[] = {"NONE", "?", "LF8", "PERM", "PAULI", "TILE", "TILE64", "PERMB", "LFD"};
     const bool perms = cfg->env_kind == QG_PAULI && cfg->add_perms;  // (a PauliEnv whose coupling map has automorphisms)
-    const uint32_t R = hp.has_z ? 2 * hp.nxp : hp.nxp;
+    const uint32_t R = plan::row_slots(hp);
     switch (op) {
     case QG_PLAN_LAYOUT: name = hp.layout == LAYOUT_PAULI ? (hp.pauli_compact ? "PTILE-compact" : "PTILE") : layouts[hp.layout]; break;
     case QG_PLAN_STEP: name = plan::step_kernel_name(plan::step_kernel_of(hp, 1, false, false, nonsymplectic != 0, num_actions, perms)); break;
@@ -1322,12 +1250,10 @@ int qg_vec_copy_envs(qg_vec *dst, const qg_vec *src, const uint32_t *src_idx_dev
         if (!d || !sp || !rows) return;
         a.r[a.n_regions++] = CopyRegionArgs{(char *)d, (const char *)sp, tile_bytes, pitch_dst, pitch_src, rows, w};
     };
-    plan::HandlePlan hp;
-    const char *why = "";
-    (void)plan::handle_plan(dst->cfg, dst->B, hp, why);
+    const plan::HandlePlan &hp = dst->plan;
     const plan::CopyLayout cl = plan::copy_layout(hp);
     const size_t covered = hp.stride_bytes ? hp.stride_bytes * dst->B : (size_t)cl.tile_bytes * ((dst->B + 63) / 64);
-    if (!cl.n || covered != dst->state_bytes)  // the regions must be exactly the layout the allocation was sized for
+    if (!cl.n || covered != hp.state_bytes)  // the regions must be exactly the layout the allocation was sized for
         return set_error(QG_ERR_UNSUPPORTED, "copy_envs: no region list for this layout");
     for (uint32_t k = 0; k < cl.n; ++k)  // the state first: region 0 is the one the tracked dense observation is written from
         add((char *)dst->state + cl.r[k].offset, (const char *)src->state + cl.r[k].offset, cl.tile_bytes, 64u * cl.r[k].w, 64u * cl.r[k].w, cl.r[k].rows,
@@ -1340,7 +1266,7 @@ int qg_vec_copy_envs(qg_vec *dst, const qg_vec *src, const uint32_t *src_idx_dev
     per_env(dst->success, src->success, 1);
     per_env(dst->inverted, src->inverted, 1);
     per_env(dst->sol_len, src->sol_len, 8);  // {solution, solution_inv} lengths
-    per_env(dst->bad, src->bad, dst->layout == LAYOUT_LFD ? 16u : dst->layout == LAYOUT_TILE64 ? 8u : 4u);  // incremental solved masks
+    per_env(dst->bad, src->bad, plan::bad_word_bytes(hp));  // incremental solved masks
     per_env(dst->perm_idx, src->perm_idx, 4);  // PauliEnv current_perm_idx (pauli.rs:661)
     add(dst->sol, src->sol, 256, 4 * dst->B, 4 * src->B, dst->sol_cap, 4);  // [sol_cap][B]: both halves of the log
     add(dst->layers, src->layers, 256ull * dst->layers_len, 256, 256, dst->layers_len, 4);  // [B / 64][2N + 2][64] (layer_rec)
@@ -1351,7 +1277,7 @@ int qg_vec_copy_envs(qg_vec *dst, const qg_vec *src, const uint32_t *src_idx_dev
     a.B_dst = dst->B;
     if (dst->dense && plan::dense_trackable(hp)) {
         a.dense = dst->dense;
-        a.D = dst->D;
+        a.D = hp.D;
         a.N = dst->N;
         a.has_z = hp.has_z ? 1u : 0u;
     }
@@ -1361,7 +1287,7 @@ int qg_vec_copy_envs(qg_vec *dst, const qg_vec *src, const uint32_t *src_idx_dev
 
 int qg_vec_pauli_observe_dense(qg_vec *v, int8_t *out_dev, const int32_t *perm_idx_dev, void *stream) {
     if (!v || !out_dev) return set_error(QG_ERR_INVALID, "null argument");
-    if (v->layout != LAYOUT_PAULI) return set_error(QG_ERR_INVALID, "not a PauliEnv batch");
+    if (v->plan.layout != LAYOUT_PAULI) return set_error(QG_ERR_INVALID, "not a PauliEnv batch");
     return observe_dense_impl(v, out_dev, perm_idx_dev, stream);
 }
 
@@ -1370,7 +1296,7 @@ int qg_vec_pauli_num_perms(const qg_vec *v) { return v ? (int)v->n_perms : -1; }
 int qg_vec_observe_packed(qg_vec *v, void *out_dev, void *stream) {
     if (!v || !out_dev) return set_error(QG_ERR_INVALID, "null argument");
     QG_ON_DEVICE(v);
-    if (v->layout == LAYOUT_PAULI) {
+    if (v->plan.layout == LAYOUT_PAULI) {
         const uint32_t cols = 2 * v->N + (uint32_t)std::max(v->cfg.max_rotations, 1);
         if (cols > 64u)
             return set_error(QG_ERR_UNSUPPORTED, "packed observation of PauliEnv needs at most 64 observation columns: use observe_dense");
@@ -1419,7 +1345,7 @@ int qg_vec_masks(qg_vec *v, uint8_t *out_dev, void *stream) {
 
 int qg_vec_pauli_reset_from(qg_vec *v, const uint8_t *tableaus, const char *labels, const int32_t *n_rot, void *stream) {
     if (!v || !tableaus || !n_rot) return set_error(QG_ERR_INVALID, "null argument");
-    if (v->layout != LAYOUT_PAULI) return set_error(QG_ERR_INVALID, "not a PauliEnv batch");
+    if (v->plan.layout != LAYOUT_PAULI) return set_error(QG_ERR_INVALID, "not a PauliEnv batch");
     QG_ON_DEVICE(v);
     return pauli_reset_from(v, tableaus, labels, n_rot, (hipStream_t)stream);
 }
@@ -1452,7 +1378,7 @@ int qg_vec_sync(qg_vec *v, void *stream) {
 // Env::solution from one env's slice of the log (`row[i * stride]` = entry i in push order, `len` = {pushed to solution, to solution_inv})
 static size_t decode_solution(const qg_vec *v, const uint32_t *row, size_t stride, const int32_t len[2], uint64_t *out, size_t cap) {
     size_t n = 0;
-    if (v->layout == LAYOUT_PAULI) {  // one list (pauli.rs:685-719); 32-bit entries
+    if (v->plan.layout == LAYOUT_PAULI) {  // one list (pauli.rs:685-719); 32-bit entries
         for (int32_t i = 0; i < len[0]; ++i, ++n)
             if (n < cap && out) out[n] = row[i * stride] == 0xFFFFFFFFu ? ~0ull : (uint64_t)row[i * stride];  // saturated invalid action
         return n;
@@ -1522,7 +1448,6 @@ int zero_list_length(const qg_vec *v, uint32_t *list, bool needed, hipStream_t s
     if (needed) HIP_TRY(hipMemsetAsync(list + v->B, 0, 2 * sizeof(uint32_t), s));
     return QG_OK;
 }
-void fill_step_args_public(const qg_vec *v, StepArgs &a) { fill_step_args(v, a); }
 int bind_error(qg_vec *v, uint32_t *error_dev) {
     if (!v || !error_dev) return set_error(QG_ERR_INVALID, "null argument");
     QG_ON_DEVICE(v);
@@ -1534,17 +1459,20 @@ int bind_error(qg_vec *v, uint32_t *error_dev) {
     drop_graphs(v);
     return QG_OK;
 }
-unsigned long long *kernel_clock_slot_public(const qg_vec *v) { return kernel_clock_slot(v); }
-uint32_t reset_tree_grid_public(const qg_vec *v, uint32_t most) { return reset_tree_grid(v, most); }
 // The launch behind a reset's trees (PauliEnv's ptile_generate_kernel) has nothing to do when the trees took the list, and
 // finds that out from one word: a few workgroups are enough for it whenever the latest list the handle's resets have reported was a trees' list (they walk the batch
 // with the grid's stride, so a longer list is still reset -- by fewer workgroups, until the next call sees its length).  0: one workgroup per 64 envs.
-uint32_t reset_second_grid_public(const qg_vec *v, bool is_tree_list_of_that_length(uint32_t, const qg_vec *)) {
+uint32_t reset_second_grid(const qg_vec *v, bool is_tree_list_of_that_length(uint32_t, const qg_vec *)) {
     const uint32_t seen = v->count_seen ? *(volatile const uint32_t *)v->count_seen : 0xFFFFFFFFu;
     return (seen != 0xFFFFFFFFu && (seen == 0 || is_tree_list_of_that_length(seen, v))) ? 32u : 0u;
 }
 
-int dense_refresh_public(qg_vec *v, hipStream_t s) { return dense_refresh(v, s); }
+int dense_refresh(qg_vec *v, hipStream_t s) {
+    ObsArgs oa;
+    fill_obs_args(v, oa, v->dense, QG_FMT_U8, (size_t)v->plan.D * v->plan.D);
+    HIP_TRY(launch_export(v, oa, s));
+    return QG_OK;
+}
 // (also what a kernel that resets finished envs itself needs: qg_vec_mid_head_sample_step)
 void fill_reset_done_args(const qg_vec *v, uint64_t seed, InitArgs &ia) {
     fill_init_args(v, ia);
@@ -1554,5 +1482,4 @@ void fill_reset_done_args(const qg_vec *v, uint64_t seed, InitArgs &ia) {
     ia.only_done = 1u;
     ia.depth_value = (int32_t)std::min<int64_t>((int64_t)v->cfg.depth_slope * v->difficulty, v->cfg.max_depth);  // clifford.rs:317, linear_function.rs:296
 }
-int reset_done_public(qg_vec *v, uint64_t seed, void *stream) { return qg_vec_reset_done(v, seed, stream); }
 }  // namespace qg

@@ -268,7 +268,7 @@ int qg_env_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, in
     e->obs = reinterpret_cast<int8_t *>(e->io) + 64;
     e->obs_dev = reinterpret_cast<int8_t *>(e->io_dev) + 64;
 #undef HIP_TRY_E
-    e->obs_ahead = !(v->layout == LAYOUT_PAULI && v->n_perms > 0);
+    e->obs_ahead = !(v->plan.layout == LAYOUT_PAULI && v->n_perms > 0);
     // the handle's per-env outputs live in the I/O block from here on (their constructor values are carried over)
     // (the remaining depth stays in device memory: the step kernel reads and writes it, the trait has no getter for it)
     rc = qg_vec_bind_outputs(v, &e->io_dev->reward, &e->io_dev->done, &e->io_dev->success, nullptr);
@@ -342,19 +342,15 @@ int qg_env_clone(const qg_env *e, qg_env **out) {  // Env: DynClone -- deep copy
     d->perm_in = nullptr;
     d->clock_dev = s->clock_dev;
     d->dense = c->tracked ? c->obs_dev : nullptr;  // (the clone's own pinned observation, made current below)
-    for (auto &g : d->graphs) {  // cached rollout graphs have the previous owner's pointers and counters baked in
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    d->graphs.clear();
+    qg::drop_graphs(d);  // cached rollout graphs have the previous owner's pointers and counters baked in
     struct { void *dst; const void *src; size_t bytes; } copies[] = {
-        {d->state, s->state, s->state_bytes},
+        {d->state, s->state, s->plan.state_bytes},
         {d->depth, s->depth, 4},
         {d->inverted, s->inverted, 1},
         {d->sol_len, s->sol_len, 8},
         {d->sol, s->sol, (size_t)s->sol_cap * 4},
         {d->layers, s->layers, (size_t)s->layers_len * 4 * 64},  // the env's tile (layer_rec)
-        {d->bad, s->bad, s->layout == LAYOUT_LFD ? (size_t)16 : s->layout == LAYOUT_TILE64 ? (size_t)8 : (size_t)4},  // incremental solved masks
+        {d->bad, s->bad, plan::bad_word_bytes(s->plan)},  // incremental solved masks
         {d->perm_idx, s->perm_idx, (size_t)4},                                 // PauliEnv current_perm_idx (pauli.rs:661)
     };
     for (auto &cp : copies)
@@ -373,7 +369,7 @@ int qg_env_clone(const qg_env *e, qg_env **out) {  // Env: DynClone -- deep copy
         memcpy(c->obs, e->obs, e->obs_bytes);
         c->obs_valid = true;
     } else if (c->tracked) {  // (a source nobody has observed: rewrite the clone's tracked observation from the copied state)
-        if (qg::dense_refresh_public(d, c->st) != QG_OK) {
+        if (qg::dense_refresh(d, c->st) != QG_OK) {
             env_free(c);
             return set_error(QG_ERR_DEVICE, "clone: observation refresh failed");
         }
@@ -409,7 +405,7 @@ int64_t qg_env_get_difficulty(const qg_env *e) { return e ? qg_vec_get_difficult
 
 int qg_env_set_state(qg_env *e, const int64_t *state, size_t n) {
     if (!e) return set_error(QG_ERR_INVALID, "null argument");
-    if (n == 0 && e->v->layout == LAYOUT_PAULI) return QG_OK;  // pauli.rs:518-520
+    if (n == 0 && e->v->plan.layout == LAYOUT_PAULI) return QG_OK;  // pauli.rs:518-520
     if (!state) return set_error(QG_ERR_INVALID, "null argument");
     QG_ON_DEVICE(e->v);
     int rc = qg_vec_set_state(e->v, state, QG_FMT_I64, n, 0, e->st);

@@ -76,15 +76,9 @@ struct qg_vec {
     qg_config cfg{};
     std::vector<qg_gate> gates;
     uint64_t B = 0;
-    uint32_t N = 0, D = 0, log2L = 0;
+    uint32_t N = 0;
     int device = 0;
-    qg::Layout layout = qg::LAYOUT_NONE;
-    size_t stride_bytes = 0;   // per-env stride (0 for the tiled layout)
-    size_t state_bytes = 0;    // total resident state size
-    uint32_t nxp = 0;          // TILE layout: X-row slots per env (N rounded up to 4); PERMB layout: 16-byte groups per env
-    bool has_z = false;        // TILE layout: Z-type rows present (CliffordEnv)
-    bool w64 = false;          // LFD layout: uint64 rows (N > 32); nxp = groups per region
-    uint32_t flags = 0;
+    qg::plan::HandlePlan plan;  // layout, sizes and behaviour flags: filled once by qg_vec_create, never changed (qgym_plan.hpp)
     int64_t difficulty = 1;
     uint64_t coin_seed = 0;
     uint64_t step_index = 0;
@@ -139,9 +133,6 @@ struct qg_vec {
 
     // PauliEnv (pauli_host.cpp, kernels_pauli_tile.hip)
     void *d_prog = nullptr;  // [num_actions] per-action programs (tableau map + micro-ops)
-    uint32_t rmax = 0;
-    uint32_t rmax_generate = 0;
-    uint32_t pt_nq = 0, pt_rm = 0;
     void *d_gen_tables = nullptr;  // PTILE target generator: coupling-graph distance tables
     uint32_t gen_nd = 0, gen_ncx = 0, gen_npairs = 0, gen_off[4] = {0, 0, 0, 0};  // final_pauli_layers: most rotations reset() generates
     uint8_t *d_qubit_perms = nullptr;  // [n_perms][N]  (add_perms)
@@ -163,17 +154,26 @@ inline bool same_ctor(const qg_vec *a, const qg_vec *b) {
     return a->device == b->device && memcmp(&a->cfg, &b->cfg, sizeof a->cfg) == 0 && a->gates.size() == b->gates.size() &&
            (a->gates.empty() || memcmp(a->gates.data(), b->gates.data(), a->gates.size() * sizeof(qg_gate)) == 0);
 }
-int ensure_scratch_public(qg_vec *v, size_t bytes);
+int ensure_scratch(qg_vec *v, size_t bytes);
+// cached rollout graphs have kernel arguments baked in: whatever changes one of them drops the cache
+inline void destroy_graph(CachedGraph &g) {
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    if (g.graph) (void)hipGraphDestroy(g.graph);
+}
+inline void drop_graphs(qg_vec *v) {
+    for (auto &g : v->graphs) destroy_graph(g);
+    v->graphs.clear();
+}
 uint64_t session_of(hipStream_t s);  // the done-list session (DoneListState::enter) a launch on `s` belongs to: 0 = eager, else the capture id
 int zero_list_length(const qg_vec *v, uint32_t *list, bool needed, hipStream_t s);  // enqueue what a DoneListState transition asked for
-void fill_step_args_public(const qg_vec *v, StepArgs &a);
+void fill_step_args(const qg_vec *v, StepArgs &a);
 // the per-env fault words in caller-owned memory (device-visible, [B] uint32, current content carried over); not part of the C ABI: the scalar env's
 int bind_error(qg_vec *v, uint32_t *error_dev);
-uint32_t reset_second_grid_public(const qg_vec *v, bool is_tree_list_of_that_length(uint32_t, const qg_vec *));  // workgroups of the launch behind a reset's trees
-uint32_t reset_tree_grid_public(const qg_vec *v, uint32_t most);  // workgroups of a reset's tree launch, from the list lengths the handle's resets have reported
-unsigned long long *kernel_clock_slot_public(const qg_vec *v);  // qg_vec_set_kernel_clock: the slot of the launch about to be enqueued, or null
+uint32_t reset_second_grid(const qg_vec *v, bool is_tree_list_of_that_length(uint32_t, const qg_vec *));  // workgroups of the launch behind a reset's trees
+uint32_t reset_tree_grid(const qg_vec *v, uint32_t most);  // workgroups of a reset's tree launch, from the list lengths the handle's resets have reported
+unsigned long long *kernel_clock_slot(const qg_vec *v);  // qg_vec_set_kernel_clock: the slot of the launch about to be enqueued, or null
 // qg_vec_track_dense: rewrite the whole tracked observation from the state (after a launch that changed states without updating it)
-int dense_refresh_public(qg_vec *v, hipStream_t s);
+int dense_refresh(qg_vec *v, hipStream_t s);
 // InitArgs of qg_vec_reset_done(v, seed) without a list (mode 2, `difficulty` draws, only the finished envs)
 void fill_reset_done_args(const qg_vec *v, uint64_t seed, InitArgs &ia);
 void compute_qubit_and_action_perms(uint32_t N, const std::vector<qg_gate> &gates, std::vector<std::vector<int64_t>> &qubit_perms,

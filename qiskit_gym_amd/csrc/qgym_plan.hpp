@@ -40,6 +40,19 @@ struct HandlePlan {
     bool pauli_compact = false;
 };
 
+// ---- facts that follow from a HandlePlan (written once, here) ------------------------------------------------------------------------
+inline bool is_tile(const HandlePlan &p) { return p.layout == LAYOUT_TILE || p.layout == LAYOUT_TILE64; }  // thread-per-env bit matrices
+// row slots per env of a TILE / TILE64 handle (TILE counts X slots in nxp, its Z slots come on top; TILE64 counts both); 0 on every other
+// layout, where nxp counts groups or nothing
+inline uint32_t row_slots(const HandlePlan &p) { return !is_tile(p) ? 0u : (p.layout == LAYOUT_TILE && p.has_z) ? 2 * p.nxp : p.nxp; }
+// bytes of one word of QG_FMT_PACKED (qg_vec_info::packed_word_bytes): a permutation entry, or one matrix row
+inline uint32_t packed_word_bytes(const HandlePlan &p) {
+    if (p.layout == LAYOUT_PERM || p.layout == LAYOUT_PERMB) return 1;
+    return (p.layout == LAYOUT_TILE64 || p.layout == LAYOUT_PAULI || (p.layout == LAYOUT_LFD && p.w64)) ? 8 : 4;
+}
+// bytes per env of the incremental `solved` word (has_bad): LFD keeps a uint64 row mask for each region, TILE64 one uint64, TILE / PERMB a uint32
+inline uint32_t bad_word_bytes(const HandlePlan &p) { return !p.has_bad ? 0u : p.layout == LAYOUT_LFD ? 16u : p.layout == LAYOUT_TILE64 ? 8u : 4u; }
+
 // The constructor's decisions (qg_vec_create).  Returns QG_OK, or the status and message the constructor reports.
 inline int handle_plan(const qg_config &cfg, uint64_t batch, HandlePlan &p, const char *&why) {
     why = "";
@@ -103,8 +116,7 @@ inline int handle_plan(const qg_config &cfg, uint64_t batch, HandlePlan &p, cons
         p.layout = LAYOUT_TILE;
         p.nxp = (N + 3u) & ~3u;
         p.has_z = cfg.env_kind == QG_CLIFFORD;
-        const size_t R = p.has_z ? 2 * p.nxp : p.nxp;
-        p.state_bytes = ((batch + 63) / 64) * R * 256;
+        p.state_bytes = ((batch + 63) / 64) * (size_t)row_slots(p) * 256;
     }
     if (p.layout == LAYOUT_NONE) {  // uint64 rows, thread per env (kernels_qm64.hip)
         p.layout = LAYOUT_TILE64;
@@ -116,8 +128,8 @@ inline int handle_plan(const qg_config &cfg, uint64_t batch, HandlePlan &p, cons
     if (cfg.track_solution) p.flags |= F_TRACK;
     if (!(cfg.w_n_layers == 0.0f && cfg.w_n_layers_cnots == 0.0f)) p.flags |= F_LAYERS;
     // TILE / TILE64 without add_inverts: `solved` as a per-env mask; PERMB: number of misplaced entries; LFD: row masks of both regions
-    p.has_bad = ((p.layout == LAYOUT_TILE || p.layout == LAYOUT_TILE64) && !(p.flags & F_INVERTS)) || p.layout == LAYOUT_PERMB || p.layout == LAYOUT_LFD;
-    p.has_done_list = p.layout == LAYOUT_TILE || p.layout == LAYOUT_TILE64 || p.layout == LAYOUT_PAULI;
+    p.has_bad = (is_tile(p) && !(p.flags & F_INVERTS)) || p.layout == LAYOUT_PERMB || p.layout == LAYOUT_LFD;
+    p.has_done_list = is_tile(p) || p.layout == LAYOUT_PAULI;
     if (!p.state_bytes) p.state_bytes = p.stride_bytes * batch;
     return QG_OK;
 }
@@ -143,10 +155,10 @@ inline CopyLayout copy_layout(const HandlePlan &p) {
         c.tile_bytes += rows * 64u * w;
     };
     switch (p.layout) {
-    case LAYOUT_TILE: add((p.has_z ? 2 * p.nxp : p.nxp) / 4u, 16); break;  // R / 4 groups of four uint32 row slots (kernels_qm.hip)
-    case LAYOUT_TILE64: add(p.nxp / 2u, 16); break;                        // two uint64 rows per group (kernels_qm64.hip)
-    case LAYOUT_PERMB: add(p.nxp, 16); break;                              // 16 entries per group (kernels_perm.hip)
-    case LAYOUT_LFD: add(2 * p.nxp, 16); break;                            // matrix, then inverse (kernels_lfd.hip)
+    case LAYOUT_TILE: add(row_slots(p) / 4u, 16); break;    // groups of four uint32 row slots (kernels_qm.hip)
+    case LAYOUT_TILE64: add(row_slots(p) / 2u, 16); break;  // two uint64 rows per group (kernels_qm64.hip)
+    case LAYOUT_PERMB: add(p.nxp, 16); break;               // 16 entries per group (kernels_perm.hip)
+    case LAYOUT_LFD: add(2 * p.nxp, 16); break;             // matrix, then inverse (kernels_lfd.hip)
     case LAYOUT_LF8:
     case LAYOUT_PERM: add(1, 8); break;
     case LAYOUT_PAULI: {  // PTLayout (kernels_pauli_tile.hip): qubit records, rotation records, DAG bookkeeping
@@ -214,32 +226,23 @@ inline const char *step_kernel_name(StepKernel k) {
     }
 }
 
-// one launch of `T` steps (T == 1: env.step(); the graph rollouts issue T of those) on a TILE handle (kernels_qm.hip launch_step)
-inline StepKernel tile_step(uint32_t flags, uint32_t T, bool has_bad, bool seq_outputs, uint32_t num_actions, bool has_z, uint32_t nxp) {
+// one launch of `T` steps (T == 1: env.step(); the graph rollouts issue T of those) on a TILE (kernels_qm.hip launch_step) or, `wide`, a TILE64 handle
+// (kernels_qm64.hip q64_launch_step): the 32- or 64-bit member of each kernel pair.  `inv_kernels`: the add_inverts kernels exist for this size
+inline StepKernel tile_step(bool wide, bool inv_kernels, uint32_t flags, uint32_t T, bool has_bad, bool seq_outputs, uint32_t num_actions) {
     const bool feat = flags & (F_TRACK | F_LAYERS);
     const bool seq = T != 1 || seq_outputs;
-    if (has_bad && T == 1 && !(flags & F_INVERTS)) return SK_QM_STEP1;
+    if (has_bad && T == 1 && !(flags & F_INVERTS)) return wide ? SK_Q64_STEP1 : SK_QM_STEP1;
     if (flags & F_INVERTS) {
-        if (!(has_z && nxp <= 16)) return SK_INVALID;  // (LinearFunctionEnv with add_inverts lives in the LFD layout)
-        if (!(flags & F_GJ) && T == 1) return SK_QM_INV2;
-        return (flags & F_GJ) ? SK_QM_STEP_GJ : SK_QM_STEP_INV;
+        if (!inv_kernels) return SK_INVALID;  // (LinearFunctionEnv with add_inverts lives in the LFD layout)
+        if (!(flags & F_GJ) && T == 1) return wide ? SK_Q64_INV2 : SK_QM_INV2;
+        if (flags & F_GJ) return wide ? SK_Q64_STEP_GJ : SK_QM_STEP_GJ;
+        return wide ? SK_Q64_STEP_INV : SK_QM_STEP_INV;
     }
-    if (!feat && seq && T > 1 && num_actions != 0) return SK_QM_FUSED_LDS;
-    return SK_QM_STEP;
+    if (!feat && seq && T > 1 && num_actions != 0) return wide ? SK_Q64_FUSED_LDS : SK_QM_FUSED_LDS;
+    return wide ? SK_Q64_STEP : SK_QM_STEP;
 }
-// ... on a TILE64 handle (kernels_qm64.hip q64_launch_step)
-inline StepKernel tile64_step(uint32_t flags, uint32_t T, bool has_bad, bool seq_outputs, uint32_t num_actions, bool has_z) {
-    const bool feat = flags & (F_TRACK | F_LAYERS);
-    const bool seq = T != 1 || seq_outputs;
-    if (has_bad && T == 1 && !(flags & F_INVERTS)) return SK_Q64_STEP1;
-    if (flags & F_INVERTS) {
-        if (!has_z) return SK_INVALID;
-        if (!(flags & F_GJ) && T == 1) return SK_Q64_INV2;
-        return (flags & F_GJ) ? SK_Q64_STEP_GJ : SK_Q64_STEP_INV;
-    }
-    if (!feat && seq && T > 1 && num_actions != 0) return SK_Q64_FUSED_LDS;
-    return SK_Q64_STEP;
-}
+// ... for which sizes the launchers instantiate the add_inverts kernels: CliffordEnv, on uint32 rows up to 16 qubits
+constexpr bool tile_inv_kernels(bool wide, bool has_z, uint32_t nxp) { return has_z && (wide || nxp <= 16); }
 inline StepKernel permb_step_kernel_of(uint32_t flags, uint32_t T, bool has_bad) {
     return (T == 1 && !(flags & F_INVERTS) && has_bad) ? SK_PERMB_STEP1 : SK_PERMB_STEP;
 }
@@ -253,14 +256,29 @@ inline StepKernel step_kernel_of(const HandlePlan &p, uint32_t T, bool fused, bo
     const uint32_t flags = p.flags | (maybe_nonsymplectic ? F_GJ : 0u);
     const uint32_t launch_T = fused ? T : 1u;  // a graph rollout is T single-step launches
     switch (p.layout) {
-    case LAYOUT_TILE: return tile_step(flags, launch_T, p.has_bad, seq_outputs, num_actions, p.has_z, p.nxp);
-    case LAYOUT_TILE64: return tile64_step(flags, launch_T, p.has_bad, seq_outputs, num_actions, p.has_z);
+    case LAYOUT_TILE:
+    case LAYOUT_TILE64: {
+        const bool wide = p.layout == LAYOUT_TILE64;
+        return tile_step(wide, tile_inv_kernels(wide, p.has_z, p.nxp), flags, launch_T, p.has_bad, seq_outputs, num_actions);
+    }
     case LAYOUT_LFD: return SK_LFD_STEP;  // (its fused form is T launches too)
     case LAYOUT_LF8:
     case LAYOUT_PERM: return SK_WORD_STEP;
     case LAYOUT_PERMB: return permb_step_kernel_of(flags, launch_T, p.has_bad);
     case LAYOUT_PAULI: return pauli_step_kernel_of(flags, launch_T, p.pauli_compact, has_perms);
     default: return SK_INVALID;
+    }
+}
+// env.step() on this handle runs a kernel with a <LIST> form: it can leave the envs it finished for the qg_vec_reset_done that follows (the caller
+// adds what is known at run time only: that the done-list session allows it and that the handle holds a list)
+inline bool step_leaves_done_list(const HandlePlan &p, uint64_t batch, bool maybe_nonsymplectic) {
+    switch (step_kernel_of(p, 1, false, false, maybe_nonsymplectic, 1, false)) {
+    case SK_QM_STEP1:
+    case SK_QM_INV2:
+    case SK_Q64_STEP1:
+    case SK_Q64_INV2: return true;
+    case SK_PTILE_STEP1C: return batch > QG_COMPACT_MIN_ENVS;  // (smaller batches are reset without compact_done, kernels_pauli_tile.hip)
+    default: return false;
     }
 }
 
@@ -306,8 +324,8 @@ constexpr bool tile_coop_fits(uint32_t R, uint32_t word_bytes) { return 16ull * 
 // ... and CliffordEnv N <= 16 with add_inverts (qm_reset_inv2_step_kernel: two lanes per env), while every env is known to be symplectic
 inline bool reset_step_fusable(const HandlePlan &p) {
     if (!p.has_done_list) return false;
-    if (p.flags & F_INVERTS) return p.layout == LAYOUT_TILE && p.has_z && p.nxp <= 16;
-    return (p.layout == LAYOUT_TILE || p.layout == LAYOUT_TILE64) && p.has_bad;
+    if (p.flags & F_INVERTS) return p.layout == LAYOUT_TILE && tile_inv_kernels(false, p.has_z, p.nxp);
+    return is_tile(p) && p.has_bad;
 }
 // ... and whether the one launch is the faster form for a steady collection with this scramble length (`draws` = difficulty) and episode length (steps):
 // what it gains is the tree resets' launch; when a large share of the batch finishes in every step (short episodes: the lane-per-env resets, whose envs' first steps
@@ -340,10 +358,7 @@ inline bool entry_formats_stream(Layout layout, uint64_t batch) {
     return batch >= QG_STREAM_MIN_ENVS && (layout == LAYOUT_TILE || layout == LAYOUT_TILE64 || layout == LAYOUT_LFD);
 }
 // qg_vec_track_dense: which handles can keep a resident dense observation, and whether the step kernel maintains it itself
-inline bool dense_trackable(const HandlePlan &p) {
-    const uint32_t R = p.has_z ? 2 * p.nxp : p.nxp;
-    return p.layout == LAYOUT_TILE && p.D == R && (p.D == 16 || p.D == 32);
-}
+inline bool dense_trackable(const HandlePlan &p) { return p.layout == LAYOUT_TILE && p.D == row_slots(p) && (p.D == 16 || p.D == 32); }
 // ... which step kernels rewrite the rows they changed themselves: the one-step kernel without add_inverts, and CliffordEnv 16q's
 // two-lanes-per-env kernel (whole env when the coin inverted it); every other launch is followed by a full rewrite
 inline bool dense_in_kernel(const HandlePlan &p, StepKernel k) {
