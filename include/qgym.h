@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
- * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select (additions only) */
+ * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
+ *      qg_beam_merge, qg_beam_seen_bytes (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -392,6 +393,39 @@ int qg_sample_actions(const void *logits_dev, int logits_dtype, uint64_t ld, uin
 int qg_beam_select(const void *logp_dev, int logp_dtype, uint64_t ld, uint32_t num_actions, uint64_t n_groups, uint32_t width,
                    const float *cum_dev, const uint8_t *live_dev, uint32_t *parent_dev, void *actions_dev, int action_dtype,
                    float *cum_out_dev, uint8_t *live_out_dev, void *stream);
+/* Which beams of a group hold a state the group has already got: the merge step of a beam search.  Groups as in qg_beam_select: group g owns
+ * slots g*width .. g*width + width-1 of a batch of n_groups*width envs.  words_dev: the batch's QG_FMT_PACKED observation as
+ * qg_vec_observe_packed writes it, [batch, words_per_env] words of word_bytes (1, 4 or 8) each -- any words will do, the kernel knows no env.
+ *
+ * The state key.  With w_0 .. w_{n-1} the n = words_per_env words of one env, each zero-extended to 64 bits, and splitmix64 the function of
+ * the reset draws above (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31),
+ *   key = splitmix64( n ^ ( sum_i splitmix64( w_i ^ splitmix64(i + 1) )  mod 2^64 ) ),     and a key of 0 is replaced by 0x9E3779B97F4A7C15
+ * (the sum wraps, so no order of summation shows; 0 is left to mean "empty" in the history).  Two envs hold "the same state" exactly when
+ * their keys are equal.  Two different states share a key with probability about 2^-64 per pair; such a collision can only drop a beam, never
+ * produce a wrong solution: the env, not this kernel, decides what solves a target.
+ *
+ * The rules (tests/beammerge_model.py restates them in numpy; results agree bit for bit), with cum_dev f32[batch] the slots' scores so far
+ * and live_dev u8[batch] != 0 where a slot holds a beam:
+ *   1. A live slot whose cum has no order word -- NaN or -inf, as for a candidate of qg_beam_select -- is dropped and counted nowhere.
+ *   2. Revisit: a live slot whose key is in its group's history is dropped, and counted in dropped[g][0].
+ *   3. Duplicate: among the remaining live slots of a group that share a key exactly one survives, the one with the largest cum in
+ *      qg_beam_select's order (-0 = +0), ties to the lowest slot.  The others are dropped, and counted in dropped[g][1].
+ *   4. live_out_dev u8[batch] = 1 for the survivors and 0 for every other slot (a slot that was not live stays 0).  It may not alias live_dev.
+ *   5. The survivors' keys enter the group's history in ascending slot order.  A history holds at most seen_cap distinct keys; once it is
+ *      full further keys are not recorded (the search goes on and only prunes less).  Nothing is ever removed.
+ *   6. No randomness; the result does not depend on the launch geometry.
+ * keys_out_dev (optional) u64[batch]: the key of every slot, live or not.  dropped_dev (optional) u32[n_groups][2]: ADDED to by every call.
+ * seen_dev (optional): the groups' histories, qg_beam_seen_bytes(n_groups, seen_cap) bytes, 8-byte aligned, opaque; all-zero bytes are the empty
+ * history (the caller clears it with a memset on its stream), and one buffer goes with one (n_groups, seen_cap).  NULL: merge within the call
+ * only (rule 2 never applies, rule 5 does nothing).  Every call scans the group's history, so a call costs time in proportion to the keys held.
+ * Limits: width <= 64 and words_per_env * word_bytes <= 2048 (a group's words are then at most 128 KiB), n_groups < 2^31, seen_cap < 2^32;
+ * QG_ERR_UNSUPPORTED beyond, QG_ERR_INVALID for a null required pointer, a zero size (seen_cap too, when seen_dev is given), a word_bytes other
+ * than 1 / 4 / 8, a misaligned buffer or aliased live arrays.  Stream-ordered on `stream`, one launch (one workgroup per group), no
+ * synchronisation, capturable into a hipGraph. */
+size_t qg_beam_seen_bytes(uint64_t n_groups, uint64_t seen_cap);
+int qg_beam_merge(const void *words_dev, int word_bytes, uint32_t words_per_env, uint64_t n_groups, uint32_t width, const float *cum_dev,
+                  const uint8_t *live_dev, void *seen_dev, uint64_t seen_cap, uint8_t *live_out_dev, uint64_t *keys_out_dev,
+                  uint32_t *dropped_dev, void *stream);
 /* Generalised advantage estimation over a [n_steps, batch] rollout (f32, done_t = the episode ended
  * with step t): delta_t = r_t + gamma*V_{t+1}*(1-done_t) - V_t, A_t = delta_t +
  * gamma*lambda*(1-done_t)*A_{t+1}, returns = A + V.  last_values_dev: V after the last step

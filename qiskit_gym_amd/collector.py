@@ -99,6 +99,45 @@ def beam_select(logp: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, width
     return parent, actions, cum_out, live_out
 
 
+def beam_seen(n_groups: int, cap: int, device=None) -> torch.Tensor:
+    """An empty history for `beam_merge`: room for `cap` state keys for each of `n_groups` groups (`qg_beam_seen_bytes`), zeroed.  Opaque;
+    `zero_()` empties it again."""
+    if int(n_groups) < 0 or int(cap) < 1:
+        raise ValueError("beam_seen: n_groups >= 0 and cap >= 1")
+    nbytes = int(_lib.load().qg_beam_seen_bytes(int(n_groups), int(cap)))
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device="cuda" if device is None else device)
+
+
+def beam_merge(words: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, width: int, seen: Optional[torch.Tensor] = None, seen_cap: int = 0,
+               keys: Optional[torch.Tensor] = None, dropped: Optional[torch.Tensor] = None, live_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The merge step of a beam search (`qg_beam_merge`): the batch is groups of `width` consecutive envs; a live slot leaves when its state
+    key -- a 64-bit hash of its row of `words` -- is in its group's history `seen` (a revisit), or when another live slot of its group holds
+    the same key with a larger `cum` (ties: the lower slot stays; a duplicate).  The survivors' keys enter the history.
+    words: [B, words_per_env] of 1-, 4- or 8-byte integers (`VecEnv.observe_packed`); cum: f32 [B]; live: uint8 / bool [B]; seen: from
+    `beam_seen(B // width, seen_cap)`, or None to merge within the call only.  keys: optional int64 [B], receives every slot's key;
+    dropped: optional int32 [B // width, 2], (revisits, duplicates) are added to it.  Returns live_out uint8 [B] (not `live` itself)."""
+    if words.dim() != 2 or not words.is_contiguous() or words.is_floating_point() or words.element_size() not in (1, 4, 8):
+        raise ValueError("beam_merge: words must be a contiguous [B, words_per_env] tensor of 1-, 4- or 8-byte integers")
+    B, dev, W = words.shape[0], words.device, int(width)
+    if W < 1 or B % W:
+        raise ValueError(f"beam_merge: {B} envs do not divide into groups of {W}")
+    if live.dtype == torch.bool:
+        live = live.view(torch.uint8)
+    live_out = torch.empty(B, dtype=torch.uint8, device=dev) if live_out is None else live_out
+    for name, t, dt, numel in (("cum", cum, (torch.float32,), B), ("live", live, (torch.uint8,), B), ("live_out", live_out, (torch.uint8,), B),
+                               ("keys", keys, (torch.int64, torch.uint64), B), ("dropped", dropped, (torch.int32, torch.uint32), 2 * (B // W))):
+        if t is not None and (t.dtype not in dt or t.numel() != numel or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"beam_merge: {name} must be a contiguous tensor of {numel} {' / '.join(str(d) for d in dt)} on the device of words")
+    L = _lib.load()
+    if seen is not None and (seen.dtype != torch.int64 or not seen.is_contiguous() or seen.device != dev
+                             or seen.numel() * 8 != L.qg_beam_seen_bytes(B // W, int(seen_cap))):
+        raise ValueError("beam_merge: seen must come from beam_seen(B // width, seen_cap) on the device of words")
+    _lib.check(L.qg_beam_merge(words.data_ptr(), words.element_size(), words.shape[1], B // W, W, cum.data_ptr(), live.data_ptr(),
+                               seen.data_ptr() if seen is not None else None, int(seen_cap) if seen is not None else 0, live_out.data_ptr(),
+                               keys.data_ptr() if keys is not None else None, dropped.data_ptr() if dropped is not None else None, _stream_ptr()))
+    return live_out
+
+
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,
         gae_lambda: float, advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None):
     """GAE(lambda) over a [T, B] rollout; `dones[t]` = the episode ended with step t.  Returns (advantages, returns)."""

@@ -1,4 +1,7 @@
-// kernels_search.hip -- qg_beam_select: the selection step of a beam search over a policy's log-probabilities.  From the W beams x A actions
+// kernels_search.hip -- the device-side steps of a beam search over a policy's log-probabilities: qg_beam_select and, at the end of this
+// file, qg_beam_merge (which beams of a target hold a state the target has already got).
+//
+// qg_beam_select: the selection step.  From the W beams x A actions
 // of one target pick the W best continuations as (parent env, action) pairs, the operands of qg_vec_copy_envs and qg_vec_step, without
 // leaving the device.  The rules are stated in include/qgym.h; tests/beammodel.py restates them in numpy.
 //
@@ -143,6 +146,120 @@ __global__ __launch_bounds__(64 * BEAM_MAX_WAVES) void beam_select_kernel(const 
     }
 }
 
+// ---- qg_beam_merge ---------------------------------------------------------------------------------------------------------------------------
+// One workgroup per group; the rules are stated in include/qgym.h, tests/beammerge_model.py restates them in numpy.
+//   1. salt[i] = splitmix64(i + 1) of every word index into LDS, once for the group's W envs;
+//   2. every wave hashes whole envs (wave, wave + NW, ...): lane l sums splitmix64(w_i ^ salt[i]) over i = l, l + 64, ... (consecutive lanes,
+//      consecutive words), a 64-lane wrapping sum (cross-lane, no LDS) closes the key.  The sum wraps, so the deal does not show in the key;
+//   3. the group's history -- [0] = number of keys held, [1 ..] = the keys in the order they came -- is dealt to the threads; each compares
+//      its keys with the W slot keys (LDS broadcast reads) and flags the slots it meets;
+//   4. lane s of wave 0 decides slot s: no order word / revisit / duplicate (one pass over the W slots: a slot is a duplicate when another
+//      remaining slot with its key has the larger (order word, lower slot)); survivors take consecutive places of the history by a ballot.
+// One workgroup owns a group's history and counters for the whole launch: plain vector loads and stores, no atomics.
+constexpr uint32_t MERGE_MAX_ENV_BYTES = 2048;
+constexpr uint32_t MERGE_WAVES = 4;
+
+struct MergeArgs {
+    const void *words;
+    const float *cum;
+    const uint8_t *live;
+    uint64_t *seen;  // [n_groups][1 + cap], or nullptr
+    uint8_t *live_out;
+    uint64_t *keys_out;  // or nullptr
+    uint32_t *dropped;   // [n_groups][2], or nullptr
+    uint64_t cap;
+    uint32_t W, n;  // n = words per env
+};
+
+__host__ __device__ inline uint64_t merge_key_close(uint32_t n, uint64_t sum) {
+    const uint64_t k = splitmix64((uint64_t)n ^ sum);
+    return k ? k : 0x9E3779B97F4A7C15ull;  // 0 is the history's "empty"
+}
+
+__device__ inline uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64), lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
+        v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
+template <typename WT>
+__global__ __launch_bounds__(64 * MERGE_WAVES) void beam_merge_kernel(const MergeArgs a) {
+    extern __shared__ uint64_t merge_lds[];
+    const uint32_t tid = threadIdx.x, NT = blockDim.x, lane = tid & (QG_WAVE - 1), wave = tid >> 6, NW = NT >> 6;
+    uint64_t *salt = merge_lds;                                  // [n]
+    uint64_t *keys = merge_lds + a.n;                            // [W]
+    uint32_t *ord = reinterpret_cast<uint32_t *>(keys + a.W);    // [W] order word of a slot still in the running, else 0
+    uint32_t *hit = ord + a.W;                                   // [W] != 0: the slot's key is in the history
+    const uint64_t slot0 = (uint64_t)blockIdx.x * a.W;           // the group's first env
+    const WT *words = reinterpret_cast<const WT *>(a.words) + slot0 * a.n;
+
+    // 1.
+    for (uint32_t i = tid; i < a.n; i += NT) salt[i] = splitmix64((uint64_t)i + 1);
+    if (tid < a.W) hit[tid] = 0;
+    __syncthreads();
+
+    // 2.
+    for (uint32_t s = wave; s < a.W; s += NW) {
+        uint64_t sum = 0;
+        for (uint32_t i = lane; i < a.n; i += QG_WAVE) sum += splitmix64((uint64_t)words[(uint64_t)s * a.n + i] ^ salt[i]);
+        sum = wave_sum_u64(sum);
+        if (lane == 0) keys[s] = merge_key_close(a.n, sum);
+    }
+    __syncthreads();
+
+    // 3.
+    uint64_t *seen = a.seen ? a.seen + (uint64_t)blockIdx.x * (a.cap + 1) : nullptr;
+    uint64_t held = 0;
+    if (seen) {
+        held = seen[0] < a.cap ? seen[0] : a.cap;  // (a buffer that was never cleared cannot send the scan out of bounds)
+        for (uint64_t j = tid; j < held; j += NT) {
+            const uint64_t h = seen[1 + j];
+            for (uint32_t s = 0; s < a.W; ++s)
+                if (keys[s] == h) hit[s] = 1;
+        }
+    }
+    uint32_t o = 0;
+    if (tid < a.W && a.live[slot0 + tid]) o = beam_order(a.cum[slot0 + tid]);
+    __syncthreads();
+    const bool revisit = tid < a.W && o && hit[tid];
+    if (tid < a.W) ord[tid] = revisit ? 0u : o;
+    __syncthreads();
+
+    // 4.
+    if (wave != 0) return;
+    const bool in = tid < a.W && o && !revisit;
+    bool dup = false;
+    uint64_t k = 0;
+    if (tid < a.W) {
+        k = keys[tid];
+        if (in)
+            for (uint32_t j = 0; j < a.W; ++j) {
+                const uint32_t oj = ord[j];
+                dup |= oj && keys[j] == k && (oj > o || (oj == o && j < tid));
+            }
+    }
+    const bool keep = in && !dup;
+    const uint64_t kept = __ballot(keep);
+    const uint32_t n_rev = (uint32_t)__popcll(__ballot(revisit)), n_dup = (uint32_t)__popcll(__ballot(dup));
+    if (tid < a.W) {
+        a.live_out[slot0 + tid] = keep ? 1 : 0;
+        if (a.keys_out) a.keys_out[slot0 + tid] = k;
+    }
+    if (seen) {
+        const uint64_t place = held + (uint64_t)__popcll(kept & ((1ull << lane) - 1ull));  // survivors in ascending slot order
+        if (keep && place < a.cap) seen[1 + place] = k;
+        const uint64_t total = held + (uint64_t)__popcll(kept);
+        if (lane == 0) seen[0] = total < a.cap ? total : a.cap;
+    }
+    if (a.dropped && lane == 0) {
+        a.dropped[2 * (uint64_t)blockIdx.x] += n_rev;
+        a.dropped[2 * (uint64_t)blockIdx.x + 1] += n_dup;
+    }
+}
+
 }  // namespace qg
 
 using namespace qg;
@@ -181,6 +298,47 @@ extern "C" int qg_beam_select(const void *logp_dev, int logp_dtype, uint64_t ld,
     case QG_DT_F32: hipLaunchKernelGGL(beam_select_kernel<float>, grid, block, lds, s, a); break;
     case QG_DT_BF16: hipLaunchKernelGGL(beam_select_kernel<uint16_t>, grid, block, lds, s, a); break;
     default: hipLaunchKernelGGL(beam_select_kernel<__half>, grid, block, lds, s, a); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}
+
+extern "C" size_t qg_beam_seen_bytes(uint64_t n_groups, uint64_t seen_cap) { return (size_t)(n_groups * (seen_cap + 1) * sizeof(uint64_t)); }
+
+extern "C" int qg_beam_merge(const void *words_dev, int word_bytes, uint32_t words_per_env, uint64_t n_groups, uint32_t width, const float *cum_dev,
+                             const uint8_t *live_dev, void *seen_dev, uint64_t seen_cap, uint8_t *live_out_dev, uint64_t *keys_out_dev,
+                             uint32_t *dropped_dev, void *stream) {
+    if (!words_dev || !cum_dev || !live_dev || !live_out_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (word_bytes != 1 && word_bytes != 4 && word_bytes != 8) return set_error(QG_ERR_INVALID, "word_bytes must be 1, 4 or 8");
+    if (words_per_env == 0 || width == 0) return set_error(QG_ERR_INVALID, "bad shape: width and words_per_env must be positive");
+    if (seen_dev && seen_cap == 0) return set_error(QG_ERR_INVALID, "a history needs seen_cap >= 1");
+    if (live_out_dev == live_dev) return set_error(QG_ERR_INVALID, "input and output arrays may not alias");
+    if (((uintptr_t)words_dev % (uintptr_t)word_bytes) || ((uintptr_t)seen_dev % 8) || ((uintptr_t)keys_out_dev % 8))
+        return set_error(QG_ERR_INVALID, "words, history and keys must be aligned to their element size");
+    if (width > BEAM_MAX_WIDTH || (uint64_t)words_per_env * (uint64_t)word_bytes > MERGE_MAX_ENV_BYTES)
+        return set_error(QG_ERR_UNSUPPORTED, "beam_merge: width <= %u and words_per_env * word_bytes <= %u supported", BEAM_MAX_WIDTH, MERGE_MAX_ENV_BYTES);
+    if (n_groups > 0x7FFFFFFFull || seen_cap > 0xFFFFFFFFull) return set_error(QG_ERR_UNSUPPORTED, "beam_merge: n_groups < 2^31 and seen_cap < 2^32 supported");
+    if (n_groups == 0) return QG_OK;
+    MergeArgs a;
+    a.words = words_dev;
+    a.cum = cum_dev;
+    a.live = live_dev;
+    a.seen = reinterpret_cast<uint64_t *>(seen_dev);
+    a.live_out = live_out_dev;
+    a.keys_out = keys_out_dev;
+    a.dropped = dropped_dev;
+    a.cap = seen_dev ? seen_cap : 0;
+    a.W = width;
+    a.n = words_per_env;
+    // one wave while a group's words and its history are a few hundred each; the result does not depend on it
+    const uint32_t waves = (uint64_t)width * words_per_env <= 512u && a.cap <= 512u ? 1u : MERGE_WAVES;
+    const dim3 grid((unsigned)n_groups), block(64u * waves);
+    const size_t lds = ((size_t)words_per_env + width) * sizeof(uint64_t) + (size_t)width * 2 * sizeof(uint32_t);  // <= 16 KiB + 1 KiB
+    hipStream_t s = (hipStream_t)stream;
+    switch (word_bytes) {
+    case 1: hipLaunchKernelGGL(beam_merge_kernel<uint8_t>, grid, block, lds, s, a); break;
+    case 4: hipLaunchKernelGGL(beam_merge_kernel<uint32_t>, grid, block, lds, s, a); break;
+    default: hipLaunchKernelGGL(beam_merge_kernel<uint64_t>, grid, block, lds, s, a); break;
     }
     HIP_TRY(hipGetLastError());
     return QG_OK;

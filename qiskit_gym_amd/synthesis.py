@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .collector import BasicPolicy, beam_select, embed, embed_words, mid_head_sample, pack_embed_words, pack_embedding, pack_head, pack_mid, sample_actions
+from .collector import BasicPolicy, beam_merge, beam_seen, beam_select, embed, embed_words, mid_head_sample, pack_embed_words, pack_embedding, pack_head, pack_mid, sample_actions
 from .envs.gyms import ROTATION_MARKER
 from .vec import VecEnv
 
@@ -120,7 +120,7 @@ class BatchedSynthesis:
             self._policy = self._policy.to(device=self._beam[1][0].device, dtype=self.dtype)
         return self._beam[1]
 
-    def _solve_beam(self, states: Sequence[Sequence[int]], W: int) -> List[Optional[List[int]]]:
+    def _solve_beam(self, states: Sequence[Sequence[int]], W: int, merge: bool = False) -> List[Optional[List[int]]]:
         M = len(states)
         cur, oth, win = self._beam_vecs(M, W)
         B, A, dev = cur.batch, cur.num_actions(), cur.device
@@ -137,6 +137,11 @@ class BatchedSynthesis:
         ret = torch.zeros(B, dtype=torch.float32, device=dev)
         nowhere = torch.full((M,), B, dtype=torch.int32, device=dev)  # out of range as a copy source: that entry is skipped
         steps = 0
+        if merge:  # the targets' own keys open the histories (one live slot per unsolved target: nothing to drop), so coming back to a target is a revisit
+            cap = T * W + 1  # a step adds at most W keys per target: the history of a search never fills
+            seen, dropped = beam_seen(M, cap, dev), torch.zeros((M, 2), dtype=torch.int32, device=dev)
+            words = cur.observe_packed()
+            live = beam_merge(words, cum, live, W, seen, cap)
         for t in range(T):
             logits = self._policy(cur.observe_as(self.dtype))[0]
             logp = torch.log_softmax(logits.float(), dim=1)
@@ -153,6 +158,8 @@ class BatchedSynthesis:
             win.copy_envs(oth, torch.where(better, group * W + j.to(torch.int32), nowhere))
             best = torch.where(better, val, best)
             found |= better
+            if merge:  # beams that ended (the step's results among them) have left `live`: they are neither merged nor recorded
+                live = beam_merge(oth.observe_packed(out=words), cum, live, W, seen, cap, dropped=dropped)
             cur, oth = oth, cur
             steps = t + 1
             if t % 8 == 7 and not bool(live.any()):
@@ -164,11 +171,14 @@ class BatchedSynthesis:
         out = [[int(x) for x in sols[m, : lens[m]]] if ok[m] else None for m in range(M)]
         gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
         self.last_stats = {"beam_width": W, "targets": M, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0}
+        if merge:
+            n_rev, n_dup = (int(x) for x in dropped.sum(dim=0).cpu())
+            self.last_stats.update(merged=n_dup, revisits=n_rev)
         return out
 
     @torch.no_grad()
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
-              beam_width: Optional[int] = None) -> List[Optional[List[int]]]:
+              beam_width: Optional[int] = None, merge_duplicates: bool = False) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         fast: run the sampled searches' forward pass and draw on the policy-layer kernels (bf16 products; default: when they apply and the
         batch has at least 4 096 envs); solutions are valid either way -- the env decides what solves a target, the policy only proposes.
@@ -180,14 +190,26 @@ class BatchedSynthesis:
         (`is_final`) leaves the search; if it ended with `success` it is a result, valued by its return like the sampled searches, and the
         first result of the highest return seen so far (lowest slot among equals in one step) is the target's winner.  The search ends when
         no beam is left or after max_depth steps.  The winner's own solution log is returned, so a PauliGym solution carries its rotation
-        markers without a replay.  Known limit: beams that reach the same state through commuting gates are not merged; they occupy a slot each."""
+        markers without a replay.  Known limit: beams that reach the same state through commuting gates are not merged; they occupy a slot each.
+
+        merge_duplicates=True (with beam_width) lifts that limit for the envs whose observation is their state (not PauliGym: ValueError).
+        After every step, among a target's beams that are still running, those whose state the target has held before -- the target
+        itself, or a survivor of an earlier step -- leave the search, and of those that share a state the one with the best score stays
+        (`collector.beam_merge` on the packed observation, one history of state keys per target).  Such a state was reached before with
+        at least as much depth left, so nothing is lost but slots are freed for distinct states; which targets are solved, and with how
+        many gates, may still change either way, since other beams survive.  `last_stats` then also counts the beams dropped: "merged"
+        (same state within a step) and "revisits"."""
         M = len(states)
         if M == 0:
             return []
         if beam_width is not None:
             if int(beam_width) < 1:
                 raise ValueError("beam_width must be at least 1")
-            return self._solve_beam(states, int(beam_width))
+            if merge_duplicates and self.env.env_kind == "pauli":
+                raise ValueError("merge_duplicates: a PauliGym observation does not determine its state (rotations beyond the observed columns, DAG order)")
+            return self._solve_beam(states, int(beam_width), bool(merge_duplicates))
+        if merge_duplicates:
+            raise ValueError("merge_duplicates needs beam_width")
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
         vec = self._vec(M * S, False)
         B, A, dev = vec.batch, vec.num_actions(), vec.device
@@ -258,9 +280,9 @@ class BatchedSynthesis:
             out.append([v for v in rep.solution(m) if v >= ROTATION_MARKER or v < A] if found[m] else None)
         return out
 
-    def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None):
+    def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
-        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, beam_width=beam_width)
+        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, beam_width=beam_width, merge_duplicates=merge_duplicates)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):

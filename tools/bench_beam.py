@@ -1,7 +1,10 @@
 """Beam search beside the sampled and the greedy search of BatchedSynthesis, with the reference's trained policies (tests/golden/policies):
 solved targets and mean gate count for beam_width 1 / 4 / 16, deterministic=True and num_searches=16 on the same targets; then the time of
 the selection kernel (`collector.beam_select`) beside the torch expression it replaces, alternating, on device events.  A record, not a gate.
-Run on the GPU box: python tools/bench_beam.py [--targets 1024]"""
+--merge: instead, beam_width 4 / 16 / 64 with and without merge_duplicates on the same targets: solved, mean gates, time per solve and the share
+of the live beams that the merge drops (revisits and duplicates apart); under `rocprofv3 --kernel-trace --stats` the same run gives
+beam_merge_kernel beside beam_select_kernel and copy_envs_kernel.
+Run on the GPU box: python tools/bench_beam.py [--targets 1024] [--merge [--widths 4 16 64]]"""
 import argparse
 import os
 import sys
@@ -44,6 +47,50 @@ def search_table(M: int, difficulty: int):
             st = syn.last_stats
             print(f"{name} x {M} targets (scrambles of {difficulty} gates), {label}: solved {st['solved']}/{M}, mean gates {st['mean_gates']:.2f}, "
                   f"{st['steps']} steps, {dt * 1e3:.1f} ms incl. handle creation", flush=True)
+
+
+def merge_table(M: int, difficulty: int, widths):
+    import qiskit_gym_amd.synthesis as synthesis
+
+    for name in ("clifford_3q_custom", "lf_5_line", "perm_square_3x3"):
+        cfg, gateset, w = load(name)
+        kind = MODELS[name]
+        gym = getattr(envs, GYMS[kind])(cfg["num_qubits"], gateset, depth_slope=cfg["depth_slope"], max_depth=cfg["max_depth"])
+        syn = BatchedSynthesis(gym, policy_from_reference_state_dict(w), seed=1)
+        v = gym.vec(M, add_inverts=False, add_perms=False, track_solution=False, difficulty=difficulty)
+        v.reset(3)
+        states = v.get_state("i64").cpu().numpy()
+        v.close()
+        for W in widths:
+            for merge in (False, True):
+                kw = dict(beam_width=W, merge_duplicates=merge)
+                syn.solve(states, **kw)  # warm-up: the handles of this batch shape
+                torch.cuda.synchronize()
+                best = float("inf")
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    syn.solve(states, **kw)
+                    torch.cuda.synchronize()
+                    best = min(best, time.perf_counter() - t0)
+                st = syn.last_stats
+                line = (f"{name} x {M} targets (scrambles of {difficulty} gates), beam_width={W}, merge_duplicates={merge}: solved {st['solved']}/{M}, "
+                        f"mean gates {st['mean_gates']:.3f}, {st['steps']} steps, {best * 1e3:.1f} ms per solve (best of 3)")
+                if merge:  # once more, untimed, counting the live beams every merge call is given (the first call holds the targets alone)
+                    seen_live, real = [], synthesis.beam_merge
+
+                    def counting(words, cum, live, *a, **k):
+                        seen_live.append(live.sum())
+                        return real(words, cum, live, *a, **k)
+
+                    synthesis.beam_merge = counting
+                    try:
+                        syn.solve(states, **kw)
+                    finally:
+                        synthesis.beam_merge = real
+                    offered = int(torch.stack(seen_live[1:]).sum())
+                    line += (f"; of {offered} live beams offered to the merge {syn.last_stats['revisits']} ({100.0 * syn.last_stats['revisits'] / max(1, offered):.1f} %) "
+                             f"were revisits, {syn.last_stats['merged']} ({100.0 * syn.last_stats['merged'] / max(1, offered):.1f} %) duplicates")
+                print(line, flush=True)
 
 
 def torch_select(logp, cum, live, W, A):
@@ -91,7 +138,12 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--targets", type=int, default=1024)
     ap.add_argument("--difficulty", type=int, default=32)
+    ap.add_argument("--merge", action="store_true", help="the merge_duplicates table instead of the search table and the selection times")
+    ap.add_argument("--widths", type=int, nargs="+", default=[4, 16, 64])
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
-    search_table(args.targets, args.difficulty)
-    select_times()
+    if args.merge:
+        merge_table(args.targets, args.difficulty, args.widths)
+    else:
+        search_table(args.targets, args.difficulty)
+        select_times()
