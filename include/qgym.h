@@ -33,7 +33,7 @@ extern "C" {
 
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
- *      qg_beam_merge, qg_beam_seen_bytes (additions only) */
+ *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -426,6 +426,44 @@ size_t qg_beam_seen_bytes(uint64_t n_groups, uint64_t seen_cap);
 int qg_beam_merge(const void *words_dev, int word_bytes, uint32_t words_per_env, uint64_t n_groups, uint32_t width, const float *cum_dev,
                   const uint8_t *live_dev, void *seen_dev, uint64_t seen_cap, uint8_t *live_out_dev, uint64_t *keys_out_dev,
                   uint32_t *dropped_dev, void *stream);
+/* Twists, batched: the symmetries of the coupling map as views of the observation (Env::twists, clifford.rs:370-372; symmetry.rs:205-295).
+ * For CliffordEnv, LinearFunctionEnv and PermutationEnv twist t is a pair: obs_perms[t] over the flat dense observation (rows * cols entries)
+ * and act_perms[t] over the actions.  THE DEFINITION, proved on the oracle env for every kind, twist and action (tests/test_twist_views.py):
+ *   view:    view_t(obs)[i] = obs[obs_perms[t][i]]                    -- a GATHER through obs_perms (the gather form holds; the scatter form,
+ *                                                                        out[obs_perms[t][i]] = obs[i], fails for every automorphism that is
+ *                                                                        not an involution, e.g. the rotations of a ring)
+ *   action:  an action a chosen on the view is the real action act_perms[t][a]   (PauliEnv's own convention, pauli.rs:596)
+ *   equivariance, for every state s, twist t, action a:
+ *            view_t(observe(step(s, act_perms[t][a]))) == observe(step(set_state(view_t(observe(s))), a))
+ * so a policy may look at a target through any twist, choose there, and the un-twisted action does to the real env what the chosen one
+ * does to the viewed one.
+ *
+ * qg_vec_twists: Env::twists of the batch's configuration with the contract of qg_env_twists (and the same host code): returns the number of
+ * twists; obs_perms_out[n * obs_size], act_perms_out[n * num_actions] are filled when non-NULL (count first, then fill).  0 when add_perms
+ * is off, always 0 for PauliEnv (pauli.rs:675-679: it permutes inside observe / step). */
+int64_t qg_vec_twists(const qg_vec *v, int64_t *obs_perms_out, int64_t *act_perms_out);
+/* The view of a packed observation: out_dev[e * rows*cols + i] = element obs_perms[twist_idx[e]][i] of what qg_expand_packed would write for env
+ * e, as `out_dtype` (int8, f16, bf16, f32).  packed_dev: the batch's QG_FMT_PACKED observation as qg_vec_observe_packed writes it, [batch, rows]
+ * words of word_bytes (4 / 8: bit c = column c; 1: the byte is the set column); obs_perms_dev int32 [n_twists, rows*cols]; twist_idx_dev
+ * int32 [batch].  Like qg_beam_merge the kernel knows no env: any words and any table will do (the table need not be a permutation).  A
+ * twist_idx[e] outside [0, n_twists) gives env e its untwisted observation (the host cannot see device indices); a table entry outside
+ * [0, rows*cols) reads as 0.  Limits: rows * word_bytes <= 2048 (an env's words live in LDS), batch < 2^31, n_twists * rows * cols < 2^31;
+ * QG_ERR_UNSUPPORTED beyond.  QG_ERR_INVALID for a null pointer, a zero size, cols that do not fit the word (> 8 * word_bytes; > 256 for bytes),
+ * an unknown dtype or word_bytes, or a buffer not aligned to its element size.  Output made of whole 16-byte chunks per env (rows*cols*element
+ * size a multiple of 16, out_dev and obs_perms_dev 16-byte aligned) is written with 16-byte stores, a wave 1 KiB at a time; other shapes one
+ * element per thread.  Stream-ordered on `stream`, one launch, no synchronisation, capturable into a hipGraph. */
+int qg_twist_expand_packed(const void *packed_dev, int word_bytes, uint64_t batch, uint32_t rows, uint32_t cols, const int32_t *obs_perms_dev,
+                           uint32_t n_twists, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, void *stream);
+/* The handle's own path: qg_vec_observe_packed into a buffer of the handle, then the view through the handle's obs_perms (two launches).  The
+ * table is uploaded once, by the first call (which therefore may not be made inside a stream capture; later ones may), and is owned by the
+ * handle.  QG_ERR_INVALID on a handle without twists (add_perms off, or a PauliEnv). */
+int qg_vec_observe_twisted(qg_vec *v, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, void *stream);
+/* out[e] = act_perms[twist_idx[e]][actions[e]]: actions chosen on views -> real actions.  actions_dev / out_dev: [batch] of `action_dtype`
+ * (qg_action_dtype; may be the same array), act_perms_dev int32 [n_twists, num_actions].  An action outside [0, num_actions) passes through
+ * unchanged (the "no gate" parking action of the search loops, clifford.rs:324), and so does every action of an env whose twist_idx is outside
+ * [0, n_twists).  One thread per env; stream-ordered, one launch, capturable. */
+int qg_untwist_actions(const void *actions_dev, int action_dtype, uint64_t batch, uint32_t num_actions, const int32_t *act_perms_dev,
+                       uint32_t n_twists, const int32_t *twist_idx_dev, void *out_dev, void *stream);
 /* Generalised advantage estimation over a [n_steps, batch] rollout (f32, done_t = the episode ended
  * with step t): delta_t = r_t + gamma*V_{t+1}*(1-done_t) - V_t, A_t = delta_t +
  * gamma*lambda*(1-done_t)*A_{t+1}, returns = A + V.  last_values_dev: V after the last step

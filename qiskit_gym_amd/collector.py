@@ -165,6 +165,49 @@ def expand_packed(packed: torch.Tensor, cols: int, dtype: torch.dtype, out: Opti
     return out
 
 
+def _twist_operands(name: str, perms: torch.Tensor, twist_idx: torch.Tensor, batch: int, width: int, dev):
+    if perms.dtype != torch.int32 or perms.dim() != 2 or perms.shape[1] != width or perms.shape[0] < 1 or not perms.is_contiguous() or perms.device != dev:
+        raise ValueError(f"{name}: the permutation table must be a contiguous int32 [n_twists, {width}] tensor on the device of the input")
+    if twist_idx.dtype != torch.int32 or twist_idx.numel() != batch or not twist_idx.is_contiguous() or twist_idx.device != dev:
+        raise ValueError(f"{name}: twist_idx must be a contiguous int32 [{batch}] tensor on the device of the input")
+
+
+def twist_expand_packed(packed: torch.Tensor, cols: int, obs_perms: torch.Tensor, twist_idx: torch.Tensor, dtype: torch.dtype,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Symmetry views of packed observations (`qg_twist_expand_packed`): out[e, i] = element obs_perms[twist_idx[e]][i] of what
+    `expand_packed` writes for env e -- a gather through the table, made while the bits are expanded.  packed: [B, rows] of 1-, 4- or 8-byte
+    integers (`VecEnv.observe_packed`); obs_perms: int32 [n_twists, rows*cols] (any table: the kernel knows no env); twist_idx: int32 [B],
+    an index outside [0, n_twists) gives that env its untwisted observation.  Returns dense {0,1} [B, rows*cols] in `dtype`."""
+    if packed.dim() != 2 or not packed.is_contiguous() or packed.is_floating_point() or packed.element_size() not in (1, 4, 8):
+        raise ValueError("twist_expand_packed: packed must be a contiguous [B, rows] tensor of 1-, 4- or 8-byte integers")
+    B, rows = packed.shape
+    _twist_operands("twist_expand_packed", obs_perms, twist_idx, B, rows * int(cols), packed.device)
+    if out is None:
+        out = torch.empty((B, rows * int(cols)), dtype=dtype, device=packed.device)
+    if out.dtype != dtype or out.numel() != B * rows * int(cols) or not out.is_contiguous() or out.device != packed.device:
+        raise ValueError("twist_expand_packed: `out` must be a contiguous [B, rows*cols] tensor of the requested dtype on the device of packed")
+    _lib.check(_lib.load().qg_twist_expand_packed(packed.data_ptr(), packed.element_size(), B, rows, int(cols), obs_perms.data_ptr(), obs_perms.shape[0],
+                                                  twist_idx.data_ptr(), out.data_ptr(), _DT[dtype], _stream_ptr()))
+    return out
+
+
+def untwist_actions(actions: torch.Tensor, act_perms: torch.Tensor, twist_idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Actions chosen on views -> real actions (`qg_untwist_actions`): out[e] = act_perms[twist_idx[e]][actions[e]].  actions: int32 / int64
+    [B]; act_perms: int32 [n_twists, num_actions]; twist_idx: int32 [B].  An action outside [0, num_actions) and every action of an env whose
+    twist index is out of range pass through unchanged.  `out` may be `actions` itself."""
+    if actions.dtype not in (torch.int32, torch.int64) or actions.dim() != 1 or not actions.is_contiguous():
+        raise ValueError("untwist_actions: actions must be a contiguous int32 / int64 [B] tensor")
+    B = actions.numel()
+    _twist_operands("untwist_actions", act_perms, twist_idx, B, act_perms.shape[1] if act_perms.dim() == 2 else 0, actions.device)
+    out = torch.empty_like(actions) if out is None else out
+    if out.dtype != actions.dtype or out.numel() != B or not out.is_contiguous() or out.device != actions.device:
+        raise ValueError("untwist_actions: `out` must match actions in dtype, size and device")
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_untwist_actions(actions.data_ptr(), act_dt, B, act_perms.shape[1], act_perms.data_ptr(), act_perms.shape[0],
+                                              twist_idx.data_ptr(), out.data_ptr(), _stream_ptr()))
+    return out
+
+
 def pack_embedding(env: VecEnv, weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """First-layer weight [hidden, rows*cols] (f32 / bf16) in the k order `embed` consumes (`qg_vec_pack_embedding`);
     repack after every optimiser step (pass `out` to rewrite the same buffer: graph-safe)."""

@@ -276,7 +276,7 @@ static int vec_free_buffers(qg_vec *v) {
     void *ptrs[] = {v->state, v->own_depth ? v->depth : nullptr, v->own_reward ? v->reward : nullptr,
                     v->own_done ? v->done : nullptr, v->own_success ? v->success : nullptr, v->inverted, v->own_error ? v->error : nullptr, v->sol,
                     v->sol_len, v->layers, v->d_gates, v->d_descs, v->scratch, v->d_prog,
-                    v->d_qubit_perms, v->d_act_perms, v->perm_idx, v->d_gen_tables, v->d_nonsymp, v->bad, v->done_list, v->done_list_alt, v->done_list_spare, v->done_mask[0], v->done_mask[1], v->mask_count, v->d_rowops, v->embed_dump, v->host_in, v->host_obs, v->fault_scratch};
+                    v->d_qubit_perms, v->d_act_perms, v->perm_idx, v->d_gen_tables, v->d_nonsymp, v->bad, v->done_list, v->done_list_alt, v->done_list_spare, v->done_mask[0], v->done_mask[1], v->mask_count, v->d_rowops, v->embed_dump, v->host_in, v->host_obs, v->fault_scratch, v->d_twist_obs, v->twist_words};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     drop_graphs(v);

@@ -148,6 +148,44 @@ void compute_qubit_and_action_perms(uint32_t N, const std::vector<qg_gate> &gate
     }
 }
 
+// Env::twists (clifford.rs:370-372): (obs_perms, act_perms), empty when add_perms is off (clifford.rs:218-222) and always for PauliEnv
+// (pauli.rs:675-679).  The one host routine behind qg_env_twists, qg_vec_twists and the table qg_vec_observe_twisted uploads.
+void build_twists(const qg_vec *v, std::vector<Perm> &obs_perms, std::vector<Perm> &act_perms) {
+    obs_perms.clear();
+    act_perms.clear();
+    if (!v->cfg.add_perms || v->cfg.env_kind == QG_PAULI) return;
+    std::vector<Perm> qp;
+    compute_qubit_and_action_perms(v->N, v->gates, qp, act_perms);
+    const uint32_t N = v->N;
+    for (const Perm &p : qp) {
+        Perm op;
+        if (v->cfg.env_kind == QG_CLIFFORD) {  // obs_perm_clifford (symmetry.rs:276-295)
+            const uint32_t dim = 2 * N;
+            op.resize((size_t)dim * dim);
+            for (uint32_t r = 0; r < dim; ++r) {
+                const int64_t mr = r < N ? p[r] : N + p[r - N];
+                for (uint32_t c = 0; c < dim; ++c) {
+                    const int64_t mc = c < N ? p[c] : N + p[c - N];
+                    op[(size_t)r * dim + c] = mr * dim + mc;
+                }
+            }
+        } else {  // obs_perm_square (symmetry.rs:265-274)
+            op.resize((size_t)N * N);
+            for (uint32_t r = 0; r < N; ++r)
+                for (uint32_t c = 0; c < N; ++c) op[(size_t)r * N + c] = p[r] * N + p[c];
+        }
+        obs_perms.push_back(op);
+    }
+}
+
+// the handle's own copy, built on first use
+static void vec_twists(const qg_vec *cv) {
+    qg_vec *v = const_cast<qg_vec *>(cv);
+    if (v->twists_done) return;
+    build_twists(v, v->obs_perms, v->act_perms);
+    v->twists_done = true;
+}
+
 }  // namespace qg
 
 // ---- scalar env ---------------------------------------------------------------------------------------------------------------
@@ -485,28 +523,7 @@ int64_t qg_env_twists(const qg_env *ce, int64_t *obs_out, int64_t *act_out) {
     // add_perms off -> (empty, empty) (clifford.rs:218-222); PauliEnv always returns empty (pauli.rs:675-679)
     if (!v->cfg.add_perms || v->cfg.env_kind == QG_PAULI) return 0;
     if (!e->twists_done) {
-        std::vector<Perm> qp;
-        compute_qubit_and_action_perms(v->N, v->gates, qp, e->act_perms);
-        const uint32_t N = v->N;
-        for (const Perm &p : qp) {
-            Perm op;
-            if (v->cfg.env_kind == QG_CLIFFORD) {  // obs_perm_clifford (symmetry.rs:276-295)
-                const uint32_t dim = 2 * N;
-                op.resize((size_t)dim * dim);
-                for (uint32_t r = 0; r < dim; ++r) {
-                    const int64_t mr = r < N ? p[r] : N + p[r - N];
-                    for (uint32_t c = 0; c < dim; ++c) {
-                        const int64_t mc = c < N ? p[c] : N + p[c - N];
-                        op[(size_t)r * dim + c] = mr * dim + mc;
-                    }
-                }
-            } else {  // obs_perm_square (symmetry.rs:265-274)
-                op.resize((size_t)N * N);
-                for (uint32_t r = 0; r < N; ++r)
-                    for (uint32_t c = 0; c < N; ++c) op[(size_t)r * N + c] = p[r] * N + p[c];
-            }
-            e->obs_perms.push_back(op);
-        }
+        build_twists(v, e->obs_perms, e->act_perms);
         e->twists_done = true;
     }
     const size_t n = e->obs_perms.size();
@@ -515,6 +532,58 @@ int64_t qg_env_twists(const qg_env *ce, int64_t *obs_out, int64_t *act_out) {
         if (act_out) std::copy(e->act_perms[i].begin(), e->act_perms[i].end(), act_out + i * e->act_perms[i].size());
     }
     return (int64_t)n;
+}
+
+
+int64_t qg_vec_twists(const qg_vec *v, int64_t *obs_out, int64_t *act_out) {
+    if (!v) return set_error(QG_ERR_INVALID, "null argument");
+    vec_twists(v);
+    const size_t n = v->obs_perms.size();
+    for (size_t i = 0; i < n; ++i) {
+        if (obs_out) std::copy(v->obs_perms[i].begin(), v->obs_perms[i].end(), obs_out + i * v->obs_perms[i].size());
+        if (act_out) std::copy(v->act_perms[i].begin(), v->act_perms[i].end(), act_out + i * v->act_perms[i].size());
+    }
+    return (int64_t)n;
+}
+
+int qg_vec_observe_twisted(qg_vec *v, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, void *stream) {
+    if (!v || !twist_idx_dev || !out_dev) return set_error(QG_ERR_INVALID, "null argument");
+    vec_twists(v);
+    if (v->obs_perms.empty()) return set_error(QG_ERR_INVALID, "observe_twisted: the handle has no twists (add_perms is off, or a PauliEnv)");
+    QG_ON_DEVICE(v);
+    qg_vec_info info;
+    qg_vec_get_info(v, &info);
+    const size_t obs = (size_t)info.obs_rows * info.obs_cols, K = v->obs_perms.size();
+    if (!v->d_twist_obs) {  // the table goes to the device once (a blocking copy: the first call of a handle is not made inside a stream capture)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) (void)hipGetLastError();
+        if (cs != hipStreamCaptureStatusNone) return set_error(QG_ERR_INVALID, "observe_twisted: call it once before capturing it (the first call uploads the table)");
+        std::vector<int32_t> flat(K * obs);
+        for (size_t t = 0; t < K; ++t)
+            for (size_t i = 0; i < obs; ++i) flat[t * obs + i] = (int32_t)v->obs_perms[t][i];
+        int32_t *dev = nullptr;
+        HIP_TRY(hipMalloc((void **)&dev, flat.size() * sizeof(int32_t)));
+        if (hipMemcpy(dev, flat.data(), flat.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(dev);
+            return set_error(QG_ERR_DEVICE, "observe_twisted: table upload failed");
+        }
+        v->d_twist_obs = dev;
+    }
+    const size_t words = (size_t)v->B * info.packed_words_per_env * info.packed_word_bytes;
+    if (v->twist_words_bytes < words) {  // the packed observation between the two launches (its own buffer: a view may be captured into a graph)
+        if (v->twist_words) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipFree(v->twist_words));
+            v->twist_words = nullptr;
+            v->twist_words_bytes = 0;
+        }
+        HIP_TRY(hipMalloc(&v->twist_words, words));
+        v->twist_words_bytes = words;
+    }
+    if (int rc = qg_vec_observe_packed(v, v->twist_words, stream)) return rc;
+    return twist_expand_impl(v->twist_words, (int)info.packed_word_bytes, v->B, info.packed_words_per_env, (uint32_t)info.obs_cols, v->d_twist_obs,
+                             (uint32_t)K, twist_idx_dev, out_dev, out_dtype, (hipStream_t)stream);
 }
 
 }  // extern "C"

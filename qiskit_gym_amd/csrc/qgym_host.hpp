@@ -143,6 +143,13 @@ struct qg_vec {
     bool perm_draw = false;            // the export in flight is an observe() (draws a new perm)
     uint64_t observe_counter = 0;
 
+    // twists (qgym_env.cpp): Env::twists of this configuration, built on first use; the observation table on the device once a view was asked for
+    bool twists_done = false;
+    std::vector<std::vector<int64_t>> obs_perms, act_perms;
+    int32_t *d_twist_obs = nullptr;    // [n twists][obs_rows * obs_cols]
+    void *twist_words = nullptr;       // qg_vec_observe_twisted: the packed observation its view is made from
+    size_t twist_words_bytes = 0;
+
     // rollout graphs
     std::vector<qg::CachedGraph> graphs;
     hipStream_t capture_stream = nullptr;
@@ -178,6 +185,11 @@ int dense_refresh(qg_vec *v, hipStream_t s);
 void fill_reset_done_args(const qg_vec *v, uint64_t seed, InitArgs &ia);
 void compute_qubit_and_action_perms(uint32_t N, const std::vector<qg_gate> &gates, std::vector<std::vector<int64_t>> &qubit_perms,
                                     std::vector<std::vector<int64_t>> &act_perms);
+// Env::twists of a handle's configuration (qgym_env.cpp)
+void build_twists(const qg_vec *v, std::vector<std::vector<int64_t>> &obs_perms, std::vector<std::vector<int64_t>> &act_perms);
+// qg_twist_expand_packed (kernels_twist.hip)
+int twist_expand_impl(const void *packed_dev, int word_bytes, uint64_t batch, uint32_t rows, uint32_t cols, const int32_t *obs_perms_dev,
+                      uint32_t n_twists, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, hipStream_t s);
 // PauliEnv host hooks (pauli_host.cpp)
 int pauli_alloc(qg_vec *v);
 int pauli_init_identity(qg_vec *v, hipStream_t s);

@@ -16,6 +16,10 @@ recovered by replaying the winners on a `track_solution` batch.
 
 `solve(..., beam_width=W)` searches differently: a deterministic beam search over the policy's log-probabilities, W beams per target, on
 the batched clone (`VecEnv.copy_envs`) and the device-side selection kernel (`collector.beam_select`); see `solve`.
+
+`solve(..., twists=V)` gives every target V symmetry views (`VecEnv.observe_twisted` / `untwist_actions`): the policy looks at a target through
+an automorphism of the coupling map and its choice is mapped back, what `RLSynthesis.init_algorithm` hands the reference's policy as
+`obs_perms` / `act_perms` (rl/synthesis.py:97-104) -- here one fixed view per search, so the deterministic searches get V opinions per target.
 """
 from __future__ import annotations
 
@@ -55,6 +59,7 @@ class BatchedSynthesis:
         self._policy = policy
         self._vecs: Dict[tuple, VecEnv] = {}
         self._beam = None  # ((targets, width), (two search batches, the winners)): the beam search's handles
+        self._view_list = None  # twists: the twist index behind each view (`_views`)
         self._packed = None  # (vec, packed first layer, its f32 bias, packed middle layer, packed head): the policy-layer kernels' operands
         self.last_stats: dict = {}
 
@@ -82,14 +87,21 @@ class BatchedSynthesis:
             self._packed = None
         return self._packed
 
-    def _vec(self, batch: int, track_solution: bool) -> VecEnv:
-        key = (batch, track_solution)
+    def _vec(self, batch: int, track_solution: bool, perms: bool = False) -> VecEnv:
+        key = (batch, track_solution, True) if perms else (batch, track_solution)  # add_perms: twists() only, the env steps alike
         if key not in self._vecs:
             for k in [k for k in self._vecs if k[1] == track_solution]:  # one batch size at a time: the handles own device memory
                 self._vecs.pop(k).close()
-            self._vecs[key] = self.env.vec(batch, device=self.device, add_inverts=False, add_perms=False, track_solution=track_solution)
+            self._vecs[key] = self.env.vec(batch, device=self.device, add_inverts=False, add_perms=perms, track_solution=track_solution)
             self._policy = self._policy.to(device=self._vecs[key].device, dtype=self.dtype)
         return self._vecs[key]
+
+    def _observe(self, vec: VecEnv, tw: Optional[torch.Tensor]) -> torch.Tensor:
+        """What the policy reads, in its dtype: the observation, or under twists env e through twist tw[e].  A dtype the library does not
+        write (float64) is written as float32 and widened: the entries are 0 and 1."""
+        dt = self.dtype if self.dtype in VecEnv._DTYPES else torch.float32
+        x = vec.observe_as(dt) if tw is None else vec.observe_twisted(tw, dt)
+        return x if dt == self.dtype else x.to(self.dtype)
 
     def _load(self, vec: VecEnv, states: Sequence[Sequence[int]], repeat: int):
         if vec.env_kind == "pauli":
@@ -108,24 +120,53 @@ class BatchedSynthesis:
         else:
             vec.set_state(np.repeat(np.asarray(states, dtype=np.int64), repeat, axis=0), fmt="i64")
 
-    def _beam_vecs(self, M: int, W: int):
+    def _beam_vecs(self, M: int, W: int, perms: bool = False):
         """The beam search's handles: two batches of M * W envs that take turns as source and destination of the per-step copy, and the M
         winners.  All three have the same constructor arguments (the rule of `copy_envs`; no layout choice depends on the batch size)."""
-        if self._beam is None or self._beam[0] != (M, W):
+        key = (M, W, True) if perms else (M, W)
+        if self._beam is None or self._beam[0] != key:
             if self._beam is not None:
                 for v in self._beam[1]:
                     v.close()
-            mk = lambda batch: self.env.vec(batch, device=self.device, add_inverts=False, add_perms=False, track_solution=True)  # noqa: E731
-            self._beam = ((M, W), (mk(M * W), mk(M * W), mk(M)))
+            mk = lambda batch: self.env.vec(batch, device=self.device, add_inverts=False, add_perms=perms, track_solution=True)  # noqa: E731
+            self._beam = (key, (mk(M * W), mk(M * W), mk(M)))
             self._policy = self._policy.to(device=self._beam[1][0].device, dtype=self.dtype)
         return self._beam[1]
 
-    def _solve_beam(self, states: Sequence[Sequence[int]], W: int, merge: bool = False) -> List[Optional[List[int]]]:
+    def _views(self, V: int) -> List[int]:
+        """Twist index of each of a target's views: view 0 is the untwisted one (-1: no such twist, `observe_twisted` and `untwist_actions`
+        pass through), then the env's non-identity twists -- those that move an observation entry -- in `twists()` order; at most V of them."""
+        if self._view_list is None:
+            probe = self.env.vec(1, device=self.device, add_inverts=False, add_perms=True, track_solution=False)
+            obs_perms = probe.twists()[0]
+            probe.close()
+            self._view_list = [-1] + [t for t, p in enumerate(obs_perms) if p != list(range(len(p)))]
+        return self._view_list[:V]
+
+    def _solve_beam(self, states: Sequence[Sequence[int]], W: int, merge: bool = False, twists: Optional[int] = None) -> List[Optional[List[int]]]:
+        if twists is not None:
+            return self._solve_beam_views(states, W, merge, twists)
         M = len(states)
         cur, oth, win = self._beam_vecs(M, W)
+        return self._beam_search(states, 1, None, W, merge, cur, oth, win)
+
+    def _solve_beam_views(self, states, W: int, merge: bool, twists: int) -> List[Optional[List[int]]]:
+        """Beam search under V views per target: the groups are the (target, view) pairs, each searched under its own fixed view (and with
+        its own merge history); a target's winner is the best result of its V groups, ties to the lowest view."""
+        M = len(states)
+        views = self._views(int(twists))
+        V = len(views)
+        cur, oth, win = self._beam_vecs(M * V, W, True)
+        tw = torch.tensor(views, dtype=torch.int32, device=cur.device).repeat(M).repeat_interleave(W).contiguous()  # env b: group b // W, view (b // W) % V
+        return self._beam_search(states, V, tw, W, merge, cur, oth, win)
+
+    def _beam_search(self, states, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv):
+        """`tw` None: the search of `solve(beam_width=W)`.  Else int32 [B]: every env's twist index; there are V consecutive groups per target."""
+        targets = len(states)
+        M = targets * V  # groups
         B, A, dev = cur.batch, cur.num_actions(), cur.device
         T = int(cur._cfg.max_depth)
-        self._load(win, states, 1)  # the targets once; a target nobody solves keeps its slot, a solved one is overwritten by its winner
+        self._load(win, states, V)  # the targets once per group; a group nobody solves keeps its slot, a solved one is overwritten by its winner
         group = torch.arange(M, dtype=torch.int32, device=dev)
         cur.copy_envs(win, group.repeat_interleave(W))
         found = win.success.bool().clone()  # a target that is already solved needs no gates: its winner is the target itself
@@ -143,9 +184,11 @@ class BatchedSynthesis:
             words = cur.observe_packed()
             live = beam_merge(words, cum, live, W, seen, cap)
         for t in range(T):
-            logits = self._policy(cur.observe_as(self.dtype))[0]
+            logits = self._policy(self._observe(cur, tw))[0]
             logp = torch.log_softmax(logits.float(), dim=1)
             parent, act, cum, live = beam_select(logp, cum, live, W, A)
+            if tw is not None:  # chosen on the view: the real action (a child lives in its parent's group, hence under its view)
+                cur.untwist_actions(act, tw, out=act)
             oth.copy_envs(cur, parent)
             oth.step(act)
             ret = ret[parent.long()] + oth.reward  # the return `solve` ranks by: the parent's plus this step's reward
@@ -167,10 +210,17 @@ class BatchedSynthesis:
         for v in (cur, oth, win):
             v.sync()
         sols, lens = win.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
-        ok = found.cpu().numpy()
-        out = [[int(x) for x in sols[m, : lens[m]]] if ok[m] else None for m in range(M)]
+        if tw is not None:  # per target the best of its V groups; argmax takes the first of equal maxima: the lowest view
+            pick = (torch.arange(targets, device=dev) * V + best.view(targets, V).argmax(dim=1)).cpu().numpy()
+            ok = found.cpu().numpy()[pick]
+            sols, lens = sols[pick], lens[pick]
+        else:
+            ok = found.cpu().numpy()
+        out = [[int(x) for x in sols[m, : lens[m]]] if ok[m] else None for m in range(targets)]
         gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
-        self.last_stats = {"beam_width": W, "targets": M, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0}
+        self.last_stats = {"beam_width": W, "targets": targets, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0}
+        if tw is not None:
+            self.last_stats["views"] = V
         if merge:
             n_rev, n_dup = (int(x) for x in dropped.sum(dim=0).cpu())
             self.last_stats.update(merged=n_dup, revisits=n_rev)
@@ -178,7 +228,7 @@ class BatchedSynthesis:
 
     @torch.no_grad()
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
-              beam_width: Optional[int] = None, merge_duplicates: bool = False) -> List[Optional[List[int]]]:
+              beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         fast: run the sampled searches' forward pass and draw on the policy-layer kernels (bf16 products; default: when they apply and the
         batch has at least 4 096 envs); solutions are valid either way -- the env decides what solves a target, the policy only proposes.
@@ -198,8 +248,27 @@ class BatchedSynthesis:
         (`collector.beam_merge` on the packed observation, one history of state keys per target).  Such a state was reached before with
         at least as much depth left, so nothing is lost but slots are freed for distinct states; which targets are solved, and with how
         many gates, may still change either way, since other beams survive.  `last_stats` then also counts the beams dropped: "merged"
-        (same state within a step) and "revisits"."""
+        (same state within a step) and "revisits".
+
+        twists=V >= 1: V symmetry views per target (None: none of this; every code path, handle and `last_stats` as without the argument).
+        View 0 is the untwisted observation, views 1 .. V-1 the env's non-identity twists in `VecEnv.twists()` order; V is cut to what the
+        coupling map has and `last_stats["views"]` says how many were used.  The policy reads `VecEnv.observe_twisted`, its choice goes
+        through `VecEnv.untwist_actions` before `step`: solutions hold real actions.  The search handles are built with `add_perms=True`,
+        which for these env kinds changes `twists()` only.  Sampled and greedy searches: search s of a target keeps view s mod V for its whole
+        episode, and `deterministic=True` runs V episodes per target instead of one (ties between equal returns go to the lowest view).  Beam
+        search: the groups are the (target, view) pairs -- V groups of W beams per target, each under its own view and with its own merge
+        history -- and a target's winner is the best result over its groups, ties to the lowest view.  View 0 is the search without twists,
+        so under the default reward weights `twists=V` never solves fewer targets nor needs more gates than `twists=None` in the two
+        deterministic modes.  The policy-layer kernels read the resident state and cannot see a view: the torch forward is used, and
+        `fast=True` with `twists` is a ValueError; so is PauliGym, which permutes inside observe / step and has no twists (pauli.rs:675-679)."""
         M = len(states)
+        if twists is not None:
+            if int(twists) < 1:
+                raise ValueError("twists must be at least 1")
+            if self.env.env_kind == "pauli":
+                raise ValueError("twists: PauliGym permutes inside observe() / step() and exposes no twists (pauli.rs:675-679)")
+            if fast:
+                raise ValueError("fast=True cannot be combined with twists: the policy-layer kernels read the resident state, not a view")
         if M == 0:
             return []
         if beam_width is not None:
@@ -207,11 +276,19 @@ class BatchedSynthesis:
                 raise ValueError("beam_width must be at least 1")
             if merge_duplicates and self.env.env_kind == "pauli":
                 raise ValueError("merge_duplicates: a PauliGym observation does not determine its state (rotations beyond the observed columns, DAG order)")
-            return self._solve_beam(states, int(beam_width), bool(merge_duplicates))
+            return self._solve_beam(states, int(beam_width), bool(merge_duplicates), twists)
         if merge_duplicates:
             raise ValueError("merge_duplicates needs beam_width")
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
-        vec = self._vec(M * S, False)
+        tw = None
+        if twists is not None:
+            views = self._views(int(twists))
+            if deterministic:
+                S = len(views)  # ... but for the view they are seen through
+            vec = self._vec(M * S, False, True)
+            tw = torch.tensor([views[s % len(views)] for s in range(S)], dtype=torch.int32, device=vec.device).repeat(M).contiguous()  # env m * S + s: view s mod V
+        else:
+            vec = self._vec(M * S, False)
         B, A, dev = vec.batch, vec.num_actions(), vec.device
         self._load(vec, states, S)
         T = int(vec._cfg.max_depth)
@@ -222,7 +299,7 @@ class BatchedSynthesis:
         parked = torch.full((B,), A, dtype=torch.int32, device=dev)  # out of range: no gate (clifford.rs:324)
         steps = 0
         kern = None
-        if not deterministic and fast is not False and (fast or B >= 4096):
+        if tw is None and not deterministic and fast is not False and (fast or B >= 4096):
             kern = self._kernels(vec)
             if fast and kern is None:
                 raise ValueError("fast=True needs a BasicPolicy of the default shape and an env whose state or packed observation the first-layer kernels read")
@@ -241,12 +318,14 @@ class BatchedSynthesis:
                     embed(vec, kern[1], kern[2], h1.shape[1], relu=True, out=h1)
                 mid_head_sample(h1, kern[3], pol.common.out_features, kern[4], A, self.seed, t, actions=act, logp=scratch[0], entropy=scratch[1], values=scratch[2])
             else:
-                x = vec.observe_as(self.dtype)
+                x = self._observe(vec, tw)
                 logits = self._policy(x)[0]
                 if deterministic:
                     act = logits.argmax(dim=1).to(torch.int32)
                 else:
                     act = sample_actions(logits.contiguous(), self.seed, t)[0].to(torch.int32)
+                if tw is not None:  # chosen on the view: the real action
+                    vec.untwist_actions(act, tw, out=act)
             actions[t] = torch.where(finished, parked, act)
             vec.step(actions[t])
             live = ~finished
@@ -266,6 +345,8 @@ class BatchedSynthesis:
         win = actions[:steps, idx].t().contiguous()  # [M, steps]
         self.last_stats.update({"targets": M, "searches": S, "steps": steps, "solved": int(found.sum()),
                            "searches_solved": float(ok.float().mean()), "mean_gates": float(lengths[found].mean()) if found.any() else 0.0})
+        if tw is not None:
+            self.last_stats["views"] = len(views)
         if vec.env_kind != "pauli":
             w = win.cpu().numpy()
             return [w[m, : lengths[m]].tolist() if found[m] else None for m in range(M)]
@@ -280,9 +361,11 @@ class BatchedSynthesis:
             out.append([v for v in rep.solution(m) if v >= ROTATION_MARKER or v < A] if found[m] else None)
         return out
 
-    def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False):
+    def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
+              twists: Optional[int] = None):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
-        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, beam_width=beam_width, merge_duplicates=merge_duplicates)
+        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, beam_width=beam_width, merge_duplicates=merge_duplicates,
+                          twists=twists)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):

@@ -315,6 +315,67 @@ class VecEnv:
         _lib.check(self._L.qg_vec_observe_dense_as(self._h, out.data_ptr(), self._DTYPES[dtype], self._stream()))
         return out
 
+    # ---- twists: the symmetries of the coupling map as views of the observation (include/qgym.h, "Twists, batched") ----
+    def twists(self) -> Tuple[list, list]:
+        """Env::twists (clifford.rs:370-372): (obs_perms, act_perms) as lists, what `RawEnv.twists()` returns for the same configuration:
+        empty without `add_perms`, always empty for PauliEnv."""
+        if getattr(self, "_twists", None) is None:
+            n = int(self._L.qg_vec_twists(self._h, None, None))
+            if n < 0:
+                _lib.check(n)
+            r, c = self.obs_shape_
+            ob = np.zeros((n, r * c), dtype=np.int64)
+            ab = np.zeros((n, self.num_actions_), dtype=np.int64)
+            if n:
+                self._L.qg_vec_twists(self._h, ob.ctypes.data_as(C.POINTER(C.c_int64)), ab.ctypes.data_as(C.POINTER(C.c_int64)))
+            self._twists = (ob, ab)
+        ob, ab = self._twists
+        return ob.tolist(), ab.tolist()
+
+    @property
+    def num_twists(self) -> int:
+        self.twists()
+        return int(self._twists[0].shape[0])
+
+    def _twist_idx(self, name: str, twist_idx: torch.Tensor) -> torch.Tensor:
+        if not isinstance(twist_idx, torch.Tensor) or twist_idx.device != self.device or twist_idx.dtype != torch.int32 \
+                or twist_idx.numel() != self.batch or not twist_idx.is_contiguous():
+            raise ValueError(f"{name}: twist_idx must be a contiguous int32 [{self.batch}] tensor on the env's device")
+        return twist_idx
+
+    def observe_twisted(self, twist_idx: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Dense observation [B, rows*cols] in `dtype`, env e seen through twist twist_idx[e] (`qg_vec_observe_twisted`): out[e, i] =
+        observe()[e, obs_perms[twist_idx[e]][i]].  An index outside [0, num_twists) gives the untwisted observation.  An action chosen on
+        such a view becomes the real one by `untwist_actions`.  The library's invalid-argument error on an env without twists."""
+        self._twist_idx("observe_twisted", twist_idx)
+        r, c = self.obs_shape_
+        if out is None:
+            out = torch.empty((self.batch, r * c), dtype=dtype, device=self.device)
+        if out.dtype != dtype or out.numel() != self.batch * r * c or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("observe_twisted: `out` must be a contiguous [B, rows*cols] tensor of the requested dtype on the env's device")
+        _lib.check(self._L.qg_vec_observe_twisted(self._h, twist_idx.data_ptr(), out.data_ptr(), self._DTYPES[dtype], self._stream()))
+        return out
+
+    def untwist_actions(self, actions: torch.Tensor, twist_idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out[e] = act_perms[twist_idx[e]][actions[e]] (`qg_untwist_actions`): the real action of one chosen on `observe_twisted`'s view.
+        Actions outside [0, num_actions) and envs with an out-of-range twist index pass through; `out` may be `actions`."""
+        self._twist_idx("untwist_actions", twist_idx)
+        if self.num_twists == 0:
+            raise ValueError("untwist_actions: this env has no twists (add_perms is off, or a PauliEnv)")
+        if getattr(self, "_act_perms_dev", None) is None:
+            self._act_perms_dev = torch.as_tensor(self._twists[1].astype(np.int32), device=self.device)
+        actions = actions.contiguous()
+        if actions.numel() != self.batch:
+            raise ValueError(f"untwist_actions: one action per env ({self.batch}), got {tuple(actions.shape)}")
+        ptr, dt = self._act(actions)
+        out = torch.empty_like(actions) if out is None else out
+        if out.dtype != actions.dtype or out.numel() != self.batch or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("untwist_actions: `out` must match actions in dtype, size and device")
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.qg_untwist_actions(ptr, dt, self.batch, self.num_actions_, self._act_perms_dev.data_ptr(), self.num_twists,
+                                                  twist_idx.data_ptr(), out.data_ptr(), self._stream()))
+        return out
+
     def pauli_observe(self, perm_idx: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """PauliEnv observe() with the qubit-permutation draws given explicitly (int32 [B])."""
         r, c = self.obs_shape_
