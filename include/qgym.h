@@ -33,7 +33,8 @@ extern "C" {
 
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
- *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions (additions only) */
+ *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
+ *      qg_policy_head_logp, qg_policy_mid_head_logp (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -533,7 +534,38 @@ int qg_policy_pack_mid(const void *weight_dev, const void *bias_dev, int dtype, 
 int qg_policy_mid_head_sample(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_mid_dev, uint32_t mid_features,
                               const void *packed_head_dev, uint32_t num_actions, uint64_t seed, uint64_t counter, const uint64_t *clock_dev, void *actions_dev,
                               int action_dtype, float *logp_dev, float *entropy_dev, float *values_dev, void *stream);
-/* The same kernel followed, in the same launch, by Env::step of handle `v` with the action it drew (the lane that holds an env's draw
+/* The deterministic twins of qg_policy_head_sample / qg_policy_mid_head_sample: the same kernels with another epilogue, which writes the
+ * whole row of log-probabilities and the arg-max instead of one draw -- what a greedy or a beam search asks of the policy (the rows go
+ * straight into qg_beam_select).  Operands, packing (qg_policy_pack_head without / with after_mid, qg_policy_pack_mid), limits, alignment
+ * rules and the choice between the small-batch and the large-batch kernel are those of the _sample call; the logit contract is the one
+ * stated above qg_policy_head_packed_bytes.  There is no seed, counter or clock: for a given batch size and device the result depends on
+ * the operands alone (no atomics, no order that varies from launch to launch).  The small-batch and the large-batch kernel -- chosen by batch
+ * size, in_features and the device's CU count, as for the _sample call -- add the terms of s below in different orders, so the same row can
+ * differ between the two in the last bits of logf(s), and with it in every log-prob of the row and the entropy: equal up to the rounding of
+ * that sum, not bit for bit (the _sample call's log-prob and entropy behave the same way).  The rules:
+ *   - With m = the row's largest logit and s = sum_a exp(logit[a] - m) (the hardware's exp2 of (logit - m) * log2(e), as in the draw; f32),
+ *     logp_rows_dev[e * ld_logp + a] = (logit[a] - m) - logf(s) for a < num_actions: two f32 subtractions, nothing contracted -- the very
+ *     expression, operand order and bits of the log-prob the _sample call reports for an action it drew, and entropy_dev / values_dev are
+ *     that call's bits as well.
+ *   - A masked action (logit below -1e29: a bias at or below -1e30, -inf, the dtype's lowest) gets -inf, which qg_beam_select reads as "no
+ *     such candidate".  An action that is merely far below the maximum (exp flushes to 0 from about 87 on) keeps its finite value.
+ *   - actions_dev[e] = the action of the largest logit, equal logits to the lowest action index; padding rows and the value row never win.
+ *     best_logp_dev[e] = the log-prob of that action, the bits of logp_rows_dev[e * ld_logp + action].
+ *   - A row without a live action (largest logit below -1e29) gives action 0, best log-prob 0, entropy 0 and a row of -inf: the empty row of
+ *     the _sample call.
+ *   - NaN and +inf are outside the contract as there: the call terminates and the action lies in [0, num_actions).
+ * logp_rows_dev: f32 [batch, ld_logp], ld_logp >= num_actions (QG_ERR_INVALID otherwise).  Columns num_actions .. ld_logp-1 and rows >= batch
+ * are never written.  A row base and stride that are multiples of 16 bytes get 16-byte stores, any 4-byte aligned layout works.  EVERY
+ * output pointer may be NULL: without logp_rows_dev no row is written (the arg-max-only step of a greedy search); all five NULL is
+ * QG_ERR_INVALID.  Limits beyond the fused head: QG_ERR_UNSUPPORTED, as for the _sample call.  Stream-ordered on `stream`, one launch, no
+ * synchronisation, capturable into a hipGraph. */
+int qg_policy_head_logp(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_dev, uint32_t num_actions,
+                        float *logp_rows_dev, uint64_t ld_logp, void *actions_dev, int action_dtype, float *best_logp_dev,
+                        float *entropy_dev, float *values_dev, void *stream);
+int qg_policy_mid_head_logp(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_mid_dev, uint32_t mid_features,
+                            const void *packed_head_dev, uint32_t num_actions, float *logp_rows_dev, uint64_t ld_logp, void *actions_dev,
+                            int action_dtype, float *best_logp_dev, float *entropy_dev, float *values_dev, void *stream);
+/* qg_policy_mid_head_sample followed, in the same launch, by Env::step of handle `v` with the action it drew (the lane that holds an env's draw
  * gathers / scatters that env's rows like qg_vec_step does: same results, one launch less per collection step), and by the compaction of
  * the envs whose episode ended with this step: the next qg_vec_reset_done finds its list ready and launches only the reset itself.
  * batch, num_actions, the device clock and the env outputs are the handle's; rewards_dev / dones_dev: per-step outputs as in

@@ -95,7 +95,7 @@ EXPORTED_SYMBOLS = [
     "qg_vec_twists", "qg_twist_expand_packed", "qg_vec_observe_twisted", "qg_untwist_actions",
     "qg_vec_embed_packed_bytes", "qg_vec_pack_embedding", "qg_vec_embed", "qg_vec_embed_observe",
     "qg_policy_embed_words_packed_bytes", "qg_policy_pack_embed_words", "qg_policy_embed_words",
-    "qg_policy_head_packed_bytes", "qg_policy_pack_head", "qg_policy_head_sample",
+    "qg_policy_head_packed_bytes", "qg_policy_pack_head", "qg_policy_head_sample", "qg_policy_head_logp", "qg_policy_mid_head_logp",
     "qg_policy_mid_packed_bytes", "qg_policy_pack_mid", "qg_policy_mid_head_sample", "qg_vec_mid_head_sample_step", "qg_vec_mid_head_sample_step_reset",
     "qg_vec_learner_shard_layout", "qg_vec_pack_learner_shard", "qg_comm_unique_id", "qg_comm_init", "qg_comm_init_local", "qg_comm_destroy",
     "qg_comm_rank", "qg_comm_world", "qg_vec_gather_learner_shard", "qg_comm_gather_submit", "qg_comm_gather_flush", "qg_comm_gather_latest",
@@ -210,6 +210,8 @@ def load():
     L.qg_vec_mid_head_sample_step.argtypes = [vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, u64, u64, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.qg_vec_mid_head_sample_step_reset.argtypes = [vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, u64, u64, vp, C.c_int, vp, vp, vp, vp, vp, u64, vp]
     L.qg_policy_head_sample.argtypes = [vp, u64, u64, C.c_uint32, vp, C.c_uint32, u64, u64, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.qg_policy_head_logp.argtypes = [vp, u64, u64, C.c_uint32, vp, C.c_uint32, vp, u64, vp, C.c_int, vp, vp, vp, vp]
+    L.qg_policy_mid_head_logp.argtypes = [vp, u64, u64, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, u64, vp, C.c_int, vp, vp, vp, vp]
     L.qg_vec_learner_shard_layout.argtypes = [vp, C.POINTER(QGShardLayout)]
     L.qg_vec_pack_learner_shard.argtypes = [vp, vp, vp]
     L.qg_comm_unique_id.argtypes = [vp]

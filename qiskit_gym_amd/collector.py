@@ -364,6 +364,63 @@ def head_sample(h: torch.Tensor, packed: torch.Tensor, num_actions: int, seed: i
     return actions, logp, entropy, values
 
 
+def _logp_outputs(name: str, B: int, A: int, dev, want_rows: bool, logp_rows, actions, best_logp, entropy, values):
+    """Outputs of the two `_logp` wrappers: allocated where None (rows with a stride rounded up to 4 floats: 16-byte stores), checked otherwise."""
+    if want_rows and logp_rows is None:
+        logp_rows = torch.empty((B, (A + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :A]
+    if not want_rows:
+        logp_rows = None
+    elif (logp_rows.dtype != torch.float32 or logp_rows.dim() != 2 or logp_rows.shape[0] != B or logp_rows.shape[1] < A or logp_rows.device != dev
+          or (logp_rows.stride(1) != 1 and logp_rows.shape[1] > 1) or (B > 1 and logp_rows.stride(0) < A)):
+        raise ValueError(f"{name}: logp_rows must be f32 [B, >= num_actions] with unit column stride on the device of h")
+    actions = torch.empty(B, dtype=torch.int64, device=dev) if actions is None else actions
+    best_logp = torch.empty(B, dtype=torch.float32, device=dev) if best_logp is None else best_logp
+    entropy = torch.empty(B, dtype=torch.float32, device=dev) if entropy is None else entropy
+    values = torch.empty(B, dtype=torch.float32, device=dev) if values is None else values
+    if actions.dtype not in (torch.int32, torch.int64) or actions.numel() != B or not actions.is_contiguous() or actions.device != dev:
+        raise ValueError(f"{name}: actions must be a contiguous int32 / int64 [B] tensor on the device of h")
+    for nm, t in (("best_logp", best_logp), ("entropy", entropy), ("values", values)):
+        if t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name}: {nm} must be a contiguous f32 [B] tensor on the device of h")
+    return logp_rows, actions, best_logp, entropy, values
+
+
+def mid_head_logp(h: torch.Tensor, packed_mid: torch.Tensor, mid_features: int, packed_head: torch.Tensor, num_actions: int, want_rows: bool = True,
+                  logp_rows: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None, best_logp: Optional[torch.Tensor] = None,
+                  entropy: Optional[torch.Tensor] = None, values: Optional[torch.Tensor] = None):
+    """`mid_head_sample` without the draw (`qg_policy_mid_head_logp`): relu(h W2^T + b2) -> last layer -> the whole row of log-probabilities
+    and the arg-max (equal logits: the lowest action), in one kernel, from the same operands.  Returns (logp_rows f32 [B, num_actions] --
+    -inf where an action is masked, ready for `beam_select`; None with want_rows=False, which writes no row: the greedy step --, actions,
+    best_logp = logp_rows[e, actions[e]], entropy, values).  Preallocated outputs may be passed; `logp_rows` may be any f32 [B, >= num_actions]
+    view with unit column stride (rows of 16-byte aligned base and stride are written 16 bytes at a time)."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+        raise ValueError("h must be bf16 [B, in_features] with unit column stride")
+    B, A = h.shape[0], int(num_actions)
+    logp_rows, actions, best_logp, entropy, values = _logp_outputs("mid_head_logp", B, A, h.device, want_rows, logp_rows, actions, best_logp, entropy, values)
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_policy_mid_head_logp(h.data_ptr(), h.stride(0), B, h.shape[1], packed_mid.data_ptr(), int(mid_features), packed_head.data_ptr(), A,
+                                                   logp_rows.data_ptr() if logp_rows is not None else None,
+                                                   (logp_rows.stride(0) if B > 1 else logp_rows.shape[1]) if logp_rows is not None else A,
+                                                   actions.data_ptr(), act_dt, best_logp.data_ptr(), entropy.data_ptr(), values.data_ptr(), _stream_ptr()))
+    return (logp_rows[:, :A] if logp_rows is not None else None), actions, best_logp, entropy, values
+
+
+def head_logp(h: torch.Tensor, packed: torch.Tensor, num_actions: int, want_rows: bool = True, logp_rows: Optional[torch.Tensor] = None,
+              actions: Optional[torch.Tensor] = None, best_logp: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
+              values: Optional[torch.Tensor] = None):
+    """`head_sample` without the draw (`qg_policy_head_logp`): last layer -> log-prob rows and arg-max; arguments and results as `mid_head_logp`."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+        raise ValueError("h must be bf16 [B, in_features] with unit column stride")
+    B, A = h.shape[0], int(num_actions)
+    logp_rows, actions, best_logp, entropy, values = _logp_outputs("head_logp", B, A, h.device, want_rows, logp_rows, actions, best_logp, entropy, values)
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_policy_head_logp(h.data_ptr(), h.stride(0), B, h.shape[1], packed.data_ptr(), A,
+                                               logp_rows.data_ptr() if logp_rows is not None else None,
+                                               (logp_rows.stride(0) if B > 1 else logp_rows.shape[1]) if logp_rows is not None else A,
+                                               actions.data_ptr(), act_dt, best_logp.data_ptr(), entropy.data_ptr(), values.data_ptr(), _stream_ptr()))
+    return (logp_rows[:, :A] if logp_rows is not None else None), actions, best_logp, entropy, values
+
+
 class BasicPolicy(nn.Module):
     def __init__(self, obs_size: int, num_actions: int, embedding_size: int = 512, common: int = 256):
         super().__init__()

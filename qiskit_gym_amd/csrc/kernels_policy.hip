@@ -477,10 +477,20 @@ struct HeadArgs {
     const uint4 *h;        // [B][ld_h] bf16 activations
     const uint4 *wp;       // packed head
     void *actions;
-    float *logp, *entropy, *values;
-    const uint64_t *clock;
+    float *logp, *entropy, *values;   // LOGP kernels: logp = the arg-max's log-prob; `actions` may be null there
+    // The LOGP kernels (head_logp below) draw nothing: their two extra operands take the place of the draw's clock and seed, so the
+    // sampling kernels' argument layout is what it was.
+    union {
+        const uint64_t *clock;
+        float *rows;       // LOGP: [B][ld_rows] f32 log-probabilities, or null
+    };
     uint64_t ld_h;         // elements per row of h
-    uint64_t B, seed, counter;
+    uint64_t B;
+    union {
+        uint64_t seed;
+        uint64_t ld_rows;  // LOGP: elements per row of `rows`
+    };
+    uint64_t counter;
     uint64_t env_base;     // global index of env 0 in the draw (the stepped handle's qg_vec_set_env_base; 0 without a handle)
     uint32_t K, A;
     int32_t act64;
@@ -585,7 +595,123 @@ __device__ __forceinline__ int64_t head_draw(f32x16 (&acc)[TILES], const HeadArg
     return act;
 }
 
+// ---- the deterministic epilogue: the whole row of log-probabilities and the arg-max instead of one draw (qg_policy_head_logp) ----
+// Softmax terms as in head_draw / draw_logit -- the same expressions in the same order, so ssum, wsum and with them log-sum, entropy and
+// every log-prob are the sampling kernels' bits -- and the largest logit in place of the smallest race key: ascending action order within
+// the lane, so ties keep the lower index.
+struct BestLane {
+    float best_l = -__builtin_huge_valf(), ssum = 0.0f, wsum = 0.0f;
+    uint32_t best_a = 0xFFFFFFFFu;
+};
+__device__ __forceinline__ void best_logit(BestLane &r, float logit, float m, uint32_t act) {
+    const float d = logit - m;
+    const float ex = __builtin_amdgcn_exp2f(d * 1.44269504088896340736f);
+    r.ssum += ex;
+    r.wsum = __builtin_fmaf(ex, d, r.wsum);
+    const bool take = logit > r.best_l;  // a NaN logit never wins
+    r.best_l = take ? logit : r.best_l;
+    r.best_a = take ? act : r.best_a;
+}
+// the race's tie rule keyed on the logit: the larger one, equal ones by the lower action index
+__device__ __forceinline__ void best_merge(float &best_l, uint32_t &best_a, float ol, uint32_t oa) {
+    const bool take = oa != 0xFFFFFFFFu && (best_a == 0xFFFFFFFFu || ol > best_l || (ol == best_l && oa < best_a));
+    best_l = take ? ol : best_l;
+    best_a = take ? oa : best_a;
+}
+
+// One run of four consecutive actions act0 .. act0 + 3 (act0 % 4 == 0) of this lane's env: lp = (logit - m) - log_s, -inf for a masked
+// action (logit below HEAD_MASKED: a bias at or below the padding value); an action that is merely far below the maximum keeps its finite
+// value.  The caller passes log_s = +inf for a row without a live action: every entry -inf.  WIDE: one 16-byte store (base and stride of
+// the rows are multiples of 16 bytes); PARTIAL: the run may reach past column A - 1, which is not written -- only the last 32-action tile
+// has such runs (tiles = ceil((A + 1) / 32)), so every other tile stores without a per-lane condition.
+// "logit < HEAD_MASKED ? -inf : (logit - m) - log_s" without a compare: min(logit - HEAD_MASKED, 0) is +0 for a live logit -- and
+// fma(+0, big, x) is x, bit for bit -- and at most -9e21 (one ulp at 1e29) for a masked one, which times `big` is -inf.  Spelled as a select,
+// the 16 x TILES lane masks are all formed ahead of the stores and held in SGPRs: 32 spilled SGPRs per action tile, scratch from 5 tiles on.
+__device__ __forceinline__ float logp_entry(float logit, float m, float log_s) {
+    return __builtin_fmaf(fminf(logit - HEAD_MASKED, 0.0f), 3.0e38f, (logit - m) - log_s);
+}
+template <bool WIDE, bool PARTIAL>
+__device__ __forceinline__ void logp_store4(float *row, uint32_t act0, uint32_t A, float l0, float l1, float l2, float l3, float m, float log_s) {
+    const float lp0 = logp_entry(l0, m, log_s), lp1 = logp_entry(l1, m, log_s), lp2 = logp_entry(l2, m, log_s), lp3 = logp_entry(l3, m, log_s);
+    if (!PARTIAL || act0 + 4u <= A) {
+        if (WIDE) {
+            *reinterpret_cast<float4 *>(row + act0) = make_float4(lp0, lp1, lp2, lp3);
+        } else {
+            row[act0] = lp0;
+            row[act0 + 1u] = lp1;
+            row[act0 + 2u] = lp2;
+            row[act0 + 3u] = lp3;
+        }
+    } else {
+        if (act0 < A) row[act0] = lp0;
+        if (act0 + 1u < A) row[act0 + 1u] = lp1;
+        if (act0 + 2u < A) row[act0 + 2u] = lp2;
+    }
+}
+// the runs of one accumulator tile: actions tile0 + 8 j + 4 h + (0 .. 3), j < 4
+template <bool WIDE, bool PARTIAL>
+__device__ __forceinline__ void logp_store_tile(float *row, const f32x16 &acc, uint32_t tile0, uint32_t h, uint32_t A, float m, float log_s) {
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j)
+        logp_store4<WIDE, PARTIAL>(row, tile0 + 8u * j + 4u * h, A, acc[4u * j], acc[4u * j + 1u], acc[4u * j + 2u], acc[4u * j + 3u], m, log_s);
+}
+__device__ __forceinline__ bool logp_rows_wide(const HeadArgs &a) { return ((reinterpret_cast<uintptr_t>(a.rows) | (a.ld_rows * sizeof(float))) & 15u) == 0; }
+
+// The per-env outputs of the deterministic epilogue (one lane per env calls it)
+__device__ __forceinline__ void logp_finish(const HeadArgs &a, uint64_t env, int64_t act, bool none, float best_l, float m, float log_s, float ssum, float wsum, float value) {
+    if (a.actions) {
+        if (a.act64) reinterpret_cast<int64_t *>(a.actions)[env] = act;
+        else reinterpret_cast<int32_t *>(a.actions)[env] = (int32_t)act;
+    }
+    if (a.logp) a.logp[env] = none ? 0.0f : (best_l - m) - log_s;
+    if (a.entropy) a.entropy[env] = none ? 0.0f : log_s - wsum / ssum;
+    if (a.values) a.values[env] = value;
+}
+
+// head_draw's counterpart: same accumulator tiles in, no draw.  Returns the arg-max (0 for a row without a live action).
 template <uint32_t TILES>
+__device__ __forceinline__ int64_t head_logp(f32x16 (&acc)[TILES], const HeadArgs &a, uint64_t env, bool live, uint32_t h) {
+    const float value = acc[TILES - 1][15];  // meaningful on the h = 1 lanes
+    if (h == 1) acc[TILES - 1][15] = HEAD_PAD_BIAS;
+    float m = -__builtin_huge_valf();
+#pragma unroll
+    for (uint32_t t = 0; t < TILES; ++t)
+#pragma unroll
+        for (uint32_t q = 0; q < 16; ++q) m = fmaxf(m, acc[t][q]);
+    m = fmaxf(m, head_xhalf(m));
+    BestLane r;
+#pragma unroll
+    for (uint32_t t = 0; t < TILES; ++t)
+#pragma unroll
+        for (uint32_t q = 0; q < 16; ++q) best_logit(r, acc[t][q], m, 32u * t + (q & 3u) + 8u * (q >> 2) + 4u * h);
+    // the other lane half holds the other actions of this env
+    best_merge(r.best_l, r.best_a, head_xhalf(r.best_l), __shfl_xor(r.best_a, 32, 64));
+    r.ssum += head_xhalf(r.ssum);
+    r.wsum += head_xhalf(r.wsum);
+    const float v_other = head_xhalf(value);
+    // no live action: every logit is a masked one (padding rows included); NaN / +inf rows (outside the contract) still end in [0, A)
+    const bool none = !(m >= HEAD_MASKED) || r.best_a >= a.A;
+    const int64_t act = none ? 0 : (int64_t)r.best_a;  // the env's action on both lane halves
+    const float log_s = logf(r.ssum);
+    if (live && a.rows) {
+        float *row = a.rows + env * a.ld_rows;
+        const float ls = none ? __builtin_huge_valf() : log_s;
+        if (logp_rows_wide(a)) {  // wave-uniform
+#pragma unroll
+            for (uint32_t t = 0; t + 1u < TILES; ++t) logp_store_tile<true, false>(row, acc[t], 32u * t, h, a.A, m, ls);
+            logp_store_tile<true, true>(row, acc[TILES - 1], 32u * (TILES - 1u), h, a.A, m, ls);
+        } else {
+#pragma unroll
+            for (uint32_t t = 0; t + 1u < TILES; ++t) logp_store_tile<false, false>(row, acc[t], 32u * t, h, a.A, m, ls);
+            logp_store_tile<false, true>(row, acc[TILES - 1], 32u * (TILES - 1u), h, a.A, m, ls);
+        }
+    }
+    if (live && h == 0) logp_finish(a, env, act, none, r.best_l, m, log_s, r.ssum, r.wsum, v_other);
+    return act;
+}
+
+// LOGP: the deterministic epilogue (head_logp) in place of the draw -- a template parameter, so the sampling instantiations hold no trace of it
+template <uint32_t TILES, bool LOGP = false>
 __global__ __launch_bounds__(64 * HEAD_WAVES, 1) void head_sample_kernel(HeadArgs a) {
     extern __shared__ uint4 head_lds[];  // packed head: [(K/16 + 1)][TILES][64]
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -636,7 +762,8 @@ __global__ __launch_bounds__(64 * HEAD_WAVES, 1) void head_sample_kernel(HeadArg
             for (uint32_t t = 0; t < TILES; ++t)
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[t * 64u]), bf, acc[t], 0, 0, 0);
         }
-        head_draw<TILES>(acc, a, env, live, h);
+        if constexpr (LOGP) head_logp<TILES>(acc, a, env, live, h);
+        else head_draw<TILES>(acc, a, env, live, h);
     }
 }
 
@@ -680,7 +807,7 @@ struct MidHeadArgs {
 // workgroup per CU whose waves carry two tiles each -- every weight fragment read from LDS feeds two MFMAs, and a tile pays half the chunk
 // barriers, staging instructions and LDS reads; the accumulators of both tiles (256 + 136 + 32 TILES registers at the widest point) need
 // the whole register file of a SIMD, i.e. one wave per SIMD.
-template <uint32_t TILES, uint32_t TPW>
+template <uint32_t TILES, uint32_t TPW, bool LOGP = false>
 __global__ __launch_bounds__(64 * MH_WAVES, TPW == 1 ? 2 : 1) void mid_head_sample_kernel(MidHeadArgs ma) {
     __shared__ uint4 cbuf[2 * MH_CHUNK_VEC];
     const HeadArgs &a = ma.head;
@@ -806,6 +933,10 @@ __global__ __launch_bounds__(64 * MH_WAVES, TPW == 1 ? 2 : 1) void mid_head_samp
         }
 #pragma unroll
         for (uint32_t p = 0; p < TPW; ++p) {
+            if constexpr (LOGP) {  // qg_policy_mid_head_logp: no draw, no step
+                head_logp<TILES>(acc[p], a, env[p], live[p], h);
+                continue;
+            }
             const int64_t act = head_draw<TILES>(acc[p], a, env[p], live[p], h);
             if (ma.step.state) {  // wave-uniform
                 bool fin = false;
@@ -846,7 +977,59 @@ __device__ __forceinline__ void mhs_lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// mid_head_small_kernel's deterministic tail (head_logp for logits spread over four waves): `m` is the env's maximum over all waves.  The
+// partial sums and the per-wave best logits cross through `part` as the draw's do; EVERY wave then adds the four partial sums in wave
+// order -- the bits wave 0 gets, the bits mid_head_small_kernel's draw gets -- because each needs log_s for its quarter of the row.
 template <uint32_t TILES>
+__device__ __forceinline__ void mhs_logp_tail(const HeadArgs &a, f32x16 (&acc)[2], float (&part)[MHS_WAVES][6][32], float m, float value, bool any, bool two,
+                                              uint32_t wave, uint32_t c, uint32_t h, uint64_t env, bool live) {
+    constexpr uint32_t VW = (TILES - 1u) % MHS_WAVES;
+    BestLane r;
+    if (any) {
+#pragma unroll
+        for (uint32_t q = 0; q < 16; ++q) best_logit(r, acc[0][q], m, 32u * wave + (q & 3u) + 8u * (q >> 2) + 4u * h);
+        if (two) {
+#pragma unroll
+            for (uint32_t q = 0; q < 16; ++q) best_logit(r, acc[1][q], m, 32u * (wave + MHS_WAVES) + (q & 3u) + 8u * (q >> 2) + 4u * h);
+        }
+    }
+    best_merge(r.best_l, r.best_a, head_xhalf(r.best_l), __shfl_xor(r.best_a, 32, 64));
+    r.ssum += head_xhalf(r.ssum);
+    r.wsum += head_xhalf(r.wsum);
+    const float v_other = head_xhalf(value);
+    if (h == 0) {
+        part[wave][0][c] = r.ssum;
+        part[wave][1][c] = r.wsum;
+        part[wave][2][c] = r.best_l;
+        part[wave][4][c] = __uint_as_float(r.best_a);
+        if (wave == VW) part[0][5][c] = v_other;
+    }
+    __syncthreads();
+    float ssum = 0.0f, wsum = 0.0f, best_l = -__builtin_huge_valf();
+    uint32_t best_a = 0xFFFFFFFFu;
+#pragma unroll
+    for (uint32_t w = 0; w < MHS_WAVES; ++w) {  // ascending action tiles within a wave, ties across waves by the lower index
+        ssum += part[w][0][c];
+        wsum += part[w][1][c];
+        best_merge(best_l, best_a, part[w][2][c], __float_as_uint(part[w][4][c]));
+    }
+    const bool none = !(m >= HEAD_MASKED) || best_a >= a.A;  // head_logp
+    const float log_s = logf(ssum);
+    if (live && a.rows && any) {  // this wave's action tiles: wave (the last one where wave == TILES - 1) and, if `two`, wave + 4
+        float *row = a.rows + env * a.ld_rows;
+        const float ls = none ? __builtin_huge_valf() : log_s;
+        if (logp_rows_wide(a)) {  // wave-uniform
+            logp_store_tile<true, true>(row, acc[0], 32u * wave, h, a.A, m, ls);
+            if (two) logp_store_tile<true, true>(row, acc[1], 32u * (wave + MHS_WAVES), h, a.A, m, ls);
+        } else {
+            logp_store_tile<false, true>(row, acc[0], 32u * wave, h, a.A, m, ls);
+            if (two) logp_store_tile<false, true>(row, acc[1], 32u * (wave + MHS_WAVES), h, a.A, m, ls);
+        }
+    }
+    if (wave == 0 && live && h == 0) logp_finish(a, env, none ? 0 : (int64_t)best_a, none, best_l, m, log_s, ssum, wsum, part[0][5][c]);
+}
+
+template <uint32_t TILES, bool LOGP = false>
 __global__ __launch_bounds__(64 * MHS_WAVES, 1) void mid_head_small_kernel(MidHeadArgs ma) {
     static_assert(MID_FT == 2 * MHS_WAVES && TILES <= 2 * MHS_WAVES, "two feature tiles and <= two action tiles per wave");
     __shared__ uint4 bbuf[MHS_KMAX * 64u];          // the tile's activations as B fragments, k-step major: loaded once, read by all four waves
@@ -980,6 +1163,10 @@ __global__ __launch_bounds__(64 * MHS_WAVES, 1) void mid_head_small_kernel(MidHe
     if (h == 0) xmax[wave][c] = m;
     __syncthreads();
     m = fmaxf(fmaxf(xmax[0][c], xmax[1][c]), fmaxf(xmax[2][c], xmax[3][c]));
+    if constexpr (LOGP) {  // qg_policy_mid_head_logp: no draw, no step
+        mhs_logp_tail<TILES>(a, acc, part, m, value, any, two, wave, c, h, env, live);
+        return;
+    }
     const uint64_t base = rng_draw(a.seed, a.env_base + env, a.counter + clock_of(a.clock));
     const uint32_t blo = (uint32_t)base, bhi = (uint32_t)(base >> 32);
     DrawLane r;
@@ -1656,10 +1843,26 @@ int qg_policy_pack_mid(const void *weight_dev, const void *bias_dev, int dtype, 
     return pack_rows_impl(weight_dev, bias_dev, dtype, ld, in_features, mid_features, -1, MID_FT, 0u, in_features / 16u + MID_CHUNK, packed_dev, (hipStream_t)stream);
 }
 
-int qg_policy_head_sample(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_dev, uint32_t num_actions,
-                          uint64_t seed, uint64_t counter, const uint64_t *clock_dev, void *actions_dev, int action_dtype, float *logp_dev,
-                          float *entropy_dev, float *values_dev, void *stream) {
-    if (!h_dev || !packed_dev || !actions_dev) return set_error(QG_ERR_INVALID, "null argument");
+// The deterministic entry points' row output (qg_policy_head_logp, qg_policy_mid_head_logp); a null LogpRows * means the draw
+struct LogpRows {
+    float *rows;
+    uint64_t ld;
+};
+
+// what the two _logp entry points check beyond their _sample twins
+static int logp_check(const LogpRows &lr, uint32_t num_actions, const void *actions_dev, const float *best_logp_dev, const float *entropy_dev,
+                      const float *values_dev) {
+    if (!lr.rows && !actions_dev && !best_logp_dev && !entropy_dev && !values_dev) return set_error(QG_ERR_INVALID, "every output is null");
+    if (lr.rows && lr.ld < num_actions) return set_error(QG_ERR_INVALID, "log-prob rows are shorter than num_actions");
+    return QG_OK;
+}
+
+static int head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_dev, uint32_t num_actions,
+                     uint64_t seed, uint64_t counter, const uint64_t *clock_dev, void *actions_dev, int action_dtype, float *logp_dev,
+                     float *entropy_dev, float *values_dev, const LogpRows *lr, void *stream) {
+    if (!h_dev || !packed_dev || (!lr && !actions_dev)) return set_error(QG_ERR_INVALID, "null argument");
+    if (lr)
+        if (const int rc = logp_check(*lr, num_actions, actions_dev, logp_dev, entropy_dev, values_dev)) return rc;
     const size_t lds = qg_policy_head_packed_bytes(num_actions, in_features);
     if (lds == 0) return set_error(QG_ERR_UNSUPPORTED, "fused head: num_actions <= 222, in_features a multiple of 64 and <= 512, packed head <= 144 KiB");
     if (ld_h < in_features || (ld_h & 7u) || (reinterpret_cast<uintptr_t>(h_dev) & 15u))
@@ -1682,6 +1885,11 @@ int qg_policy_head_sample(const void *h_dev, uint64_t ld_h, uint64_t batch, uint
     a.A = num_actions;
     a.act64 = action_dtype == QG_ACT_I64;
     a.env_base = 0;
+    if (lr) {  // no draw: the rows take the place of clock and seed (HeadArgs)
+        a.rows = lr->rows;
+        a.ld_rows = lr->ld;
+        a.counter = 0;
+    }
     const uint32_t tiles = (num_actions + 1u + 31u) / 32u;
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
@@ -1689,18 +1897,39 @@ int qg_policy_head_sample(const void *h_dev, uint64_t ld_h, uint64_t batch, uint
     const uint64_t env_tiles = (batch + 31u) / 32u, want = (env_tiles + HEAD_WAVES - 1) / HEAD_WAVES;
     const dim3 grid((unsigned)(want < (uint64_t)cus ? want : (uint64_t)cus)), block(64 * HEAD_WAVES);
     hipStream_t s = (hipStream_t)stream;
-#define QG_HEAD_CASE(TT)                                                                                                      \
-    case TT:                                                                                                                  \
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(head_sample_kernel<TT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(head_sample_kernel<TT>, grid, block, lds, s, a);                                                   \
+#define QG_HEAD_LAUNCH(KERNEL)                                                                                                \
+    do {                                                                                                                      \
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        hipLaunchKernelGGL(KERNEL, grid, block, lds, s, a);                                                                   \
+    } while (0)
+#define QG_HEAD_CASE(TT)                                          \
+    case TT:                                                      \
+        if (lr) QG_HEAD_LAUNCH((head_sample_kernel<TT, true>));   \
+        else QG_HEAD_LAUNCH((head_sample_kernel<TT>));            \
         break;
     switch (tiles) {
         QG_HEAD_CASE(1) QG_HEAD_CASE(2) QG_HEAD_CASE(3) QG_HEAD_CASE(4) QG_HEAD_CASE(5) QG_HEAD_CASE(6) QG_HEAD_CASE(7)
     default: return set_error(QG_ERR_UNSUPPORTED, "too many actions for the fused head");
     }
 #undef QG_HEAD_CASE
+#undef QG_HEAD_LAUNCH
     HIP_TRY(hipGetLastError());
     return QG_OK;
+}
+
+int qg_policy_head_sample(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_dev, uint32_t num_actions,
+                          uint64_t seed, uint64_t counter, const uint64_t *clock_dev, void *actions_dev, int action_dtype, float *logp_dev,
+                          float *entropy_dev, float *values_dev, void *stream) {
+    return head_impl(h_dev, ld_h, batch, in_features, packed_dev, num_actions, seed, counter, clock_dev, actions_dev, action_dtype, logp_dev, entropy_dev,
+                     values_dev, nullptr, stream);
+}
+
+int qg_policy_head_logp(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_dev, uint32_t num_actions,
+                        float *logp_rows_dev, uint64_t ld_logp, void *actions_dev, int action_dtype, float *best_logp_dev, float *entropy_dev,
+                        float *values_dev, void *stream) {
+    const LogpRows lr{logp_rows_dev, ld_logp};
+    return head_impl(h_dev, ld_h, batch, in_features, packed_dev, num_actions, 0, 0, nullptr, actions_dev, action_dtype, best_logp_dev, entropy_dev, values_dev,
+                     &lr, stream);
 }
 
 // up to one workgroup per CU of mid_head_small_kernel (a tile of 32 envs each)
@@ -1727,8 +1956,10 @@ static bool mid_head_two_tiles(uint64_t batch, int cus) {
 static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_mid_dev, uint32_t mid_features,
                          const void *packed_head_dev, uint32_t num_actions, uint64_t seed, uint64_t counter, const uint64_t *clock_dev, void *actions_dev,
                          int action_dtype, float *logp_dev, float *entropy_dev, float *values_dev, qg_vec *step_of, float *step_rewards,
-                         uint8_t *step_dones, const uint64_t *reset_seed, uint64_t env_base, void *stream) {
-    if (!h_dev || !packed_mid_dev || !packed_head_dev || !actions_dev) return set_error(QG_ERR_INVALID, "null argument");
+                         uint8_t *step_dones, const uint64_t *reset_seed, uint64_t env_base, void *stream, const LogpRows *lr = nullptr) {
+    if (!h_dev || !packed_mid_dev || !packed_head_dev || (!lr && !actions_dev)) return set_error(QG_ERR_INVALID, "null argument");
+    if (lr)
+        if (const int rc = logp_check(*lr, num_actions, actions_dev, logp_dev, entropy_dev, values_dev)) return rc;
     if (qg_policy_head_packed_bytes(num_actions, mid_features) == 0 || qg_policy_mid_packed_bytes(in_features, mid_features) == 0)
         return set_error(QG_ERR_UNSUPPORTED, "fused middle layer + head: 256 middle features, in_features a multiple of 32, num_actions <= 222");
     if (ld_h < in_features || (ld_h & 7u) || (reinterpret_cast<uintptr_t>(h_dev) & 15u))
@@ -1752,6 +1983,11 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
     a.A = num_actions;
     a.act64 = action_dtype == QG_ACT_I64;
     a.env_base = env_base;  // a shard draws what its envs would draw in the unsharded batch (qg_vec_set_env_base of the stepped handle)
+    if (lr) {  // no draw: the rows take the place of clock and seed (HeadArgs)
+        a.rows = lr->rows;
+        a.ld_rows = lr->ld;
+        a.counter = 0;
+    }
     m.w2p = reinterpret_cast<const uint4 *>(packed_mid_dev);
     m.K1 = in_features;
     if (step_of) {  // Env::step with the drawn action in the same launch
@@ -1786,8 +2022,11 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
         if (int rc = zero_list_length(step_of, step_of->done_list, step_of->dl.before_append(), s)) return rc;
     if (small) {
         const dim3 grid((unsigned)env_tiles), block(64 * MHS_WAVES);
-#define QG_MHS_CASE(TT)                                                        \
-    case TT: hipLaunchKernelGGL(mid_head_small_kernel<TT>, grid, block, 0, s, m); break;
+#define QG_MHS_CASE(TT)                                                                       \
+    case TT:                                                                                  \
+        if (lr) hipLaunchKernelGGL((mid_head_small_kernel<TT, true>), grid, block, 0, s, m);  \
+        else hipLaunchKernelGGL(mid_head_small_kernel<TT>, grid, block, 0, s, m);             \
+        break;
         switch (tiles) {
             QG_MHS_CASE(1) QG_MHS_CASE(2) QG_MHS_CASE(3) QG_MHS_CASE(4) QG_MHS_CASE(5) QG_MHS_CASE(6) QG_MHS_CASE(7)
         default: return set_error(QG_ERR_UNSUPPORTED, "too many actions for the fused head");
@@ -1799,7 +2038,7 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
     }
     // two tiles per wave (one workgroup of 256 envs per CU) once the batch gives every CU such a workgroup; below that, one tile per wave, two
     // workgroups per CU (32 KiB of LDS and 256 registers x 4 waves each)
-    const bool two = mid_head_two_tiles(batch, cus);
+    const bool two = !lr && mid_head_two_tiles(batch, cus);
     const uint64_t per_wg = two ? 2ull * MH_WAVES : (uint64_t)MH_WAVES, want_wg = (env_tiles + per_wg - 1) / per_wg;
     const uint64_t resident = two ? (uint64_t)cus : 2ull * (uint64_t)cus;
     const dim3 grid((unsigned)(want_wg < resident ? want_wg : resident)), block(64 * MH_WAVES);
@@ -1811,7 +2050,10 @@ static int mid_head_impl(const void *h_dev, uint64_t ld_h, uint64_t batch, uint3
         break;
 #else
 #define QG_MH_CASE(TT)                                                                                   \
-    case TT: hipLaunchKernelGGL((mid_head_sample_kernel<TT, 1>), grid, block, 0, s, m); break;
+    case TT:                                                                                             \
+        if (lr) hipLaunchKernelGGL((mid_head_sample_kernel<TT, 1, true>), grid, block, 0, s, m);         \
+        else hipLaunchKernelGGL((mid_head_sample_kernel<TT, 1>), grid, block, 0, s, m);                  \
+        break;
 #endif
     switch (tiles) {
         QG_MH_CASE(1) QG_MH_CASE(2) QG_MH_CASE(3) QG_MH_CASE(4) QG_MH_CASE(5) QG_MH_CASE(6) QG_MH_CASE(7)
@@ -1828,6 +2070,14 @@ int qg_policy_mid_head_sample(const void *h_dev, uint64_t ld_h, uint64_t batch, 
                               int action_dtype, float *logp_dev, float *entropy_dev, float *values_dev, void *stream) {
     return mid_head_impl(h_dev, ld_h, batch, in_features, packed_mid_dev, mid_features, packed_head_dev, num_actions, seed, counter, clock_dev, actions_dev,
                          action_dtype, logp_dev, entropy_dev, values_dev, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int qg_policy_mid_head_logp(const void *h_dev, uint64_t ld_h, uint64_t batch, uint32_t in_features, const void *packed_mid_dev, uint32_t mid_features,
+                            const void *packed_head_dev, uint32_t num_actions, float *logp_rows_dev, uint64_t ld_logp, void *actions_dev,
+                            int action_dtype, float *best_logp_dev, float *entropy_dev, float *values_dev, void *stream) {
+    const LogpRows lr{logp_rows_dev, ld_logp};
+    return mid_head_impl(h_dev, ld_h, batch, in_features, packed_mid_dev, mid_features, packed_head_dev, num_actions, 0, 0, nullptr, actions_dev, action_dtype,
+                         best_logp_dev, entropy_dev, values_dev, nullptr, nullptr, nullptr, nullptr, 0, stream, &lr);
 }
 
 static int mid_head_step_impl(qg_vec *v, const void *h_dev, uint64_t ld_h, uint32_t in_features, const void *packed_mid_dev, uint32_t mid_features,

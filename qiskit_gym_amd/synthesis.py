@@ -17,6 +17,10 @@ recovered by replaying the winners on a `track_solution` batch.
 `solve(..., beam_width=W)` searches differently: a deterministic beam search over the policy's log-probabilities, W beams per target, on
 the batched clone (`VecEnv.copy_envs`) and the device-side selection kernel (`collector.beam_select`); see `solve`.
 
+`solve(..., fast=True)` takes the policy off the tensor library: the first layer reads the bit-packed state (`collector.embed` /
+`embed_words`), the rest is one kernel that either draws (`mid_head_sample`: the sampled searches) or, for the greedy and the beam search,
+writes the arg-max and the row of log-probabilities (`mid_head_logp`), which `beam_select` reads as it stands.
+
 `solve(..., twists=V)` gives every target V symmetry views (`VecEnv.observe_twisted` / `untwist_actions`): the policy looks at a target through
 an automorphism of the coupling map and its choice is mapped back, what `RLSynthesis.init_algorithm` hands the reference's policy as
 `obs_perms` / `act_perms` (rl/synthesis.py:97-104) -- here one fixed view per search, so the deterministic searches get V opinions per target.
@@ -29,7 +33,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .collector import BasicPolicy, beam_merge, beam_seen, beam_select, embed, embed_words, mid_head_sample, pack_embed_words, pack_embedding, pack_head, pack_mid, sample_actions
+from .collector import (BasicPolicy, beam_merge, beam_seen, beam_select, embed, embed_words, mid_head_logp, mid_head_sample, pack_embed_words, pack_embedding,
+                        pack_head, pack_mid, sample_actions)
 from .envs.gyms import ROTATION_MARKER
 from .vec import VecEnv
 
@@ -60,19 +65,33 @@ class BatchedSynthesis:
         self._vecs: Dict[tuple, VecEnv] = {}
         self._beam = None  # ((targets, width), (two search batches, the winners)): the beam search's handles
         self._view_list = None  # twists: the twist index behind each view (`_views`)
-        self._packed = None  # (vec, packed first layer, its f32 bias, packed middle layer, packed head): the policy-layer kernels' operands
+        # the policy-layer kernels' operands per search handle, by id(vec): (vec, packed first layer, its f32 bias, packed middle layer, packed
+        # head, words route?) or None where they do not apply.  The first layer is packed through the handle it will read (`pack_embedding`);
+        # bias, middle layer and head are packed once and shared (`_packed_tail`).  All of it is a snapshot of the policy's weights at
+        # `_packed_at` (the parameters' version counters): an in-place update of the policy drops the whole cache, so the kernels never run
+        # one layer of the new weights with another of the old, and follow the policy as the torch forward does.
+        self._packed: Dict[int, Optional[tuple]] = {}
+        self._packed_tail = None
+        self._packed_at = None
         self.last_stats: dict = {}
 
+    _NO_KERNELS = "fast=True needs a BasicPolicy of the default shape and an env whose state or packed observation the first-layer kernels read"
+
     def _kernels(self, vec: VecEnv):
-        """Operands of the two policy-layer kernels (qg_vec_embed, qg_policy_mid_head_sample: bf16 products, f32 accumulation) when the
+        """Operands of the two policy-layer kernels (qg_vec_embed, qg_policy_mid_head_sample / _logp: bf16 products, f32 accumulation) when the
         policy has the default shape and the env a TILE layout or 64-bit observation words; None otherwise (the torch forward is used)."""
-        if self._packed is not None and self._packed[0] is vec:
-            return self._packed
         pol = self._policy
         if not isinstance(pol, BasicPolicy):
             return None
+        at = tuple((id(p), p._version) for p in pol.parameters())
+        if at != self._packed_at:  # the weights were updated in place since the operands were packed
+            self._packed.clear()
+            self._packed_tail, self._packed_at = None, at
+        hit = self._packed.get(id(vec))
+        if hit is not None and hit[0] is vec:
+            return hit
+        packed = None
         try:
-            w, b, A = pol.fused_heads()
             try:
                 first = pack_embedding(vec, pol.embeddings.weight)  # TILE layout: the first layer reads the resident state
                 words = False
@@ -81,17 +100,32 @@ class BatchedSynthesis:
                     raise
                 first = pack_embed_words(pol.embeddings.weight, *vec.obs_shape_)  # 64-bit row words (PauliEnv, wide CliffordEnv): qg_policy_embed_words
                 words = True
-            self._packed = (vec, first, pol.embeddings.bias.detach().float().contiguous(), pack_mid(pol.common.weight, pol.common.bias),
-                            pack_head(w, b, A, A, after_mid=True), words)
+            if self._packed_tail is None:
+                w, b, A = pol.fused_heads()
+                self._packed_tail = (pol.embeddings.bias.detach().float().contiguous(), pack_mid(pol.common.weight, pol.common.bias),
+                                     pack_head(w, b, A, A, after_mid=True))
+            packed = (vec, first, *self._packed_tail, words)
         except (ValueError, _lib.QGymError):
-            self._packed = None
-        return self._packed
+            packed = None
+        if packed is not None:
+            self._packed[id(vec)] = packed
+        return packed
+
+    def _close(self, vec: VecEnv):
+        self._packed.pop(id(vec), None)
+        vec.close()
+
+    def _first_layer(self, vec: VecEnv, kern, h1: torch.Tensor, words_buf: Optional[torch.Tensor]) -> torch.Tensor:
+        """relu(obs W1^T + b1) of the handle's current state into `h1` (bf16), from the resident bits or the packed observation words."""
+        if kern[5]:
+            return embed_words(vec.observe_packed(out=words_buf), vec.obs_shape_[1], kern[1], kern[2], h1.shape[1], relu=True, out=h1)
+        return embed(vec, kern[1], kern[2], h1.shape[1], relu=True, out=h1)
 
     def _vec(self, batch: int, track_solution: bool, perms: bool = False) -> VecEnv:
         key = (batch, track_solution, True) if perms else (batch, track_solution)  # add_perms: twists() only, the env steps alike
         if key not in self._vecs:
             for k in [k for k in self._vecs if k[1] == track_solution]:  # one batch size at a time: the handles own device memory
-                self._vecs.pop(k).close()
+                self._close(self._vecs.pop(k))
             self._vecs[key] = self.env.vec(batch, device=self.device, add_inverts=False, add_perms=perms, track_solution=track_solution)
             self._policy = self._policy.to(device=self._vecs[key].device, dtype=self.dtype)
         return self._vecs[key]
@@ -127,7 +161,7 @@ class BatchedSynthesis:
         if self._beam is None or self._beam[0] != key:
             if self._beam is not None:
                 for v in self._beam[1]:
-                    v.close()
+                    self._close(v)
             mk = lambda batch: self.env.vec(batch, device=self.device, add_inverts=False, add_perms=perms, track_solution=True)  # noqa: E731
             self._beam = (key, (mk(M * W), mk(M * W), mk(M)))
             self._policy = self._policy.to(device=self._beam[1][0].device, dtype=self.dtype)
@@ -143,12 +177,13 @@ class BatchedSynthesis:
             self._view_list = [-1] + [t for t, p in enumerate(obs_perms) if p != list(range(len(p)))]
         return self._view_list[:V]
 
-    def _solve_beam(self, states: Sequence[Sequence[int]], W: int, merge: bool = False, twists: Optional[int] = None) -> List[Optional[List[int]]]:
+    def _solve_beam(self, states: Sequence[Sequence[int]], W: int, merge: bool = False, twists: Optional[int] = None,
+                    fast: bool = False) -> List[Optional[List[int]]]:
         if twists is not None:
             return self._solve_beam_views(states, W, merge, twists)
         M = len(states)
         cur, oth, win = self._beam_vecs(M, W)
-        return self._beam_search(states, 1, None, W, merge, cur, oth, win)
+        return self._beam_search(states, 1, None, W, merge, cur, oth, win, fast)
 
     def _solve_beam_views(self, states, W: int, merge: bool, twists: int) -> List[Optional[List[int]]]:
         """Beam search under V views per target: the groups are the (target, view) pairs, each searched under its own fixed view (and with
@@ -160,11 +195,23 @@ class BatchedSynthesis:
         tw = torch.tensor(views, dtype=torch.int32, device=cur.device).repeat(M).repeat_interleave(W).contiguous()  # env b: group b // W, view (b // W) % V
         return self._beam_search(states, V, tw, W, merge, cur, oth, win)
 
-    def _beam_search(self, states, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv):
-        """`tw` None: the search of `solve(beam_width=W)`.  Else int32 [B]: every env's twist index; there are V consecutive groups per target."""
+    def _beam_search(self, states, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv, fast: bool = False):
+        """`tw` None: the search of `solve(beam_width=W)`.  Else int32 [B]: every env's twist index; there are V consecutive groups per target.
+        `fast`: the log-probabilities come from the policy-layer kernels (`tw` is None then)."""
         targets = len(states)
         M = targets * V  # groups
         B, A, dev = cur.batch, cur.num_actions(), cur.device
+        kern = None
+        if fast:  # the two search handles take turns: each has its own packed first layer (packed through the handle), the rest is shared
+            kern = {id(v): self._kernels(v) for v in (cur, oth)}
+            if any(k is None for k in kern.values()):
+                raise ValueError(self._NO_KERNELS)
+            pol = self._policy
+            h1 = torch.empty((B, pol.embeddings.out_features), dtype=torch.bfloat16, device=dev)
+            rows = torch.empty((B, (A + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :A]  # 16-byte row stride: 16-byte stores
+            top = torch.empty(B, dtype=torch.int32, device=dev)  # the kernel's other outputs: not used by the search
+            scratch = torch.empty((3, B), dtype=torch.float32, device=dev)
+            words_buf = torch.empty((B, cur.packed_words_per_env), dtype=torch.int64, device=dev) if kern[id(cur)][5] else None
         T = int(cur._cfg.max_depth)
         self._load(win, states, V)  # the targets once per group; a group nobody solves keeps its slot, a solved one is overwritten by its winner
         group = torch.arange(M, dtype=torch.int32, device=dev)
@@ -184,8 +231,13 @@ class BatchedSynthesis:
             words = cur.observe_packed()
             live = beam_merge(words, cum, live, W, seen, cap)
         for t in range(T):
-            logits = self._policy(self._observe(cur, tw))[0]
-            logp = torch.log_softmax(logits.float(), dim=1)
+            if kern is not None:  # first layer from the bits, then middle layer + head + log-softmax in one kernel: no logits in memory
+                k = kern[id(cur)]
+                logp = mid_head_logp(self._first_layer(cur, k, h1, words_buf), k[3], pol.common.out_features, k[4], A, logp_rows=rows, actions=top,
+                                     best_logp=scratch[0], entropy=scratch[1], values=scratch[2])[0]
+            else:
+                logits = self._policy(self._observe(cur, tw))[0]
+                logp = torch.log_softmax(logits.float(), dim=1)
             parent, act, cum, live = beam_select(logp, cum, live, W, A)
             if tw is not None:  # chosen on the view: the real action (a child lives in its parent's group, hence under its view)
                 cur.untwist_actions(act, tw, out=act)
@@ -219,6 +271,8 @@ class BatchedSynthesis:
         out = [[int(x) for x in sols[m, : lens[m]]] if ok[m] else None for m in range(targets)]
         gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
         self.last_stats = {"beam_width": W, "targets": targets, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0}
+        if kern is not None:
+            self.last_stats["kernels"] = True
         if tw is not None:
             self.last_stats["views"] = V
         if merge:
@@ -230,10 +284,15 @@ class BatchedSynthesis:
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
               beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
-        fast: run the sampled searches' forward pass and draw on the policy-layer kernels (bf16 products; default: when they apply and the
-        batch has at least 4 096 envs); solutions are valid either way -- the env decides what solves a target, the policy only proposes.
+        fast: run the forward pass on the policy-layer kernels (bf16 products, f32 accumulation; `last_stats["kernels"]` says whether they
+        ran).  Sampled searches: forward pass and draw (default, fast=None: when the kernels apply and the batch has at least 4 096 envs).
+        deterministic=True and beam_width: only on fast=True (None and False: the torch forward in `dtype`) -- the greedy step takes the
+        arg-max of `collector.mid_head_logp`, the beam search its rows of log-probabilities in place of `log_softmax(logits)`.  fast=True
+        where the kernels do not apply (another policy class or shape, an env without TILE layout or 64-bit observation words) is a
+        ValueError.  Solutions are valid either way -- the env decides what solves a target, the policy only proposes -- but bf16 products
+        may rank two nearly equal actions the other way round than f32 torch, so the greedy and beam results of the two paths can differ.
 
-        beam_width=W >= 1: beam search over the policy's log-probabilities instead (`deterministic`, `num_searches` and `fast` are then
+        beam_width=W >= 1: beam search over the policy's log-probabilities instead (`deterministic` and `num_searches` are then
         ignored; no randomness).  Every target keeps up to W partial gate sequences ("beams"), at first the empty one.  Per step every beam is
         scored `cum + log_softmax(logits)[a]` for each action a (f32), the W best continuations of a target survive (`collector.beam_select`:
         ties by slot, then action), each as a copy of its parent env (`VecEnv.copy_envs`) stepped with its action.  A beam that ends
@@ -276,7 +335,7 @@ class BatchedSynthesis:
                 raise ValueError("beam_width must be at least 1")
             if merge_duplicates and self.env.env_kind == "pauli":
                 raise ValueError("merge_duplicates: a PauliGym observation does not determine its state (rotations beyond the observed columns, DAG order)")
-            return self._solve_beam(states, int(beam_width), bool(merge_duplicates), twists)
+            return self._solve_beam(states, int(beam_width), bool(merge_duplicates), twists, fast is True)
         if merge_duplicates:
             raise ValueError("merge_duplicates needs beam_width")
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
@@ -299,10 +358,10 @@ class BatchedSynthesis:
         parked = torch.full((B,), A, dtype=torch.int32, device=dev)  # out of range: no gate (clifford.rs:324)
         steps = 0
         kern = None
-        if tw is None and not deterministic and fast is not False and (fast or B >= 4096):
+        if tw is None and fast is not False and (fast or (not deterministic and B >= 4096)):  # greedy: on request only
             kern = self._kernels(vec)
             if fast and kern is None:
-                raise ValueError("fast=True needs a BasicPolicy of the default shape and an env whose state or packed observation the first-layer kernels read")
+                raise ValueError(self._NO_KERNELS)
         if kern is not None:
             pol = self._policy
             h1 = torch.empty((B, pol.embeddings.out_features), dtype=torch.bfloat16, device=dev)
@@ -312,11 +371,13 @@ class BatchedSynthesis:
         self.last_stats = {"kernels": kern is not None}
         for t in range(T):
             if kern is not None:
-                if kern[5]:
-                    embed_words(vec.observe_packed(out=words_buf), vec.obs_shape_[1], kern[1], kern[2], h1.shape[1], relu=True, out=h1)
+                self._first_layer(vec, kern, h1, words_buf)
+                if deterministic:  # the arg-max alone: no row is written
+                    mid_head_logp(h1, kern[3], pol.common.out_features, kern[4], A, want_rows=False, actions=act, best_logp=scratch[0], entropy=scratch[1],
+                                  values=scratch[2])
                 else:
-                    embed(vec, kern[1], kern[2], h1.shape[1], relu=True, out=h1)
-                mid_head_sample(h1, kern[3], pol.common.out_features, kern[4], A, self.seed, t, actions=act, logp=scratch[0], entropy=scratch[1], values=scratch[2])
+                    mid_head_sample(h1, kern[3], pol.common.out_features, kern[4], A, self.seed, t, actions=act, logp=scratch[0], entropy=scratch[1],
+                                    values=scratch[2])
             else:
                 x = self._observe(vec, tw)
                 logits = self._policy(x)[0]
@@ -362,10 +423,10 @@ class BatchedSynthesis:
         return out
 
     def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
-              twists: Optional[int] = None):
+              twists: Optional[int] = None, fast: Optional[bool] = None):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
-        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, beam_width=beam_width, merge_duplicates=merge_duplicates,
-                          twists=twists)
+        sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, fast=fast, beam_width=beam_width,
+                          merge_duplicates=merge_duplicates, twists=twists)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):
