@@ -14,19 +14,23 @@ namespace qg {
 // and one lane stores the pair {entry, exit} into the wave's OWN record of the launch's slot (wave w of the grid -> record w; plain 16-byte stores to
 // distinct addresses: atomics folding 1 024 waves into one pair of words queue at one L2 channel for ~12 ns each, and every wave's exit stamp
 // waits for its stores behind them -- the headline kernel read 17 us that way).  The host takes min(entry) and max(exit) over the records.
-// Without a slot (every ordinary launch) the cost is that one scalar instruction and a scalar branch.  Declare as the first statement of a kernel;
+// Without a slot (every ordinary launch) the cost is that one scalar instruction and a scalar branch.  The entry stamp means "the wave's first
+// instructions": nothing waits for it until the exit stamp, so in a kernel whose first vector loads need no scalar load (qm_step1_kernel: preloaded
+// arguments) it returns while those loads are already in flight and adds no wait in front of them.  `block_threads`: the launch's workgroup size when
+// it is a constant the kernel shares with its launcher -- the wave index then needs no blockDim.x (a hidden kernel argument, one more scalar load);
+// 0: read blockDim.x.  Declare as the first statement of a kernel;
 // the destructor runs on every return path (a ragged last wave whose lanes leave at different points writes its record more than once: the
 // last write, the latest exit, stays).
 struct KernelClock {
     unsigned long long *slot;
     unsigned long long t0;
-    uint32_t waves;
-    __device__ inline KernelClock(unsigned long long *s, uint32_t n) : slot(s), t0(wall_clock64()), waves(n) {}
+    uint32_t waves, block;
+    __device__ inline KernelClock(unsigned long long *s, uint32_t n, uint32_t block_threads = 0) : slot(s), t0(wall_clock64()), waves(n), block(block_threads) {}
     __device__ inline ~KernelClock() {
         if (slot) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the wave's own stores have reached the L2 (gfx9: stores count in vmcnt)
             const unsigned long long t1 = wall_clock64();
-            const uint32_t wave = blockIdx.x * ((blockDim.x + 63u) >> 6) + (threadIdx.x >> 6);
+            const uint32_t wave = blockIdx.x * (((block ? block : blockDim.x) + 63u) >> 6) + (threadIdx.x >> 6);
             const unsigned long long m = __ballot(1);
             if (wave < waves && __lane_id() == (unsigned)__ffsll((long long)m) - 1u)
                 *reinterpret_cast<ulonglong2 *>(slot + 2ull * wave) = make_ulonglong2(t0, t1);

@@ -8,7 +8,7 @@
 // Why a second layout: the ROWS layout spends ~19 wave-instructions per env-step (8 lanes per env)
 // and is instruction-issue-bound on MI355X.  Here one lane owns one whole env, so every wave
 // instruction advances 64 envs and nothing crosses lanes: no shuffles, no ballots.  Three kernels:
-//   qm_step1_kernel   one env.step() per launch without add_inverts (the hot path): holds nothing, gathers and
+//   qm_step1_kernel   (kernels_qm_step1.hip) one env.step() per launch without add_inverts (the hot path): holds nothing, gathers and
 //                     scatters the gate's <= 2 row groups, `solved` from an incremental mask (~1.5 wave
 //                     instructions per env-step);
 //   qm_step_kernel    fused rollouts and add_inverts: the env's <= 32 row words live in VGPRs (~4.5);
@@ -488,31 +488,7 @@ __global__ __launch_bounds__(256) void qm_inv2_kernel(StepArgs a) {
     }
 }
 
-// One step per launch without holding the matrix (the env.step() path without add_inverts).  A gate
-// touches the rows of <= 2 qubits (CliffordEnv) / <= 2 rows (LinearFunctionEnv), i.e. <= 2 of the env's
-// 16-byte groups: they are gathered and scattered at per-lane addresses, and `solved` comes from the
-// incrementally kept `bad` mask (bit j: qubit j's rows / row j differ from the identity's).  ~3x fewer
-// instructions than the register-resident kernel, which at one wave per SIMD is what a step costs;
-// measured 3.77 -> 3.15 us per step at B = 65 536 and 34.9 -> 30.0 us at B = 2^20 (CliffordEnv 16q).
-// LIST: also record the envs that finish, one bit each in StepArgs::done_mask (F_DONE_LIST; its own instantiation: the plain kernel's code stays as it is)
-// DENSE (qg_vec_track_dense, N == NXP, D % 16 == 0): the rows the gate rewrote also go to the resident dense int8 observation
-template <int NXP, bool HAS_Z, bool FEAT, bool LIST = false, bool DENSE = false>
-__global__ __launch_bounds__(256) void qm_step1_kernel(StepArgs a) {
-    KernelClock kclk(a.kclk, a.kclk_waves);  // device_common.hpp
-    using Rows = QmRows<NXP, HAS_Z>;
-    constexpr int D16 = DENSE ? Rows::R / 16 : 0;
-    const uint64_t env = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    QG_PREFETCH_STEP_ARGS(a);  // qgym_internal.hpp
-    if constexpr (LIST) {  // every thread reaches the wave's ballot
-        bool fin = false;
-        if (env < a.B) fin = qm_step1_body<HAS_Z, FEAT, D16>(a, Rows::G, env, load_action(a.actions, env, a.flags & F_ACT64));
-        done_mask_store(a.done_mask, a.B, fin, env, a.done_epoch);
-    } else {
-        if (env >= a.B) return;
-        const int64_t act = load_action(a.actions, env, a.flags & F_ACT64);
-        (void)qm_step1_body<HAS_Z, FEAT, D16>(a, Rows::G, env, act);  // qm_step1.hpp
-    }
-}
+// (the one-step kernel without add_inverts, qm_step1_kernel: kernels_qm_step1.hip)
 
 // Fused rollout on LDS-resident rows (T steps per launch, plain configuration: no add_inverts, no solution log, default
 // weights).  The register-resident fused kernel pays ~300 VALU instructions per env-step for select trees over 32 row
@@ -1093,7 +1069,7 @@ __global__ __launch_bounds__(256) void qm_reset_step_kernel(ResetStepArgs ra) {
         if (env < a.B && !((resets >> (env & 63u)) & 1ull)) {
             // (the dense rows are written by lane pairs: a lane whose neighbour is being reset writes its rows alone)
             const bool alone = D16 != 0 && ((resets >> ((env ^ 1ull) & 63u)) & 1ull);
-            fin = qm_step1_body<HAS_Z, FEAT, D16>(a, Rows::G, env, load_action(a.actions, env, a.flags & F_ACT64), alone);
+            fin = qm_step1_body<HAS_Z, FEAT, D16>(step1_front(a), a, Rows::G, env, nullptr, alone);
         }
         done_mask_store(a.done_mask, a.B, fin, env, a.done_epoch);  // (an env being reset: bit clear -- if it is final again after its first step the reset's lane appends it to the list)
         return;
@@ -1101,7 +1077,7 @@ __global__ __launch_bounds__(256) void qm_reset_step_kernel(ResetStepArgs ra) {
     // (plain configuration: the tree's wave takes the env's first step on the rows it holds -- qm_init_finish_wave_step; otherwise the lane
     // that has just written the env's fresh episode -- state, depth, bad mask, log lengths -- takes it, as qm_step1_body)
     qm_init_block<NXP, HAS_Z, false, 1>(ra.reset, role_index, WAVE ? &a : nullptr, [&](uint64_t env, bool stepped, bool fin) {
-        if (!stepped) fin = qm_step1_body<HAS_Z, FEAT, D16>(a, Rows::G, env, load_action(a.actions, env, a.flags & F_ACT64), true);
+        if (!stepped) fin = qm_step1_body<HAS_Z, FEAT, D16>(step1_front(a), a, Rows::G, env, nullptr, true);
         if (fin) {  // (rare: one atomic per env that is final again after its first step)
             const uint32_t slot = atomicAdd(a.done_count, 1u);
             if (slot < a.B) a.done_list[slot] = (uint32_t)env;
@@ -1361,23 +1337,7 @@ static hipError_t launch_step(const StepArgs &a, hipStream_t s) {
     const bool seq = a.T != 1 || a.rewards_seq || a.dones_seq;
     const bool list = a.flags & F_DONE_LIST;
     switch (plan::tile_step(false, plan::tile_inv_kernels(false, HAS_Z, NXP), a.flags, a.T, a.bad != nullptr, a.rewards_seq || a.dones_seq, a.num_actions)) {  // qgym_plan.hpp
-    case plan::SK_QM_STEP1: {  // the env.step() path
-        const dim3 lgrid = grid, lblock = block;
-        if constexpr (QmRows<NXP, HAS_Z>::R % 16 == 0) {
-            if (a.dense) {  // qg_vec_track_dense (the host passes it for N == NXP only)
-                if (feat && list) hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, true, true, true>), lgrid, lblock, 0, s, a);
-                else if (feat) hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, true, false, true>), grid, block, 0, s, a);
-                else if (list) hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, false, true, true>), lgrid, lblock, 0, s, a);
-                else hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, false, false, true>), grid, block, 0, s, a);
-                return hipGetLastError();
-            }
-        }
-        if (feat && list) hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, true, true>), lgrid, lblock, 0, s, a);
-        else if (feat) hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, true>), grid, block, 0, s, a);
-        else if (list) hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, false, true>), lgrid, lblock, 0, s, a);
-        else hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, false>), grid, block, 0, s, a);
-        return hipGetLastError();
-    }
+    case plan::SK_QM_STEP1: return qm_step1(a, NXP, HAS_Z, s);  // the env.step() path: kernels_qm_step1.hip
     case plan::SK_QM_INV2:  // CliffordEnv with add_inverts, every env symplectic, one step per launch: two lanes per env
         if constexpr (HAS_Z && NXP <= 16) {
             const dim3 grid2(grid_for(2 * a.B, 256)), lgrid2 = grid2, lblock = block;

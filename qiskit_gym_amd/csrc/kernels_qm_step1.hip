@@ -1,0 +1,102 @@
+// kernels_qm_step1.hip -- qm_step1_kernel, the one-step kernel of the TILE layout without add_inverts (env.step(): the headline), in a translation
+// unit of its own: the Makefile builds this file alone with the kernel-argument preload (-mllvm -amdgpu-kernarg-preload-count=16), which applies to
+// every kernel of a translation unit that has leading scalar or pointer parameters.  Layout and the other TILE kernels: kernels_qm.hip.
+#include "device_common.hpp"
+#include "qgym_plan.hpp"
+#include "qm_step1.hpp"
+
+namespace qg {
+
+// threads per workgroup of the one-step launch: the kernel and qm_step1 below share it, so the kernel never reads blockDim.x (a hidden kernel
+// argument: one more scalar load in front of the first vector load)
+constexpr uint32_t QM_STEP1_BLOCK = 256;  // 64- and 128-thread blocks measured no faster
+
+// One step per launch without holding the matrix (the env.step() path without add_inverts).  A gate
+// touches the rows of <= 2 qubits (CliffordEnv) / <= 2 rows (LinearFunctionEnv), i.e. <= 2 of the env's
+// 16-byte groups: they are gathered and scattered at per-lane addresses, and `solved` comes from the
+// incrementally kept `bad` mask (bit j: qubit j's rows / row j differ from the identity's).  ~3x fewer
+// instructions than the register-resident kernel, which at one wave per SIMD is what a step costs;
+// measured 3.77 -> 3.15 us per step at B = 65 536 and 34.9 -> 30.0 us at B = 2^20 (CliffordEnv 16q).
+//
+// At one wave per SIMD nothing overlaps a lane's memory round trips, so their number is what the kernel costs (EXPERIMENTS.md round 6).  Four are
+// left, all needed (qm_step1_body, qm_step1.hpp): {action, depth, bad} -> gate entry -> row groups -> every store.  What the front of that chain
+// reads comes as the kernel's leading parameters -- 14 dwords, the most the preload delivers in SGPRs beside the kernarg pointer -- so the first vector
+// loads are issued without a scalar load in front of them; the rest of StepArgs follows by value and is fetched while those loads fly (one batch,
+// waited for where the gate entry is consumed: a cold scalar line must not surface between the rows and the stores).  On firmware
+// that does not preload, the compiler's compatibility prologue loads the same SGPRs first: correct, without the gain.
+// LIST: also record the envs that finish, one bit each in StepArgs::done_mask (F_DONE_LIST; its own instantiation: the plain kernel's code stays as it is)
+// DENSE (qg_vec_track_dense, N == NXP, D % 16 == 0): the rows the gate rewrote also go to the resident dense int8 observation
+template <int NXP, bool HAS_Z, bool FEAT, bool LIST = false, bool DENSE = false>
+__global__ __launch_bounds__(QM_STEP1_BLOCK) void qm_step1_kernel(const void *actions, int32_t *depth, uint32_t *bad, const GateEntry *gates, void *state,
+                                                                   uint64_t B, uint32_t flags, uint32_t num_actions, StepArgs a) {
+#if QG_STEP1_ABLATE & 4
+    const uint32_t block = blockDim.x;
+    KernelClock kclk(a.kclk, a.kclk_waves);  // device_common.hpp
+#else
+    constexpr uint32_t block = QM_STEP1_BLOCK;
+    KernelClock kclk(a.kclk, a.kclk_waves, QM_STEP1_BLOCK);  // device_common.hpp
+#endif
+    constexpr int R = HAS_Z ? 2 * NXP : NXP, G = R / 4;  // row slots and 16-byte groups per env (QmRows, kernels_qm.hip)
+    constexpr int D16 = DENSE ? R / 16 : 0;
+    const Step1Front f{actions, depth, bad, gates, state, B, flags, num_actions};
+    const uint64_t env = (uint64_t)blockIdx.x * block + threadIdx.x;
+    if constexpr (LIST) {  // every thread reaches the wave's ballot
+        bool fin = false;
+        if (env < B) fin = qm_step1_body<HAS_Z, FEAT, D16>(f, a, G, env, nullptr);  // qm_step1.hpp
+        done_mask_store(a.done_mask, B, fin, env, a.done_epoch);
+    } else {
+        if (env >= B) return;
+        (void)qm_step1_body<HAS_Z, FEAT, D16>(f, a, G, env, nullptr);  // qm_step1.hpp
+    }
+}
+
+template <int NXP, bool HAS_Z>
+static hipError_t launch_step1(const StepArgs &a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.B + QM_STEP1_BLOCK - 1) / QM_STEP1_BLOCK)), block(QM_STEP1_BLOCK);
+    const bool feat = a.flags & (F_TRACK | F_LAYERS);
+    const bool list = a.flags & F_DONE_LIST;
+#define QM_STEP1_LAUNCH(...) \
+    hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, __VA_ARGS__>), grid, block, 0, s, a.actions, a.depth, a.bad, a.gates, a.state, a.B, a.flags, a.num_actions, a)
+    constexpr int R = HAS_Z ? 2 * NXP : NXP;
+    if constexpr (R % 16 == 0) {
+        if (a.dense) {  // qg_vec_track_dense (the host passes it for N == NXP only)
+            if (feat && list) QM_STEP1_LAUNCH(true, true, true);
+            else if (feat) QM_STEP1_LAUNCH(true, false, true);
+            else if (list) QM_STEP1_LAUNCH(false, true, true);
+            else QM_STEP1_LAUNCH(false, false, true);
+            return hipGetLastError();
+        }
+    }
+    if (feat && list) QM_STEP1_LAUNCH(true, true);
+    else if (feat) QM_STEP1_LAUNCH(true);
+    else if (list) QM_STEP1_LAUNCH(false, true);
+    else QM_STEP1_LAUNCH(false);
+#undef QM_STEP1_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t qm_step1(const StepArgs &a, uint32_t nxp, bool has_z, hipStream_t s) {
+    if (!a.B) return hipSuccess;
+    if (has_z) {
+        switch (nxp) {
+        case 4: return launch_step1<4, true>(a, s);
+        case 8: return launch_step1<8, true>(a, s);
+        case 12: return launch_step1<12, true>(a, s);
+        case 16: return launch_step1<16, true>(a, s);
+        }
+    } else {
+        switch (nxp) {
+        case 4: return launch_step1<4, false>(a, s);
+        case 8: return launch_step1<8, false>(a, s);
+        case 12: return launch_step1<12, false>(a, s);
+        case 16: return launch_step1<16, false>(a, s);
+        case 20: return launch_step1<20, false>(a, s);
+        case 24: return launch_step1<24, false>(a, s);
+        case 28: return launch_step1<28, false>(a, s);
+        case 32: return launch_step1<32, false>(a, s);
+        }
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace qg

@@ -131,6 +131,9 @@ struct StepArgs {
 // right before its first use -- one cold line after the other along a one-step kernel's dependent chain (bounds check -> action -> gate
 // entry -> rows), plus waited-for re-fetches in the middle of it.  Asking for every field the chain needs at the top of the kernel puts
 // all misses in flight at once and keeps the values in SGPRs (CliffordEnv 16q x 65 536: 3.16 -> 3.10 us per step, same box).
+// The trip itself stays in front of the first vector load: a by-value struct cannot be preloaded.  qm_step1_kernel (kernels_qm_step1.hip) does without it --
+// the fields its front reads are leading kernel parameters, preloaded into SGPRs, and the fields its back reads are asked for under the first vector loads
+// (qm_step1_body, qm_step1.hpp) -- so it does not use this macro; the other step kernels do.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(QG_NO_ARG_PREFETCH)
 #define QG_PREFETCH_STEP_ARGS(a)                                                                                                          \
     asm volatile("" ::"s"((a).state), "s"((a).actions), "s"((a).gates), "s"((a).depth), "s"((a).bad), "s"((a).B), "s"((a).flags),        \
@@ -236,6 +239,7 @@ hipError_t lfd_export(const ObsArgs &a, bool w64, uint32_t rg, const uint8_t *in
 
 hipError_t qm_step(const StepArgs &a, uint32_t nxp, bool has_z, hipStream_t s);
 hipError_t qm_init(const InitArgs &a, uint32_t nxp, bool has_z, hipStream_t s);
+hipError_t qm_step1(const StepArgs &a, uint32_t nxp, bool has_z, hipStream_t s);  // kernels_qm_step1.hip: the env.step() launch of qm_step (SK_QM_STEP1)
 // qg_vec_reset_done (mask + list in `reset`) + qg_vec_step (`step`, F_DONE_LIST: writes ITS mask, a reset env that is final again after its first step
 // goes to ITS list) in one launch
 hipError_t qm_reset_step(const InitArgs &reset, const StepArgs &step, uint32_t nxp, bool has_z, hipStream_t s);

@@ -1,5 +1,5 @@
 // qm_step1.hpp -- the body of the one-step kernel of the TILE layout (CliffordEnv N <= 16, LinearFunctionEnv 8 < N <= 32, no add_inverts),
-// shared by qm_step1_kernel (kernels_qm.hip) and by the policy kernel that samples an action and steps its env in the same launch
+// shared by qm_step1_kernel (kernels_qm_step1.hip), the step lanes of qm_reset_step_kernel (kernels_qm.hip) and by the policy kernel that samples an action and steps its env in the same launch
 // (mid_head_sample_kernel, kernels_policy.hip).  Reference: Clifford::step rust/src/envs/clifford.rs:321-347.
 #pragma once
 
@@ -34,28 +34,111 @@ __device__ inline void qm_group_put(uint32_t (&u)[4], uint32_t q, uint32_t x, ui
     }
 }
 
-// One env.step() of env `env` with action `act` (already loaded): gathers the gate's <= 2 row groups from the env's tile (G groups of
+// The fields the front of the one-step chain reads -- the action, depth and bad-mask loads, the gate entry behind the action, the rows behind the
+// gate entry.  qm_step1_kernel (kernels_qm_step1.hip) takes them as leading kernel parameters of their own (14 dwords: what the kernel-argument preload
+// delivers in SGPRs at wave start, no scalar load in front of the first vector load); every other caller fills them from its StepArgs.
+struct Step1Front {
+    const void *actions;
+    int32_t *depth;
+    uint32_t *bad;
+    const GateEntry *gates;
+    void *state;
+    uint64_t B;
+    uint32_t flags, num_actions;
+};
+__device__ inline Step1Front step1_front(const StepArgs &a) { return Step1Front{a.actions, a.depth, a.bad, a.gates, a.state, a.B, a.flags, a.num_actions}; }
+
+// QG_STEP1_ABLATE (development, tools/build_variant.sh; EXPERIMENTS.md round 6) puts one avoidable round trip back: bit 0 -- the front in its old
+// order (action, then depth and bad, then the gate entry behind the in_range branch), bit 1 -- a wait for the row stores in front of the output
+// stores, bit 2 -- blockDim.x instead of the constant block size (kernels_qm_step1.hip)
+#ifndef QG_STEP1_ABLATE
+#define QG_STEP1_ABLATE 0
+#endif
+
+// The env's action for the one-step kernels in two halves, so that no wait sits inside the width's branch: action_issue only chooses the load
+// instruction (a uniform branch on a flag that sits in an SGPR), action_value extends the sign behind whatever the caller issues in between --
+// those loads then fly with the action (load_action's i32 arm waits for its load inside the branch).  An int64 action keeps all 64 bits: one
+// whose low half alone is in range stays out of range.
+__device__ inline void action_issue(const void *actions, uint64_t idx, bool act64, int32_t &lo, int32_t &hi) {
+    hi = 0;
+    if (act64) {
+        const int64_t v = reinterpret_cast<const int64_t *>(actions)[idx];
+        lo = (int32_t)v;
+        hi = (int32_t)(v >> 32);
+    } else {
+        lo = reinterpret_cast<const int32_t *>(actions)[idx];
+    }
+}
+__device__ inline int64_t action_value(int32_t lo, int32_t hi, bool act64) {
+    hi = act64 ? hi : lo >> 31;
+    return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
+}
+
+// One env.step() of env `env`: gathers the gate's <= 2 row groups from the env's tile (G groups of
 // 1 KiB), applies the gate's 4x4 GF(2) map, scatters, updates the incremental solved mask, depth, reward, done, success (and the
 // solution log / layer metrics when FEAT).  Returns is_final.
+// `act_in`: the env's action when the caller holds it in a register (the policy kernel), or null: load it from f.actions.
+// The dependent memory round trips of a lane are four: {action, depth, bad} issued back to back, the action first -- the gate entry (unconditional,
+// clamped index: an out-of-range action reads entry 0 and is given "no gate, penalty 0" afterwards, clifford.rs:324) needs the action alone; the
+// <= 2 row groups; every store.  depth and bad are pinned where the gate entry is consumed: left alone the compiler sinks their first use below the
+// row stores and waits there for ALL outstanding memory operations -- the output stores then leave only after the row stores have been acknowledged.
 // D16 > 0 (qg_vec_track_dense; the matrix has D = 16 * D16 rows, no padding slots): the rows the gate rewrote also go to the env's
 // dense int8 observation -- <= 4 rows of D bytes instead of the D * D bytes a full qg_vec_observe_dense writes.
 // `alone`: the neighbouring lane does not run this body with the neighbouring env (the reset's lanes in qm_reset_step_kernel): the dense rows are
 // then written by this lane alone.
-template <bool HAS_Z, bool FEAT, int D16 = 0>
-__device__ inline bool qm_step1_body(const StepArgs &a, uint32_t G, uint64_t env, int64_t act, bool alone = false) {
+// PLAIN_FRONT: the front and back as the compiler orders them by itself -- action, then depth and bad, then the gate entry behind the in_range branch,
+// nothing pinned.  The policy kernel (mid_head_sample_kernel) keeps it: it holds the action in a register, sits at its register limit, and the
+// pinned form costs two of its instantiations one VGPR more.
+template <bool HAS_Z, bool FEAT, int D16 = 0, bool PLAIN_FRONT = false>
+__device__ inline bool qm_step1_body(const Step1Front &f, const StepArgs &a, uint32_t G, uint64_t env, const int64_t *act_in, bool alone = false) {
     const uint32_t lane = (uint32_t)env & (QG_WAVE - 1);
-    uint4 *tile = reinterpret_cast<uint4 *>(a.state) + (env >> 6) * (uint64_t)(G * 64);
-    int32_t depth = a.depth[env];
-    const uint32_t bad0 = a.bad[env];
+    uint4 *tile = reinterpret_cast<uint4 *>(f.state) + (env >> 6) * (uint64_t)(G * 64);
+    int64_t act;
+    int32_t depth, sol_n;
+    uint32_t bad0;
+    bool in_range;
+    GateEntry g = GateEntry{QM_IDENTITY << 10, 0.0f};  // "no gate", penalty 0: what an out-of-range action selects (clifford.rs:324)
+    if constexpr (PLAIN_FRONT) {
+        act = act_in ? *act_in : load_action(f.actions, env, f.flags & F_ACT64);
+        depth = f.depth[env];
+        bad0 = f.bad[env];
+        sol_n = (FEAT && (f.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
+        in_range = act >= 0 && act < (int64_t)f.num_actions;  // gateset.get(action) (clifford.rs:324)
+        if (in_range) g = f.gates[act];
+    } else {
+        int32_t act_lo = 0, act_hi = 0;
+        if (!act_in) action_issue(f.actions, env, f.flags & F_ACT64, act_lo, act_hi);
+#if QG_STEP1_ABLATE & 1  // the front in its old order
+        act = act_in ? *act_in : action_value(act_lo, act_hi, f.flags & F_ACT64);
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+        depth = f.depth[env];
+        bad0 = f.bad[env];
+        sol_n = (FEAT && (f.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
+#if QG_STEP1_ABLATE & 1
+        asm volatile("" : "+v"(bad0));
+        in_range = (uint64_t)act < (uint64_t)f.num_actions;
+        if (in_range) g = f.gates[act];
+#else
+        __builtin_amdgcn_sched_barrier(0);  // (compiler only: the loads above are issued before anything uses the action -- the gate entry's load waits for it alone)
+        act = act_in ? *act_in : action_value(act_lo, act_hi, f.flags & F_ACT64);
+        in_range = (uint64_t)act < (uint64_t)f.num_actions;  // gateset.get(action) (clifford.rs:324): 0 <= act < num_actions
+        const GateEntry entry = f.gates[in_range ? act : 0];
+        if (in_range) g = entry;
+#endif
+        // the gate entry, depth and bad are all here: no later wait for a load.  The StepArgs fields the back of the chain reads are asked for here too:
+        // their scalar loads are issued at the top, fly with the vector loads and have long arrived -- left alone the compiler fetches a field right
+        // before its first use, a cold scalar line between the rows and the stores
+        asm volatile("" : "+v"(g.ops), "+v"(g.penalty), "+v"(depth), "+v"(bad0)
+                     : "s"(a.N), "s"(a.rewards_seq), "s"(a.dones_seq), "s"(a.reward), "s"(a.done), "s"(a.success));
+        depth = depth > 0 ? depth - 1 : 0;  // clifford.rs:342
+    }
     uint32_t bad = bad0, fault = 0;
-    int32_t sol_n = (FEAT && (a.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
-    const bool in_range = act >= 0 && act < (int64_t)a.num_actions;  // gateset.get(action) (clifford.rs:324)
     float penalty = 0.0f;
     uint32_t drow[4] = {0, 0, 0, 0}, dword[4] = {0, 0, 0, 0}, dchg = 0;  // D16: the rows the gate changed (bit k of dchg: entry k)
     if (in_range) {
-        const GateEntry g = a.gates[act];
         penalty = g.penalty;
-        const bool layered = FEAT && (a.flags & F_LAYERS);
+        const bool layered = FEAT && (f.flags & F_LAYERS);
         LayerTxn lt;
         if (layered) lt = layers_begin(layer_rec(a.layers, env, 2 * a.N + 2), a.N, a.descs[act]);  // its loads fly with the state's
         const uint32_t q0 = g.ops & 31u, q1 = (g.ops >> 5) & 31u, m = (g.ops >> 10) & 0xFFFFu;
@@ -103,7 +186,7 @@ __device__ inline bool qm_step1_body(const StepArgs &a, uint32_t G, uint64_t env
         // 65 536 envs, this form 4.83 (3.11 without the dense observation).  Every lane that runs this body reaches this point; a pair lane
         // that does not (past the batch's odd end) reads as "no row" -- update_dpp keeps `old` = 0 for a disabled source lane -- and the
         // env it leaves without a partner writes its rows alone.
-        const bool solo = alone || (env ^ 1ull) >= a.B;
+        const bool solo = alone || (env ^ 1ull) >= f.B;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (solo && ((dchg >> k) & 1u)) dense_row_store<2>(a.dense, env, drow[k], dword[k]);
@@ -124,24 +207,32 @@ __device__ inline bool qm_step1_body(const StepArgs &a, uint32_t G, uint64_t env
         for (int k = 0; k < 4; ++k)
             if ((dchg >> k) & 1u) dense_row_store<1>(a.dense, env, drow[k], dword[k]);
     }
-    if (FEAT && (a.flags & F_TRACK)) {  // clifford.rs:334-340
+    if (FEAT && (f.flags & F_TRACK)) {  // clifford.rs:334-340
         if ((uint32_t)sol_n < a.sol_cap) sol_at(a, env, (uint32_t)sol_n++) = sol_word_framed(act, false);
         else fault |= 8u;
     }
-    depth = depth > 0 ? depth - 1 : 0;  // clifford.rs:342
+#if QG_STEP1_ABLATE & 2  // the wait that stood between the row stores and the output stores
+    if constexpr (!PLAIN_FRONT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    if constexpr (PLAIN_FRONT) depth = depth > 0 ? depth - 1 : 0;  // clifford.rs:342
     const bool solved = bad == 0;       // clifford.rs:344
     const float achieved = solved ? 1.0f : 0.0f;
     const float reward = achieved - penalty;  // clifford.rs:345-346
     if (a.rewards_seq) a.rewards_seq[env] = reward;
     if (a.dones_seq) a.dones_seq[env] = (uint8_t)(depth == 0 || solved);
-    if (bad != bad0) a.bad[env] = bad;
-    a.depth[env] = depth;
+    if (bad != bad0) f.bad[env] = bad;
+    f.depth[env] = depth;
     a.reward[env] = reward;
     a.done[env] = (uint8_t)(depth == 0 || solved);  // is_final (clifford.rs:353)
     a.success[env] = (uint8_t)solved;
-    if (FEAT && (a.flags & F_TRACK)) a.sol_len[env * 2] = sol_n;
+    if (FEAT && (f.flags & F_TRACK)) a.sol_len[env * 2] = sol_n;
     if (FEAT && fault) atomicOr(&a.error[env], fault);
     return depth == 0 || solved;
+}
+// ... for the policy kernel: the action in a register, the front from its StepArgs, the body's order left to the compiler
+template <bool HAS_Z, bool FEAT, int D16 = 0>
+__device__ inline bool qm_step1_body(const StepArgs &a, uint32_t G, uint64_t env, int64_t act, bool alone = false) {
+    return qm_step1_body<HAS_Z, FEAT, D16, true>(step1_front(a), a, G, env, &act, alone);
 }
 
 
