@@ -34,7 +34,7 @@ extern "C" {
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
- *      qg_policy_head_logp, qg_policy_mid_head_logp (additions only) */
+ *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -459,6 +459,22 @@ int qg_twist_expand_packed(const void *packed_dev, int word_bytes, uint64_t batc
  * table is uploaded once, by the first call (which therefore may not be made inside a stream capture; later ones may), and is owned by the
  * handle.  QG_ERR_INVALID on a handle without twists (add_perms off, or a PauliEnv). */
 int qg_vec_observe_twisted(qg_vec *v, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, void *stream);
+/* The same view as packed words, the [batch, rows] uint64 format qg_policy_embed_words reads (a packed -> packed bit gather): bit c of
+ * out_dev[e * rows_out + r] = element obs_perms[twist_idx[e]][r * cols + c] of what qg_expand_packed would write for env e (r < rows,
+ * c < cols); bits c >= cols are 0, and so are the words rows <= r < rows_out -- padding, so that a caller reaches the even row count
+ * qg_policy_embed_words asks for whatever the env's.  The input contract is qg_twist_expand_packed's: words of 1, 4 or 8 bytes (1: the byte is
+ * the set column), any table, an entry outside [0, rows*cols) reads as 0, a twist_idx[e] outside [0, n_twists) gives the untwisted
+ * observation.  The output is always 64-bit words, so byte words, 32-bit words and odd row counts reach the words first layer this way.
+ * Limits: cols <= 64, rows * word_bytes <= 2048, rows <= rows_out <= 2 * rows + 2, batch < 2^31, n_twists * rows * cols < 2^31;
+ * QG_ERR_UNSUPPORTED beyond.  QG_ERR_INVALID for a null pointer, a zero size, an unknown word_bytes, cols that do not fit the word, words or
+ * tables not aligned to their element size, out_dev not 8-byte aligned.  A wave makes one output word per ballot and writes 64 of them
+ * as 512 contiguous bytes; the result does not depend on the launch geometry.  Stream-ordered, one launch, no synchronisation, capturable. */
+int qg_twist_pack_words(const void *packed_dev, int word_bytes, uint64_t batch, uint32_t rows, uint32_t cols, const int32_t *obs_perms_dev,
+                        uint32_t n_twists, const int32_t *twist_idx_dev, uint64_t *out_dev, uint32_t rows_out, void *stream);
+/* The handle's own path, the words sibling of qg_vec_observe_twisted: qg_vec_observe_packed into the handle's buffer, then qg_twist_pack_words
+ * through the handle's obs_perms -- the one table both calls share (whichever is called first uploads it, outside a stream capture).
+ * out_dev: uint64 [batch, rows_out].  QG_ERR_INVALID on a handle without twists. */
+int qg_vec_observe_twisted_words(qg_vec *v, const int32_t *twist_idx_dev, uint64_t *out_dev, uint32_t rows_out, void *stream);
 /* out[e] = act_perms[twist_idx[e]][actions[e]]: actions chosen on views -> real actions.  actions_dev / out_dev: [batch] of `action_dtype`
  * (qg_action_dtype; may be the same array), act_perms_dev int32 [n_twists, num_actions].  An action outside [0, num_actions) passes through
  * unchanged (the "no gate" parking action of the search loops, clifford.rs:324), and so does every action of an env whose twist_idx is outside

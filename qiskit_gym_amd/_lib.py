@@ -92,7 +92,7 @@ EXPORTED_SYMBOLS = [
     "qg_vec_set_kernel_clock",
     "qg_kernel_clock_rate_khz",
     "qg_vec_observe_dense_as", "qg_expand_packed", "qg_widen_dense", "qg_sample_actions", "qg_beam_select", "qg_beam_seen_bytes", "qg_beam_merge", "qg_gae",
-    "qg_vec_twists", "qg_twist_expand_packed", "qg_vec_observe_twisted", "qg_untwist_actions",
+    "qg_vec_twists", "qg_twist_expand_packed", "qg_vec_observe_twisted", "qg_untwist_actions", "qg_twist_pack_words", "qg_vec_observe_twisted_words",
     "qg_vec_embed_packed_bytes", "qg_vec_pack_embedding", "qg_vec_embed", "qg_vec_embed_observe",
     "qg_policy_embed_words_packed_bytes", "qg_policy_pack_embed_words", "qg_policy_embed_words",
     "qg_policy_head_packed_bytes", "qg_policy_pack_head", "qg_policy_head_sample", "qg_policy_head_logp", "qg_policy_mid_head_logp",
@@ -181,6 +181,8 @@ def load():
     L.qg_vec_twists.restype = i64
     L.qg_twist_expand_packed.argtypes = [vp, C.c_int, u64, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_int, vp]
     L.qg_vec_observe_twisted.argtypes = [vp, vp, vp, C.c_int, vp]
+    L.qg_twist_pack_words.argtypes = [vp, C.c_int, u64, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+    L.qg_vec_observe_twisted_words.argtypes = [vp, vp, vp, C.c_uint32, vp]
     L.qg_untwist_actions.argtypes = [vp, C.c_int, u64, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
     L.qg_vec_set_clock.argtypes = [vp, vp]
     L.qg_vec_set_counters.argtypes = [vp, u64, u64]

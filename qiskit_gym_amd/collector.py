@@ -191,6 +191,28 @@ def twist_expand_packed(packed: torch.Tensor, cols: int, obs_perms: torch.Tensor
     return out
 
 
+def twist_pack_words(packed: torch.Tensor, cols: int, obs_perms: torch.Tensor, twist_idx: torch.Tensor, rows_out: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`twist_expand_packed` with the view left packed (`qg_twist_pack_words`): int64 [B, rows_out], bit c of out[e, r] = element
+    obs_perms[twist_idx[e]][r*cols + c] of what `expand_packed` writes for env e; bits past `cols` and the words rows .. rows_out-1 are 0.
+    The operands are those of `twist_expand_packed` (cols <= 64); rows_out defaults to rows rounded up to even, the row count
+    `embed_words` takes -- with a first layer packed from the weight padded by `cols` zero columns when rows is odd."""
+    if packed.dim() != 2 or not packed.is_contiguous() or packed.is_floating_point() or packed.element_size() not in (1, 4, 8):
+        raise ValueError("twist_pack_words: packed must be a contiguous [B, rows] tensor of 1-, 4- or 8-byte integers")
+    B, rows = packed.shape
+    _twist_operands("twist_pack_words", obs_perms, twist_idx, B, rows * int(cols), packed.device)
+    rows_out = (rows + 1) // 2 * 2 if rows_out is None else int(rows_out)
+    if rows_out < rows:
+        raise ValueError(f"twist_pack_words: rows_out must be at least the {rows} rows of the input")
+    if out is None:
+        out = torch.empty((B, rows_out), dtype=torch.int64, device=packed.device)
+    if out.dtype != torch.int64 or out.numel() != B * rows_out or not out.is_contiguous() or out.device != packed.device:
+        raise ValueError("twist_pack_words: `out` must be a contiguous int64 [B, rows_out] tensor on the device of packed")
+    _lib.check(_lib.load().qg_twist_pack_words(packed.data_ptr(), packed.element_size(), B, rows, int(cols), obs_perms.data_ptr(), obs_perms.shape[0],
+                                               twist_idx.data_ptr(), out.data_ptr(), rows_out, _stream_ptr()))
+    return out
+
+
 def untwist_actions(actions: torch.Tensor, act_perms: torch.Tensor, twist_idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Actions chosen on views -> real actions (`qg_untwist_actions`): out[e] = act_perms[twist_idx[e]][actions[e]].  actions: int32 / int64
     [B]; act_perms: int32 [n_twists, num_actions]; twist_idx: int32 [B].  An action outside [0, num_actions) and every action of an env whose

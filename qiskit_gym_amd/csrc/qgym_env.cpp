@@ -546,14 +546,15 @@ int64_t qg_vec_twists(const qg_vec *v, int64_t *obs_out, int64_t *act_out) {
     return (int64_t)n;
 }
 
-int qg_vec_observe_twisted(qg_vec *v, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, void *stream) {
-    if (!v || !twist_idx_dev || !out_dev) return set_error(QG_ERR_INVALID, "null argument");
+// What both views of a handle start with: the handle's obs_perms on the device (uploaded once, shared by the two calls) and its packed
+// observation in the handle's own buffer.  `K`: the number of twists.
+static int twisted_words(qg_vec *v, void *stream, qg_vec_info &info, size_t &K) {
     vec_twists(v);
     if (v->obs_perms.empty()) return set_error(QG_ERR_INVALID, "observe_twisted: the handle has no twists (add_perms is off, or a PauliEnv)");
     QG_ON_DEVICE(v);
-    qg_vec_info info;
     qg_vec_get_info(v, &info);
-    const size_t obs = (size_t)info.obs_rows * info.obs_cols, K = v->obs_perms.size();
+    const size_t obs = (size_t)info.obs_rows * info.obs_cols;
+    K = v->obs_perms.size();
     if (!v->d_twist_obs) {  // the table goes to the device once (a blocking copy: the first call of a handle is not made inside a stream capture)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) (void)hipGetLastError();
@@ -581,9 +582,25 @@ int qg_vec_observe_twisted(qg_vec *v, const int32_t *twist_idx_dev, void *out_de
         HIP_TRY(hipMalloc(&v->twist_words, words));
         v->twist_words_bytes = words;
     }
-    if (int rc = qg_vec_observe_packed(v, v->twist_words, stream)) return rc;
+    return qg_vec_observe_packed(v, v->twist_words, stream);
+}
+
+int qg_vec_observe_twisted(qg_vec *v, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, void *stream) {
+    if (!v || !twist_idx_dev || !out_dev) return set_error(QG_ERR_INVALID, "null argument");
+    qg_vec_info info;
+    size_t K = 0;
+    if (int rc = twisted_words(v, stream, info, K)) return rc;
     return twist_expand_impl(v->twist_words, (int)info.packed_word_bytes, v->B, info.packed_words_per_env, (uint32_t)info.obs_cols, v->d_twist_obs,
                              (uint32_t)K, twist_idx_dev, out_dev, out_dtype, (hipStream_t)stream);
+}
+
+int qg_vec_observe_twisted_words(qg_vec *v, const int32_t *twist_idx_dev, uint64_t *out_dev, uint32_t rows_out, void *stream) {
+    if (!v || !twist_idx_dev || !out_dev) return set_error(QG_ERR_INVALID, "null argument");
+    qg_vec_info info;
+    size_t K = 0;
+    if (int rc = twisted_words(v, stream, info, K)) return rc;
+    return twist_words_impl(v->twist_words, (int)info.packed_word_bytes, v->B, info.packed_words_per_env, (uint32_t)info.obs_cols, v->d_twist_obs,
+                            (uint32_t)K, twist_idx_dev, out_dev, rows_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -147,7 +147,7 @@ struct qg_vec {
     bool twists_done = false;
     std::vector<std::vector<int64_t>> obs_perms, act_perms;
     int32_t *d_twist_obs = nullptr;    // [n twists][obs_rows * obs_cols]
-    void *twist_words = nullptr;       // qg_vec_observe_twisted: the packed observation its view is made from
+    void *twist_words = nullptr;       // qg_vec_observe_twisted(_words): the packed observation the view is made from
     size_t twist_words_bytes = 0;
 
     // rollout graphs
@@ -190,6 +190,9 @@ void build_twists(const qg_vec *v, std::vector<std::vector<int64_t>> &obs_perms,
 // qg_twist_expand_packed (kernels_twist.hip)
 int twist_expand_impl(const void *packed_dev, int word_bytes, uint64_t batch, uint32_t rows, uint32_t cols, const int32_t *obs_perms_dev,
                       uint32_t n_twists, const int32_t *twist_idx_dev, void *out_dev, int out_dtype, hipStream_t s);
+// qg_twist_pack_words (kernels_twist.hip)
+int twist_words_impl(const void *packed_dev, int word_bytes, uint64_t batch, uint32_t rows, uint32_t cols, const int32_t *obs_perms_dev,
+                     uint32_t n_twists, const int32_t *twist_idx_dev, uint64_t *out_dev, uint32_t rows_out, hipStream_t s);
 // PauliEnv host hooks (pauli_host.cpp)
 int pauli_alloc(qg_vec *v);
 int pauli_init_identity(qg_vec *v, hipStream_t s);

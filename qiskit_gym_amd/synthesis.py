@@ -24,6 +24,8 @@ writes the arg-max and the row of log-probabilities (`mid_head_logp`), which `be
 `solve(..., twists=V)` gives every target V symmetry views (`VecEnv.observe_twisted` / `untwist_actions`): the policy looks at a target through
 an automorphism of the coupling map and its choice is mapped back, what `RLSynthesis.init_algorithm` hands the reference's policy as
 `obs_perms` / `act_perms` (rl/synthesis.py:97-104) -- here one fixed view per search, so the deterministic searches get V opinions per target.
+`twist_kernels=True` runs such a search on the policy-layer kernels: the view is written as packed words (`VecEnv.observe_twisted_words`),
+which is what `embed_words` reads.
 """
 from __future__ import annotations
 
@@ -72,10 +74,50 @@ class BatchedSynthesis:
         # one layer of the new weights with another of the old, and follow the policy as the torch forward does.
         self._packed: Dict[int, Optional[tuple]] = {}
         self._packed_tail = None
+        self._packed_views = None  # twist_kernels: the first layer packed for `embed_words` on the views' words (no handle in it: packed once)
         self._packed_at = None
         self.last_stats: dict = {}
 
     _NO_KERNELS = "fast=True needs a BasicPolicy of the default shape and an env whose state or packed observation the first-layer kernels read"
+
+    _NO_TWIST_KERNELS = "twist_kernels=True needs a BasicPolicy of the default shape and an env with twists whose observation has at most 64 columns"
+
+    def _weights_current(self):
+        """Drop every packed operand when the weights were updated in place since they were packed."""
+        at = tuple((id(p), p._version) for p in self._policy.parameters())
+        if at != self._packed_at:
+            self._packed.clear()
+            self._packed_tail, self._packed_views, self._packed_at = None, None, at
+
+    def _tail(self):
+        """Bias of the first layer, packed middle layer and head: packed once, shared by every handle and by the views."""
+        if self._packed_tail is None:
+            pol = self._policy
+            w, b, A = pol.fused_heads()
+            self._packed_tail = (pol.embeddings.bias.detach().float().contiguous(), pack_mid(pol.common.weight, pol.common.bias),
+                                 pack_head(w, b, A, A, after_mid=True))
+        return self._packed_tail
+
+    def _view_kernels(self, vec: VecEnv):
+        """Operands of the policy-layer kernels for a search under twists, in the form of `_kernels`: the first layer is `embed_words` on
+        `observe_twisted_words`, whose row count is the env's rounded up to even -- the weight gets `cols` zero columns for the pad word.
+        ValueError where they do not apply."""
+        pol = self._policy
+        if not isinstance(pol, BasicPolicy):
+            raise ValueError(self._NO_TWIST_KERNELS)
+        self._weights_current()
+        if self._packed_views is None:
+            rows, cols = vec.obs_shape_
+            try:
+                if cols > 64 or vec.packed_words_per_env != rows:
+                    raise ValueError("a row of the view is one 64-bit word")
+                w = pol.embeddings.weight.detach()
+                if rows % 2:
+                    w = torch.nn.functional.pad(w, (0, cols))
+                self._packed_views = (pack_embed_words(w, rows + rows % 2, cols), *self._tail())
+            except (ValueError, KeyError, _lib.QGymError) as e:
+                raise ValueError(f"{self._NO_TWIST_KERNELS} ({e})") from None
+        return (vec, *self._packed_views, True)
 
     def _kernels(self, vec: VecEnv):
         """Operands of the two policy-layer kernels (qg_vec_embed, qg_policy_mid_head_sample / _logp: bf16 products, f32 accumulation) when the
@@ -83,10 +125,7 @@ class BatchedSynthesis:
         pol = self._policy
         if not isinstance(pol, BasicPolicy):
             return None
-        at = tuple((id(p), p._version) for p in pol.parameters())
-        if at != self._packed_at:  # the weights were updated in place since the operands were packed
-            self._packed.clear()
-            self._packed_tail, self._packed_at = None, at
+        self._weights_current()
         hit = self._packed.get(id(vec))
         if hit is not None and hit[0] is vec:
             return hit
@@ -100,11 +139,7 @@ class BatchedSynthesis:
                     raise
                 first = pack_embed_words(pol.embeddings.weight, *vec.obs_shape_)  # 64-bit row words (PauliEnv, wide CliffordEnv): qg_policy_embed_words
                 words = True
-            if self._packed_tail is None:
-                w, b, A = pol.fused_heads()
-                self._packed_tail = (pol.embeddings.bias.detach().float().contiguous(), pack_mid(pol.common.weight, pol.common.bias),
-                                     pack_head(w, b, A, A, after_mid=True))
-            packed = (vec, first, *self._packed_tail, words)
+            packed = (vec, first, *self._tail(), words)
         except (ValueError, _lib.QGymError):
             packed = None
         if packed is not None:
@@ -115,8 +150,19 @@ class BatchedSynthesis:
         self._packed.pop(id(vec), None)
         vec.close()
 
-    def _first_layer(self, vec: VecEnv, kern, h1: torch.Tensor, words_buf: Optional[torch.Tensor]) -> torch.Tensor:
-        """relu(obs W1^T + b1) of the handle's current state into `h1` (bf16), from the resident bits or the packed observation words."""
+    def _words_buf(self, vec: VecEnv, kern, tw: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """Where the words route of `_first_layer` keeps its packed observation (None for the resident-state route)."""
+        if not kern[5]:
+            return None
+        rows = vec.obs_shape_[0] + vec.obs_shape_[0] % 2 if tw is not None else vec.packed_words_per_env
+        return torch.empty((vec.batch, rows), dtype=torch.int64, device=vec.device)
+
+    def _first_layer(self, vec: VecEnv, kern, h1: torch.Tensor, words_buf: Optional[torch.Tensor], tw: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """relu(obs W1^T + b1) of the handle's current state into `h1` (bf16), from the resident bits or the packed observation words; under
+        twists (`tw`, operands of `_view_kernels`) from the words of every env's view."""
+        if tw is not None:
+            words = vec.observe_twisted_words(tw, words_buf.shape[1], out=words_buf)
+            return embed_words(words, vec.obs_shape_[1], kern[1], kern[2], h1.shape[1], relu=True, out=h1)
         if kern[5]:
             return embed_words(vec.observe_packed(out=words_buf), vec.obs_shape_[1], kern[1], kern[2], h1.shape[1], relu=True, out=h1)
         return embed(vec, kern[1], kern[2], h1.shape[1], relu=True, out=h1)
@@ -178,14 +224,14 @@ class BatchedSynthesis:
         return self._view_list[:V]
 
     def _solve_beam(self, states: Sequence[Sequence[int]], W: int, merge: bool = False, twists: Optional[int] = None,
-                    fast: bool = False) -> List[Optional[List[int]]]:
+                    fast: bool = False, twist_kernels: bool = False) -> List[Optional[List[int]]]:
         if twists is not None:
-            return self._solve_beam_views(states, W, merge, twists)
+            return self._solve_beam_views(states, W, merge, twists, twist_kernels)
         M = len(states)
         cur, oth, win = self._beam_vecs(M, W)
         return self._beam_search(states, 1, None, W, merge, cur, oth, win, fast)
 
-    def _solve_beam_views(self, states, W: int, merge: bool, twists: int) -> List[Optional[List[int]]]:
+    def _solve_beam_views(self, states, W: int, merge: bool, twists: int, twist_kernels: bool = False) -> List[Optional[List[int]]]:
         """Beam search under V views per target: the groups are the (target, view) pairs, each searched under its own fixed view (and with
         its own merge history); a target's winner is the best result of its V groups, ties to the lowest view."""
         M = len(states)
@@ -193,17 +239,22 @@ class BatchedSynthesis:
         V = len(views)
         cur, oth, win = self._beam_vecs(M * V, W, True)
         tw = torch.tensor(views, dtype=torch.int32, device=cur.device).repeat(M).repeat_interleave(W).contiguous()  # env b: group b // W, view (b // W) % V
-        return self._beam_search(states, V, tw, W, merge, cur, oth, win)
+        return self._beam_search(states, V, tw, W, merge, cur, oth, win, view_kernels=twist_kernels)
 
-    def _beam_search(self, states, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv, fast: bool = False):
+    def _beam_search(self, states, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv, fast: bool = False,
+                     view_kernels: bool = False):
         """`tw` None: the search of `solve(beam_width=W)`.  Else int32 [B]: every env's twist index; there are V consecutive groups per target.
-        `fast`: the log-probabilities come from the policy-layer kernels (`tw` is None then)."""
+        `fast`: the log-probabilities come from the policy-layer kernels (`tw` is None then); `view_kernels`: the same under `tw`, the first
+        layer reading the views as packed words."""
         targets = len(states)
         M = targets * V  # groups
         B, A, dev = cur.batch, cur.num_actions(), cur.device
         kern = None
-        if fast:  # the two search handles take turns: each has its own packed first layer (packed through the handle), the rest is shared
-            kern = {id(v): self._kernels(v) for v in (cur, oth)}
+        if fast or view_kernels:  # the two search handles take turns: each has its own packed first layer (packed through the handle), the rest is shared
+            if view_kernels:
+                kern = {id(v): self._view_kernels(v) for v in (cur, oth)}
+            else:
+                kern = {id(v): self._kernels(v) for v in (cur, oth)}
             if any(k is None for k in kern.values()):
                 raise ValueError(self._NO_KERNELS)
             pol = self._policy
@@ -211,7 +262,7 @@ class BatchedSynthesis:
             rows = torch.empty((B, (A + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :A]  # 16-byte row stride: 16-byte stores
             top = torch.empty(B, dtype=torch.int32, device=dev)  # the kernel's other outputs: not used by the search
             scratch = torch.empty((3, B), dtype=torch.float32, device=dev)
-            words_buf = torch.empty((B, cur.packed_words_per_env), dtype=torch.int64, device=dev) if kern[id(cur)][5] else None
+            words_buf = self._words_buf(cur, kern[id(cur)], tw)
         T = int(cur._cfg.max_depth)
         self._load(win, states, V)  # the targets once per group; a group nobody solves keeps its slot, a solved one is overwritten by its winner
         group = torch.arange(M, dtype=torch.int32, device=dev)
@@ -233,7 +284,7 @@ class BatchedSynthesis:
         for t in range(T):
             if kern is not None:  # first layer from the bits, then middle layer + head + log-softmax in one kernel: no logits in memory
                 k = kern[id(cur)]
-                logp = mid_head_logp(self._first_layer(cur, k, h1, words_buf), k[3], pol.common.out_features, k[4], A, logp_rows=rows, actions=top,
+                logp = mid_head_logp(self._first_layer(cur, k, h1, words_buf, tw), k[3], pol.common.out_features, k[4], A, logp_rows=rows, actions=top,
                                      best_logp=scratch[0], entropy=scratch[1], values=scratch[2])[0]
             else:
                 logits = self._policy(self._observe(cur, tw))[0]
@@ -282,7 +333,8 @@ class BatchedSynthesis:
 
     @torch.no_grad()
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
-              beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None) -> List[Optional[List[int]]]:
+              beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None,
+              twist_kernels: bool = False) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         fast: run the forward pass on the policy-layer kernels (bf16 products, f32 accumulation; `last_stats["kernels"]` says whether they
         ran).  Sampled searches: forward pass and draw (default, fast=None: when the kernels apply and the batch has at least 4 096 envs).
@@ -319,15 +371,29 @@ class BatchedSynthesis:
         history -- and a target's winner is the best result over its groups, ties to the lowest view.  View 0 is the search without twists,
         so under the default reward weights `twists=V` never solves fewer targets nor needs more gates than `twists=None` in the two
         deterministic modes.  The policy-layer kernels read the resident state and cannot see a view: the torch forward is used, and
-        `fast=True` with `twists` is a ValueError; so is PauliGym, which permutes inside observe / step and has no twists (pauli.rs:675-679)."""
+        `fast=True` with `twists` is a ValueError; so is PauliGym, which permutes inside observe / step and has no twists (pauli.rs:675-679).
+
+        twist_kernels=True (with `twists`; default False: everything as above) runs the twisted search on the policy-layer kernels all the
+        same, in all three modes: `VecEnv.observe_twisted_words` writes every env's view as packed 64-bit row words, which is the input of
+        `collector.embed_words`; then `mid_head_sample` (the `(seed, t)` counters of the `fast` path) or `mid_head_logp` (greedy: the
+        arg-max; beam: the rows for `beam_select`), `untwist_actions`, `step`.  The first layer is packed once per weight version for the
+        env's rows rounded up to even (an odd row count gets a zero pad word and `cols` zero weight columns), so this also reaches envs
+        `fast=True` does not: byte and 32-bit observation words, odd row counts.  Groups, views, tie rules and winners are those of the
+        torch path, solutions hold real actions, and `last_stats` carries "kernels": True beside "views"; as for `fast`, bf16 products may
+        rank two nearly equal actions the other way round than the torch forward, so results can differ from `twists=V` alone.
+        ValueError: without `twists`, together with `fast=True`, on PauliGym, with a policy that is not a `BasicPolicy` of the kernels'
+        shape, or an observation of more than 64 columns."""
         M = len(states)
+        if twist_kernels and twists is None:
+            raise ValueError("twist_kernels=True needs twists: it is the kernel path of a search under symmetry views")
         if twists is not None:
             if int(twists) < 1:
                 raise ValueError("twists must be at least 1")
             if self.env.env_kind == "pauli":
                 raise ValueError("twists: PauliGym permutes inside observe() / step() and exposes no twists (pauli.rs:675-679)")
             if fast:
-                raise ValueError("fast=True cannot be combined with twists: the policy-layer kernels read the resident state, not a view")
+                raise ValueError("fast=True cannot be combined with twists: the policy-layer kernels read the resident state, not a view"
+                                 " (twist_kernels=True runs a twisted search on the kernels)")
         if M == 0:
             return []
         if beam_width is not None:
@@ -335,7 +401,7 @@ class BatchedSynthesis:
                 raise ValueError("beam_width must be at least 1")
             if merge_duplicates and self.env.env_kind == "pauli":
                 raise ValueError("merge_duplicates: a PauliGym observation does not determine its state (rotations beyond the observed columns, DAG order)")
-            return self._solve_beam(states, int(beam_width), bool(merge_duplicates), twists, fast is True)
+            return self._solve_beam(states, int(beam_width), bool(merge_duplicates), twists, fast is True, bool(twist_kernels))
         if merge_duplicates:
             raise ValueError("merge_duplicates needs beam_width")
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
@@ -358,7 +424,9 @@ class BatchedSynthesis:
         parked = torch.full((B,), A, dtype=torch.int32, device=dev)  # out of range: no gate (clifford.rs:324)
         steps = 0
         kern = None
-        if tw is None and fast is not False and (fast or (not deterministic and B >= 4096)):  # greedy: on request only
+        if twist_kernels:
+            kern = self._view_kernels(vec)
+        elif tw is None and fast is not False and (fast or (not deterministic and B >= 4096)):  # greedy: on request only
             kern = self._kernels(vec)
             if fast and kern is None:
                 raise ValueError(self._NO_KERNELS)
@@ -367,11 +435,11 @@ class BatchedSynthesis:
             h1 = torch.empty((B, pol.embeddings.out_features), dtype=torch.bfloat16, device=dev)
             act = torch.empty(B, dtype=torch.int32, device=dev)
             scratch = torch.empty((3, B), dtype=torch.float32, device=dev)
-            words_buf = torch.empty((B, vec.packed_words_per_env), dtype=torch.int64, device=dev) if kern[5] else None
+            words_buf = self._words_buf(vec, kern, tw)
         self.last_stats = {"kernels": kern is not None}
         for t in range(T):
             if kern is not None:
-                self._first_layer(vec, kern, h1, words_buf)
+                self._first_layer(vec, kern, h1, words_buf, tw)
                 if deterministic:  # the arg-max alone: no row is written
                     mid_head_logp(h1, kern[3], pol.common.out_features, kern[4], A, want_rows=False, actions=act, best_logp=scratch[0], entropy=scratch[1],
                                   values=scratch[2])
@@ -385,8 +453,8 @@ class BatchedSynthesis:
                     act = logits.argmax(dim=1).to(torch.int32)
                 else:
                     act = sample_actions(logits.contiguous(), self.seed, t)[0].to(torch.int32)
-                if tw is not None:  # chosen on the view: the real action
-                    vec.untwist_actions(act, tw, out=act)
+            if tw is not None:  # chosen on the view: the real action
+                vec.untwist_actions(act, tw, out=act)
             actions[t] = torch.where(finished, parked, act)
             vec.step(actions[t])
             live = ~finished
@@ -423,10 +491,10 @@ class BatchedSynthesis:
         return out
 
     def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
-              twists: Optional[int] = None, fast: Optional[bool] = None):
+              twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
         sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, fast=fast, beam_width=beam_width,
-                          merge_duplicates=merge_duplicates, twists=twists)
+                          merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):

@@ -356,6 +356,22 @@ class VecEnv:
         _lib.check(self._L.qg_vec_observe_twisted(self._h, twist_idx.data_ptr(), out.data_ptr(), self._DTYPES[dtype], self._stream()))
         return out
 
+    def observe_twisted_words(self, twist_idx: torch.Tensor, rows_out: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`observe_twisted` as packed words, int64 [B, rows_out] (`qg_vec_observe_twisted_words`): bit c of out[e, r] is entry r*cols + c of env
+        e's view, words rows .. rows_out-1 are 0.  What `collector.embed_words` reads, for every env with twists and at most 64 columns,
+        whatever its own word size and row count; rows_out defaults to the rows rounded up to even, which `embed_words` asks for."""
+        self._twist_idx("observe_twisted_words", twist_idx)
+        rows = self.obs_shape_[0]
+        rows_out = (rows + 1) // 2 * 2 if rows_out is None else int(rows_out)
+        if rows_out < rows:
+            raise ValueError(f"observe_twisted_words: rows_out must be at least the {rows} rows of the observation")
+        if out is None:
+            out = torch.empty((self.batch, rows_out), dtype=torch.int64, device=self.device)
+        if out.dtype != torch.int64 or out.numel() != self.batch * rows_out or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("observe_twisted_words: `out` must be a contiguous int64 [B, rows_out] tensor on the env's device")
+        _lib.check(self._L.qg_vec_observe_twisted_words(self._h, twist_idx.data_ptr(), out.data_ptr(), rows_out, self._stream()))
+        return out
+
     def untwist_actions(self, actions: torch.Tensor, twist_idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """out[e] = act_perms[twist_idx[e]][actions[e]] (`qg_untwist_actions`): the real action of one chosen on `observe_twisted`'s view.
         Actions outside [0, num_actions) and envs with an out-of-range twist index pass through; `out` may be `actions`."""
