@@ -26,10 +26,16 @@ an automorphism of the coupling map and its choice is mapped back, what `RLSynth
 `obs_perms` / `act_perms` (rl/synthesis.py:97-104) -- here one fixed view per search, so the deterministic searches get V opinions per target.
 `twist_kernels=True` runs such a search on the policy-layer kernels: the view is written as packed words (`VecEnv.observe_twisted_words`),
 which is what `embed_words` reads.
+
+How the policy's opinion about a handle's current state is obtained is one decision, taken once per `solve`: the step loops ask a forward
+object (`_TorchForward`, `_KernelForward`) for the row of log-probabilities, the arg-max or the draw, and know nothing else about it.  The
+kernels' operands are a snapshot of the weights (`_Packed`); the first layer packed through a handle stays with the handle's owner
+(`_Handles.first`) and goes when the handle is closed or the snapshot dropped.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -54,6 +60,130 @@ def policy_from_reference_state_dict(sd: Dict[str, "np.ndarray | torch.Tensor"])
     return pol
 
 
+@dataclass
+class _FirstLayer:
+    """The first layer packed for one route of the kernel forward: "state" is `embed` on the handle's resident bits (TILE layout), "words"
+    `embed_words` on `observe_packed` (64-bit row words: PauliEnv, wide CliffordEnv), "views" `embed_words` on `observe_twisted_words`."""
+    route: str
+    weight: torch.Tensor
+
+
+@dataclass
+class _Packed:
+    """The policy-layer kernels' operands: a snapshot of the policy's weights at `at`, the parameters' version counters.  An in-place
+    update of the policy drops all of it, the per-handle first layers (`_Handles.first`) included, so the kernels never run one layer of the
+    new weights with another of the old, and follow the policy as the torch forward does."""
+    at: tuple
+    bias: torch.Tensor  # of the first layer, f32
+    mid: torch.Tensor  # packed middle layer and head: packed once, shared by every handle and by the views
+    head: torch.Tensor
+    views: Optional[_FirstLayer] = None  # twist_kernels: the first layer for the views' words (no handle in it: packed once)
+
+
+@dataclass
+class _Handles:
+    """The handles of one kind, all of one batch shape (`key`), and per handle the first layer packed through it (`pack_embedding` goes
+    through the handle that will read it), in the route the handle takes: closed and dropped together."""
+    key: tuple
+    vecs: Tuple[VecEnv, ...]
+    first: Dict[VecEnv, _FirstLayer] = field(default_factory=dict)
+
+
+def _winner(solved: torch.Tensor, ret: torch.Tensor):
+    """Per row of `solved` / `ret` [N, K]: the scores (the return where solved, else -inf) and the index of the best; argmax takes the first
+    of equal maxima: the lowest index."""
+    score = torch.where(solved, ret, torch.full(ret.shape, -float("inf"), device=ret.device))
+    return score, score.argmax(dim=1)
+
+
+class _Forward:
+    """What the step loops ask about a handle's current state: `logp(vec)`, the rows of log-probabilities [B, A] f32 (beam search);
+    `greedy(vec)`, the arg-max, int32 [B]; `draw(vec, t)`, the draw of step t from `seed`, int32 [B].  Under twists (`tw` int32 [B]: env e
+    is seen through twist tw[e]) the answers are about the view, and `real_actions` maps a choice back.  `kernels` is for `last_stats`."""
+
+    def __init__(self, seed: int, tw: Optional[torch.Tensor]):
+        self.seed, self.tw = seed, tw
+
+    def real_actions(self, vec: VecEnv, act: torch.Tensor) -> torch.Tensor:
+        """`act` was chosen on the view: the real action, in place."""
+        return act if self.tw is None else vec.untwist_actions(act, self.tw, out=act)
+
+
+class _TorchForward(_Forward):
+    """The answers of the policy module in `dtype`."""
+    kernels = False
+
+    def __init__(self, policy: torch.nn.Module, dtype: torch.dtype, seed: int, tw: Optional[torch.Tensor]):
+        super().__init__(seed, tw)
+        self.policy, self.dtype = policy, dtype
+
+    def _logits(self, vec: VecEnv) -> torch.Tensor:
+        """The policy on what it reads, in its dtype: the observation, or the view.  A dtype the library does not write (float64) is written
+        as float32 and widened: the entries are 0 and 1."""
+        dt = self.dtype if self.dtype in VecEnv._DTYPES else torch.float32
+        x = vec.observe_as(dt) if self.tw is None else vec.observe_twisted(self.tw, dt)
+        return self.policy(x if dt == self.dtype else x.to(self.dtype))[0]
+
+    def logp(self, vec: VecEnv) -> torch.Tensor:
+        return torch.log_softmax(self._logits(vec).float(), dim=1)
+
+    def greedy(self, vec: VecEnv) -> torch.Tensor:
+        return self._logits(vec).argmax(dim=1).to(torch.int32)
+
+    def draw(self, vec: VecEnv, t: int) -> torch.Tensor:
+        return sample_actions(self._logits(vec).contiguous(), self.seed, t)[0].to(torch.int32)
+
+
+class _KernelForward(_Forward):
+    """The answers of the policy-layer kernels (bf16 products, f32 accumulation): the first layer from the bits (`first`: per handle
+    its packed first layer and route), then middle layer + head + log-softmax or draw in one kernel, no logits in memory.  The buffers are
+    allocated here, once per search; `greedy` and `draw` return the same buffer every step."""
+    kernels = True
+
+    def __init__(self, packed: _Packed, first: Dict[VecEnv, _FirstLayer], policy: BasicPolicy, seed: int, tw: Optional[torch.Tensor], rows: bool):
+        super().__init__(seed, tw)
+        self.packed, self.first = packed, first
+        vec = next(iter(first))  # the handles of a search are alike
+        B, dev = vec.batch, vec.device
+        self.hidden, self.common, self.A = policy.embeddings.out_features, policy.common.out_features, vec.num_actions()
+        self.h1 = torch.empty((B, self.hidden), dtype=torch.bfloat16, device=dev)
+        # 16-byte row stride: 16-byte stores
+        self.rows = torch.empty((B, (self.A + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, : self.A] if rows else None
+        self.act = torch.empty(B, dtype=torch.int32, device=dev)
+        self.scratch = torch.empty((3, B), dtype=torch.float32, device=dev)  # the kernels' other outputs: not used by the searches
+        # where the two words routes keep the packed observation; the views' row count is the env's rounded up to even
+        words = {"state": 0, "words": vec.packed_words_per_env, "views": vec.obs_shape_[0] + vec.obs_shape_[0] % 2}[first[vec].route]
+        self.words = torch.empty((B, words), dtype=torch.int64, device=dev) if words else None
+
+    def _first_layer(self, vec: VecEnv) -> torch.Tensor:
+        """relu(obs W1^T + b1) of the handle's current state into `h1` (bf16)."""
+        first, bias = self.first[vec], self.packed.bias
+        if first.route == "state":
+            return embed(vec, first.weight, bias, self.hidden, relu=True, out=self.h1)
+        if first.route == "words":
+            words = vec.observe_packed(out=self.words)
+        else:
+            words = vec.observe_twisted_words(self.tw, self.words.shape[1], out=self.words)
+        return embed_words(words, vec.obs_shape_[1], first.weight, bias, self.hidden, relu=True, out=self.h1)
+
+    def logp(self, vec: VecEnv) -> torch.Tensor:
+        p, s = self.packed, self.scratch
+        return mid_head_logp(self._first_layer(vec), p.mid, self.common, p.head, self.A, logp_rows=self.rows, actions=self.act, best_logp=s[0],
+                             entropy=s[1], values=s[2])[0]
+
+    def greedy(self, vec: VecEnv) -> torch.Tensor:
+        p, s = self.packed, self.scratch
+        mid_head_logp(self._first_layer(vec), p.mid, self.common, p.head, self.A, want_rows=False, actions=self.act, best_logp=s[0], entropy=s[1],
+                      values=s[2])  # the arg-max alone: no row is written
+        return self.act
+
+    def draw(self, vec: VecEnv, t: int) -> torch.Tensor:
+        p, s = self.packed, self.scratch
+        mid_head_sample(self._first_layer(vec), p.mid, self.common, p.head, self.A, self.seed, t, actions=self.act, logp=s[0], entropy=s[1],
+                        values=s[2])
+        return self.act
+
+
 class BatchedSynthesis:
     """`env`: one of the *Gym front ends (its configuration and gateset are used); `policy`: a module mapping the flat
     observation [B, rows*cols] to (logits [B, num_actions], value [B])."""
@@ -64,124 +194,97 @@ class BatchedSynthesis:
         self.seed = int(seed)
         self.device = device
         self._policy = policy
-        self._vecs: Dict[tuple, VecEnv] = {}
-        self._beam = None  # ((targets, width), (two search batches, the winners)): the beam search's handles
+        self._held: Dict[str, _Handles] = {}  # by kind, see `_handles`
         self._view_list = None  # twists: the twist index behind each view (`_views`)
-        # the policy-layer kernels' operands per search handle, by id(vec): (vec, packed first layer, its f32 bias, packed middle layer, packed
-        # head, words route?) or None where they do not apply.  The first layer is packed through the handle it will read (`pack_embedding`);
-        # bias, middle layer and head are packed once and shared (`_packed_tail`).  All of it is a snapshot of the policy's weights at
-        # `_packed_at` (the parameters' version counters): an in-place update of the policy drops the whole cache, so the kernels never run
-        # one layer of the new weights with another of the old, and follow the policy as the torch forward does.
-        self._packed: Dict[int, Optional[tuple]] = {}
-        self._packed_tail = None
-        self._packed_views = None  # twist_kernels: the first layer packed for `embed_words` on the views' words (no handle in it: packed once)
-        self._packed_at = None
+        self._packed: Optional[_Packed] = None
         self.last_stats: dict = {}
 
     _NO_KERNELS = "fast=True needs a BasicPolicy of the default shape and an env whose state or packed observation the first-layer kernels read"
 
     _NO_TWIST_KERNELS = "twist_kernels=True needs a BasicPolicy of the default shape and an env with twists whose observation has at most 64 columns"
 
-    def _weights_current(self):
-        """Drop every packed operand when the weights were updated in place since they were packed."""
-        at = tuple((id(p), p._version) for p in self._policy.parameters())
-        if at != self._packed_at:
-            self._packed.clear()
-            self._packed_tail, self._packed_views, self._packed_at = None, None, at
+    @property
+    def _beam(self) -> Optional[_Handles]:
+        """The beam search's handles (two search batches that take turns, and the winners); None until a beam search has run."""
+        return self._held.get("beam")
 
-    def _tail(self):
-        """Bias of the first layer, packed middle layer and head: packed once, shared by every handle and by the views."""
-        if self._packed_tail is None:
-            pol = self._policy
+    def _handles(self, kind: str, batches: Sequence[int], perms: bool = False) -> _Handles:
+        """The handles of `kind`, one per entry of `batches`: "search" (the sampled and greedy searches' batch), "replay" (the winners of a
+        PauliGym search, replayed with the solution log on) or "beam" (the two batches of targets * width envs that take turns as source and
+        destination of the per-step copy, and the winners, all three with the same constructor arguments: the rule of `copy_envs`; no layout
+        choice depends on the batch size).  One batch shape at a time per kind: the handles own device memory."""
+        key = (*batches, perms)  # add_perms: twists() only, the env steps alike
+        held = self._held.get(kind)
+        if held is not None and held.key != key:
+            del self._held[kind]
+            for v in held.vecs:
+                v.close()
+            held = None
+        if held is None:
+            held = self._held[kind] = _Handles(key, tuple(self.env.vec(b, device=self.device, add_inverts=False, add_perms=perms,
+                                                                       track_solution=kind != "search") for b in batches))
+            self._policy = self._policy.to(device=held.vecs[0].device, dtype=self.dtype)
+        return held
+
+    def _snapshot(self) -> _Packed:
+        """The packed operands of the weights as they are now: after an in-place update everything packed before is dropped first."""
+        pol = self._policy
+        at = tuple((id(p), p._version) for p in pol.parameters())
+        if self._packed is None or self._packed.at != at:
+            self._packed = None
+            for held in self._held.values():
+                held.first.clear()
             w, b, A = pol.fused_heads()
-            self._packed_tail = (pol.embeddings.bias.detach().float().contiguous(), pack_mid(pol.common.weight, pol.common.bias),
-                                 pack_head(w, b, A, A, after_mid=True))
-        return self._packed_tail
+            self._packed = _Packed(at, pol.embeddings.bias.detach().float().contiguous(), pack_mid(pol.common.weight, pol.common.bias),
+                                   pack_head(w, b, A, A, after_mid=True))
+        return self._packed
 
-    def _view_kernels(self, vec: VecEnv):
-        """Operands of the policy-layer kernels for a search under twists, in the form of `_kernels`: the first layer is `embed_words` on
+    def _first_layer(self, vec: VecEnv, kept: Dict[VecEnv, _FirstLayer], views: bool) -> _FirstLayer:
+        """The first layer of the policy-layer kernels (qg_vec_embed / qg_policy_embed_words in front of qg_policy_mid_head_sample / _logp) for
+        `vec`, packed on first use: through the handle and kept in `kept`, its owner's `_Handles.first`; or, `views`, for `embed_words` on
         `observe_twisted_words`, whose row count is the env's rounded up to even -- the weight gets `cols` zero columns for the pad word.
-        ValueError where they do not apply."""
+        ValueError where the kernels do not apply: another policy class or shape, no TILE layout nor 64-bit row words, a view too wide."""
         pol = self._policy
         if not isinstance(pol, BasicPolicy):
-            raise ValueError(self._NO_TWIST_KERNELS)
-        self._weights_current()
-        if self._packed_views is None:
-            rows, cols = vec.obs_shape_
-            try:
-                if cols > 64 or vec.packed_words_per_env != rows:
-                    raise ValueError("a row of the view is one 64-bit word")
-                w = pol.embeddings.weight.detach()
-                if rows % 2:
-                    w = torch.nn.functional.pad(w, (0, cols))
-                self._packed_views = (pack_embed_words(w, rows + rows % 2, cols), *self._tail())
-            except (ValueError, KeyError, _lib.QGymError) as e:
-                raise ValueError(f"{self._NO_TWIST_KERNELS} ({e})") from None
-        return (vec, *self._packed_views, True)
-
-    def _kernels(self, vec: VecEnv):
-        """Operands of the two policy-layer kernels (qg_vec_embed, qg_policy_mid_head_sample / _logp: bf16 products, f32 accumulation) when the
-        policy has the default shape and the env a TILE layout or 64-bit observation words; None otherwise (the torch forward is used)."""
-        pol = self._policy
-        if not isinstance(pol, BasicPolicy):
-            return None
-        self._weights_current()
-        hit = self._packed.get(id(vec))
-        if hit is not None and hit[0] is vec:
-            return hit
-        packed = None
+            raise ValueError(self._NO_TWIST_KERNELS if views else self._NO_KERNELS)
+        # as the two builders this one replaces: a weight dtype the packers do not take (KeyError) is an error of its own on the handle routes
+        caught = (ValueError, KeyError, _lib.QGymError) if views else (ValueError, _lib.QGymError)
         try:
+            packed = self._snapshot()
+            if views:
+                if packed.views is None:
+                    rows, cols = vec.obs_shape_
+                    if cols > 64 or vec.packed_words_per_env != rows:
+                        raise ValueError("a row of the view is one 64-bit word")
+                    w = pol.embeddings.weight.detach()
+                    if rows % 2:
+                        w = torch.nn.functional.pad(w, (0, cols))
+                    packed.views = _FirstLayer("views", pack_embed_words(w, rows + rows % 2, cols))
+                return packed.views
+            if vec not in kept:
+                try:
+                    kept[vec] = _FirstLayer("state", pack_embedding(vec, pol.embeddings.weight))
+                except (ValueError, _lib.QGymError):
+                    if vec.packed_word_bytes != 8 or vec.packed_words_per_env != vec.obs_shape_[0]:
+                        raise
+                    kept[vec] = _FirstLayer("words", pack_embed_words(pol.embeddings.weight, *vec.obs_shape_))
+            return kept[vec]
+        except caught as e:
+            raise ValueError(f"{self._NO_TWIST_KERNELS} ({e})" if views else self._NO_KERNELS) from None
+
+    def _forward(self, held: _Handles, readers: int, tw: Optional[torch.Tensor], kernels: Optional[bool], rows: bool = False) -> _Forward:
+        """The forward object of one search on the first `readers` handles of `held`, under the views `tw` if any.  `kernels` True: the
+        policy-layer kernels, or ValueError where they do not apply; None: the kernels where they apply, else torch; False: torch.
+        `rows`: the search asks for `logp`."""
+        if kernels is not False:
             try:
-                first = pack_embedding(vec, pol.embeddings.weight)  # TILE layout: the first layer reads the resident state
-                words = False
-            except (ValueError, _lib.QGymError):
-                if vec.packed_word_bytes != 8 or vec.packed_words_per_env != vec.obs_shape_[0]:
+                first = {v: self._first_layer(v, held.first, tw is not None) for v in held.vecs[:readers]}
+            except ValueError:
+                if kernels:
                     raise
-                first = pack_embed_words(pol.embeddings.weight, *vec.obs_shape_)  # 64-bit row words (PauliEnv, wide CliffordEnv): qg_policy_embed_words
-                words = True
-            packed = (vec, first, *self._tail(), words)
-        except (ValueError, _lib.QGymError):
-            packed = None
-        if packed is not None:
-            self._packed[id(vec)] = packed
-        return packed
-
-    def _close(self, vec: VecEnv):
-        self._packed.pop(id(vec), None)
-        vec.close()
-
-    def _words_buf(self, vec: VecEnv, kern, tw: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        """Where the words route of `_first_layer` keeps its packed observation (None for the resident-state route)."""
-        if not kern[5]:
-            return None
-        rows = vec.obs_shape_[0] + vec.obs_shape_[0] % 2 if tw is not None else vec.packed_words_per_env
-        return torch.empty((vec.batch, rows), dtype=torch.int64, device=vec.device)
-
-    def _first_layer(self, vec: VecEnv, kern, h1: torch.Tensor, words_buf: Optional[torch.Tensor], tw: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """relu(obs W1^T + b1) of the handle's current state into `h1` (bf16), from the resident bits or the packed observation words; under
-        twists (`tw`, operands of `_view_kernels`) from the words of every env's view."""
-        if tw is not None:
-            words = vec.observe_twisted_words(tw, words_buf.shape[1], out=words_buf)
-            return embed_words(words, vec.obs_shape_[1], kern[1], kern[2], h1.shape[1], relu=True, out=h1)
-        if kern[5]:
-            return embed_words(vec.observe_packed(out=words_buf), vec.obs_shape_[1], kern[1], kern[2], h1.shape[1], relu=True, out=h1)
-        return embed(vec, kern[1], kern[2], h1.shape[1], relu=True, out=h1)
-
-    def _vec(self, batch: int, track_solution: bool, perms: bool = False) -> VecEnv:
-        key = (batch, track_solution, True) if perms else (batch, track_solution)  # add_perms: twists() only, the env steps alike
-        if key not in self._vecs:
-            for k in [k for k in self._vecs if k[1] == track_solution]:  # one batch size at a time: the handles own device memory
-                self._close(self._vecs.pop(k))
-            self._vecs[key] = self.env.vec(batch, device=self.device, add_inverts=False, add_perms=perms, track_solution=track_solution)
-            self._policy = self._policy.to(device=self._vecs[key].device, dtype=self.dtype)
-        return self._vecs[key]
-
-    def _observe(self, vec: VecEnv, tw: Optional[torch.Tensor]) -> torch.Tensor:
-        """What the policy reads, in its dtype: the observation, or under twists env e through twist tw[e].  A dtype the library does not
-        write (float64) is written as float32 and widened: the entries are 0 and 1."""
-        dt = self.dtype if self.dtype in VecEnv._DTYPES else torch.float32
-        x = vec.observe_as(dt) if tw is None else vec.observe_twisted(tw, dt)
-        return x if dt == self.dtype else x.to(self.dtype)
+            else:
+                return _KernelForward(self._snapshot(), first, self._policy, self.seed, tw, rows)
+        return _TorchForward(self._policy, self.dtype, self.seed, tw)
 
     def _load(self, vec: VecEnv, states: Sequence[Sequence[int]], repeat: int):
         if vec.env_kind == "pauli":
@@ -200,19 +303,6 @@ class BatchedSynthesis:
         else:
             vec.set_state(np.repeat(np.asarray(states, dtype=np.int64), repeat, axis=0), fmt="i64")
 
-    def _beam_vecs(self, M: int, W: int, perms: bool = False):
-        """The beam search's handles: two batches of M * W envs that take turns as source and destination of the per-step copy, and the M
-        winners.  All three have the same constructor arguments (the rule of `copy_envs`; no layout choice depends on the batch size)."""
-        key = (M, W, True) if perms else (M, W)
-        if self._beam is None or self._beam[0] != key:
-            if self._beam is not None:
-                for v in self._beam[1]:
-                    self._close(v)
-            mk = lambda batch: self.env.vec(batch, device=self.device, add_inverts=False, add_perms=perms, track_solution=True)  # noqa: E731
-            self._beam = (key, (mk(M * W), mk(M * W), mk(M)))
-            self._policy = self._policy.to(device=self._beam[1][0].device, dtype=self.dtype)
-        return self._beam[1]
-
     def _views(self, V: int) -> List[int]:
         """Twist index of each of a target's views: view 0 is the untwisted one (-1: no such twist, `observe_twisted` and `untwist_actions`
         pass through), then the env's non-identity twists -- those that move an observation entry -- in `twists()` order; at most V of them."""
@@ -223,46 +313,20 @@ class BatchedSynthesis:
             self._view_list = [-1] + [t for t, p in enumerate(obs_perms) if p != list(range(len(p)))]
         return self._view_list[:V]
 
-    def _solve_beam(self, states: Sequence[Sequence[int]], W: int, merge: bool = False, twists: Optional[int] = None,
-                    fast: bool = False, twist_kernels: bool = False) -> List[Optional[List[int]]]:
-        if twists is not None:
-            return self._solve_beam_views(states, W, merge, twists, twist_kernels)
-        M = len(states)
-        cur, oth, win = self._beam_vecs(M, W)
-        return self._beam_search(states, 1, None, W, merge, cur, oth, win, fast)
+    def _twist_index(self, views: List[int], groups: int, M: int, width: Optional[int], dev) -> torch.Tensor:
+        """Every env's twist index, int32 [B]: per target `groups` consecutive groups, group g under view g mod V.  Sampled and greedy
+        searches: a group is one search (`width` None), env m * S + s sees view s mod V.  Beam search: V groups of `width` beams, env b is in
+        group b // W under view (b // W) % V."""
+        tw = torch.tensor([views[g % len(views)] for g in range(groups)], dtype=torch.int32, device=dev).repeat(M)
+        return (tw if width is None else tw.repeat_interleave(width)).contiguous()
 
-    def _solve_beam_views(self, states, W: int, merge: bool, twists: int, twist_kernels: bool = False) -> List[Optional[List[int]]]:
-        """Beam search under V views per target: the groups are the (target, view) pairs, each searched under its own fixed view (and with
-        its own merge history); a target's winner is the best result of its V groups, ties to the lowest view."""
-        M = len(states)
-        views = self._views(int(twists))
-        V = len(views)
-        cur, oth, win = self._beam_vecs(M * V, W, True)
-        tw = torch.tensor(views, dtype=torch.int32, device=cur.device).repeat(M).repeat_interleave(W).contiguous()  # env b: group b // W, view (b // W) % V
-        return self._beam_search(states, V, tw, W, merge, cur, oth, win, view_kernels=twist_kernels)
-
-    def _beam_search(self, states, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv, fast: bool = False,
-                     view_kernels: bool = False):
-        """`tw` None: the search of `solve(beam_width=W)`.  Else int32 [B]: every env's twist index; there are V consecutive groups per target.
-        `fast`: the log-probabilities come from the policy-layer kernels (`tw` is None then); `view_kernels`: the same under `tw`, the first
-        layer reading the views as packed words."""
+    def _beam_search(self, states, fwd: _Forward, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv):
+        """The search of `solve(beam_width=W)`: `cur` and `oth` take turns, `fwd` reads whichever is current.  `tw` None: V is 1.  Else the
+        groups are the (target, view) pairs, V consecutive ones per target, each searched under its own fixed view (and with its own merge
+        history); a target's winner is the best result of its V groups, ties to the lowest view."""
         targets = len(states)
         M = targets * V  # groups
         B, A, dev = cur.batch, cur.num_actions(), cur.device
-        kern = None
-        if fast or view_kernels:  # the two search handles take turns: each has its own packed first layer (packed through the handle), the rest is shared
-            if view_kernels:
-                kern = {id(v): self._view_kernels(v) for v in (cur, oth)}
-            else:
-                kern = {id(v): self._kernels(v) for v in (cur, oth)}
-            if any(k is None for k in kern.values()):
-                raise ValueError(self._NO_KERNELS)
-            pol = self._policy
-            h1 = torch.empty((B, pol.embeddings.out_features), dtype=torch.bfloat16, device=dev)
-            rows = torch.empty((B, (A + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :A]  # 16-byte row stride: 16-byte stores
-            top = torch.empty(B, dtype=torch.int32, device=dev)  # the kernel's other outputs: not used by the search
-            scratch = torch.empty((3, B), dtype=torch.float32, device=dev)
-            words_buf = self._words_buf(cur, kern[id(cur)], tw)
         T = int(cur._cfg.max_depth)
         self._load(win, states, V)  # the targets once per group; a group nobody solves keeps its slot, a solved one is overwritten by its winner
         group = torch.arange(M, dtype=torch.int32, device=dev)
@@ -282,23 +346,14 @@ class BatchedSynthesis:
             words = cur.observe_packed()
             live = beam_merge(words, cum, live, W, seen, cap)
         for t in range(T):
-            if kern is not None:  # first layer from the bits, then middle layer + head + log-softmax in one kernel: no logits in memory
-                k = kern[id(cur)]
-                logp = mid_head_logp(self._first_layer(cur, k, h1, words_buf, tw), k[3], pol.common.out_features, k[4], A, logp_rows=rows, actions=top,
-                                     best_logp=scratch[0], entropy=scratch[1], values=scratch[2])[0]
-            else:
-                logits = self._policy(self._observe(cur, tw))[0]
-                logp = torch.log_softmax(logits.float(), dim=1)
-            parent, act, cum, live = beam_select(logp, cum, live, W, A)
-            if tw is not None:  # chosen on the view: the real action (a child lives in its parent's group, hence under its view)
-                cur.untwist_actions(act, tw, out=act)
+            parent, act, cum, live = beam_select(fwd.logp(cur), cum, live, W, A)
+            fwd.real_actions(cur, act)  # a child lives in its parent's group, hence under its view
             oth.copy_envs(cur, parent)
             oth.step(act)
             ret = ret[parent.long()] + oth.reward  # the return `solve` ranks by: the parent's plus this step's reward
             solved = (live.bool() & oth.success.bool()).view(M, W)
             live = live & (1 - oth.done)
-            score = torch.where(solved, ret.view(M, W), torch.full((M, W), -float("inf"), device=dev))
-            j = score.argmax(dim=1)  # the first of equal maxima: the lowest slot
+            score, j = _winner(solved, ret.view(M, W))  # the lowest slot among equals
             val = score.gather(1, j.view(M, 1)).view(M)
             better = val > best
             win.copy_envs(oth, torch.where(better, group * W + j.to(torch.int32), nowhere))
@@ -313,8 +368,8 @@ class BatchedSynthesis:
         for v in (cur, oth, win):
             v.sync()
         sols, lens = win.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
-        if tw is not None:  # per target the best of its V groups; argmax takes the first of equal maxima: the lowest view
-            pick = (torch.arange(targets, device=dev) * V + best.view(targets, V).argmax(dim=1)).cpu().numpy()
+        if tw is not None:  # per target the best of its V groups, the lowest view among equals
+            pick = (torch.arange(targets, device=dev) * V + _winner(found.view(targets, V), best.view(targets, V))[1]).cpu().numpy()
             ok = found.cpu().numpy()[pick]
             sols, lens = sols[pick], lens[pick]
         else:
@@ -322,7 +377,7 @@ class BatchedSynthesis:
         out = [[int(x) for x in sols[m, : lens[m]]] if ok[m] else None for m in range(targets)]
         gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
         self.last_stats = {"beam_width": W, "targets": targets, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0}
-        if kern is not None:
+        if fwd.kernels:
             self.last_stats["kernels"] = True
         if tw is not None:
             self.last_stats["views"] = V
@@ -401,20 +456,24 @@ class BatchedSynthesis:
                 raise ValueError("beam_width must be at least 1")
             if merge_duplicates and self.env.env_kind == "pauli":
                 raise ValueError("merge_duplicates: a PauliGym observation does not determine its state (rotations beyond the observed columns, DAG order)")
-            return self._solve_beam(states, int(beam_width), bool(merge_duplicates), twists, fast is True, bool(twist_kernels))
-        if merge_duplicates:
+        elif merge_duplicates:
             raise ValueError("merge_duplicates needs beam_width")
+        views = None if twists is None else self._views(int(twists))
+        V = 1 if views is None else len(views)
+        if beam_width is not None:
+            W = int(beam_width)
+            held = self._handles("beam", (M * V * W, M * V * W, M * V), views is not None)
+            cur, oth, win = held.vecs
+            tw = None if views is None else self._twist_index(views, V, M, W, cur.device)
+            fwd = self._forward(held, 2, tw, bool(twist_kernels) or fast is True, rows=True)  # on request only: the kernels or a ValueError
+            return self._beam_search(states, fwd, V, tw, W, bool(merge_duplicates), cur, oth, win)
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
-        tw = None
-        if twists is not None:
-            views = self._views(int(twists))
-            if deterministic:
-                S = len(views)  # ... but for the view they are seen through
-            vec = self._vec(M * S, False, True)
-            tw = torch.tensor([views[s % len(views)] for s in range(S)], dtype=torch.int32, device=vec.device).repeat(M).contiguous()  # env m * S + s: view s mod V
-        else:
-            vec = self._vec(M * S, False)
+        if views is not None and deterministic:
+            S = V  # ... but for the view they are seen through
+        held = self._handles("search", (M * S,), views is not None)
+        vec = held.vecs[0]
         B, A, dev = vec.batch, vec.num_actions(), vec.device
+        tw = None if views is None else self._twist_index(views, S, M, None, dev)
         self._load(vec, states, S)
         T = int(vec._cfg.max_depth)
         actions = torch.empty((T, B), dtype=torch.int32, device=dev)
@@ -423,38 +482,17 @@ class BatchedSynthesis:
         ret = torch.zeros(B, dtype=torch.float32, device=dev)
         parked = torch.full((B,), A, dtype=torch.int32, device=dev)  # out of range: no gate (clifford.rs:324)
         steps = 0
-        kern = None
-        if twist_kernels:
-            kern = self._view_kernels(vec)
-        elif tw is None and fast is not False and (fast or (not deterministic and B >= 4096)):  # greedy: on request only
-            kern = self._kernels(vec)
-            if fast and kern is None:
-                raise ValueError(self._NO_KERNELS)
-        if kern is not None:
-            pol = self._policy
-            h1 = torch.empty((B, pol.embeddings.out_features), dtype=torch.bfloat16, device=dev)
-            act = torch.empty(B, dtype=torch.int32, device=dev)
-            scratch = torch.empty((3, B), dtype=torch.float32, device=dev)
-            words_buf = self._words_buf(vec, kern, tw)
-        self.last_stats = {"kernels": kern is not None}
+        if twist_kernels or fast:
+            kernels = True
+        elif tw is None and fast is not False and not deterministic and B >= 4096:  # fast=None: where the kernels apply; greedy: on request only
+            kernels = None
+        else:
+            kernels = False
+        fwd = self._forward(held, 1, tw, kernels)
+        choose = (lambda t: fwd.greedy(vec)) if deterministic else (lambda t: fwd.draw(vec, t))
+        self.last_stats = {"kernels": fwd.kernels}
         for t in range(T):
-            if kern is not None:
-                self._first_layer(vec, kern, h1, words_buf, tw)
-                if deterministic:  # the arg-max alone: no row is written
-                    mid_head_logp(h1, kern[3], pol.common.out_features, kern[4], A, want_rows=False, actions=act, best_logp=scratch[0], entropy=scratch[1],
-                                  values=scratch[2])
-                else:
-                    mid_head_sample(h1, kern[3], pol.common.out_features, kern[4], A, self.seed, t, actions=act, logp=scratch[0], entropy=scratch[1],
-                                    values=scratch[2])
-            else:
-                x = self._observe(vec, tw)
-                logits = self._policy(x)[0]
-                if deterministic:
-                    act = logits.argmax(dim=1).to(torch.int32)
-                else:
-                    act = sample_actions(logits.contiguous(), self.seed, t)[0].to(torch.int32)
-            if tw is not None:  # chosen on the view: the real action
-                vec.untwist_actions(act, tw, out=act)
+            act = fwd.real_actions(vec, choose(t))
             actions[t] = torch.where(finished, parked, act)
             vec.step(actions[t])
             live = ~finished
@@ -466,8 +504,7 @@ class BatchedSynthesis:
                 break
         vec.sync()
         ok = (solved_at >= 0).view(M, S)
-        score = torch.where(ok, ret.view(M, S), torch.full((M, S), -float("inf"), device=dev))
-        best = score.argmax(dim=1)
+        best = _winner(ok, ret.view(M, S))[1]
         idx = torch.arange(M, device=dev) * S + best
         lengths = solved_at[idx].cpu().numpy()
         found = ok.any(dim=1).cpu().numpy()
@@ -475,12 +512,12 @@ class BatchedSynthesis:
         self.last_stats.update({"targets": M, "searches": S, "steps": steps, "solved": int(found.sum()),
                            "searches_solved": float(ok.float().mean()), "mean_gates": float(lengths[found].mean()) if found.any() else 0.0})
         if tw is not None:
-            self.last_stats["views"] = len(views)
+            self.last_stats["views"] = V
         if vec.env_kind != "pauli":
             w = win.cpu().numpy()
             return [w[m, : lengths[m]].tolist() if found[m] else None for m in range(M)]
         # PauliEnv: replay the winners with the solution log on; padding entries (no gate, no marker) are dropped
-        rep = self._vec(M, True)
+        rep = self._handles("replay", (M,)).vecs[0]
         self._load(rep, states, 1)
         keep = torch.arange(steps, device=dev).view(1, -1) < solved_at[idx].view(-1, 1)
         rep.rollout(torch.where(keep, win, torch.full_like(win, A)).t().contiguous())

@@ -172,10 +172,14 @@ def test_the_two_search_handles_pack_the_same_first_layer():
     c = case()
     syn = c["syn"]
     syn.solve(c["tg"][:8], beam_width=2, fast=True)
-    cur, oth, _ = syn._beam[1]
-    a, b = syn._kernels(cur), syn._kernels(oth)
-    assert a[0] is cur and b[0] is oth and a[1] is not b[1] and torch.equal(a[1], b[1])
-    assert a[3] is b[3] and a[4] is b[4]
+    cur, oth, _ = syn._beam.vecs
+    a, b = syn._beam.first[cur], syn._beam.first[oth]
+    assert set(syn._beam.first) == {cur, oth} and a.route == b.route == "state"
+    assert a.weight is not b.weight and torch.equal(a.weight, b.weight)
+    before = (syn._packed.mid, syn._packed.head)
+    syn.solve(c["tg"][:8], beam_width=2, fast=True)  # both handles again: the same first layers, and the one middle layer and head
+    assert syn._beam.first[cur] is a and syn._beam.first[oth] is b
+    assert syn._packed.mid is before[0] and syn._packed.head is before[1]
 
 
 def test_an_in_place_weight_update_reaches_every_packed_layer():
@@ -222,7 +226,7 @@ def test_pauli_beam_on_the_kernels():
     syn = BatchedSynthesis(gym, policy, seed=1)
     sols = syn.solve(states, beam_width=2, fast=True)
     assert syn.last_stats["kernels"] is True
-    assert syn._kernels(syn._beam[1][0])[5]  # the words route
+    assert syn._beam.first[syn._beam.vecs[0]].route == "words"
     assert syn.solve(states, beam_width=2, fast=True) == sols
     okw = oracle_kwargs(gym)
     for m, sol in enumerate(sols):

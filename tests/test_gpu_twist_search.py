@@ -161,4 +161,4 @@ def test_twist_kernels_argument_errors():
 
     wide = BatchedSynthesis(syn.env, BasicPolicy(4 * 66, 8).cuda(), seed=1)
     with pytest.raises(ValueError, match="twist_kernels=True needs"):
-        wide._view_kernels(types.SimpleNamespace(obs_shape_=(4, 66), packed_words_per_env=4))
+        wide._first_layer(types.SimpleNamespace(obs_shape_=(4, 66), packed_words_per_env=4), {}, views=True)
