@@ -434,6 +434,10 @@ __device__ inline uint32_t lower_half_on_both(uint32_t v) { return __builtin_amd
 // a ^ (b & c) as ONE v_bitop3_b32 (gfx950; truth table from a = 0xF0, b = 0xCC, c = 0xAA).  The scramble chains and the GF(2) products below are
 // bound by their instruction count (a lone wave issues one instruction every ~5 cycles), and this pair is most of what they do
 __device__ inline uint32_t xor_and(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x78); }
+// ... (m & a) | (~m & b), v_bfi_b32's function, and (a ^ b) | c, each as ONE instruction (the same table: 0xCA, 0xBE): the one-step kernel's selects,
+// merges and "differs from the identity" tests (qm_step1.hpp)
+__device__ inline uint32_t bit_select(uint32_t m, uint32_t a, uint32_t b) { return __builtin_amdgcn_bitop3_b32(m, a, b, 0xCA); }
+__device__ inline uint32_t xor_or(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0xBE); }
 template <int R>
 __device__ inline uint32_t gf2_cols_product_halves(const uint32_t *a_cols, uint32_t b, uint32_t half) {
     constexpr int H = (R + 1) / 2;

@@ -1069,7 +1069,7 @@ __global__ __launch_bounds__(256) void qm_reset_step_kernel(ResetStepArgs ra) {
         if (env < a.B && !((resets >> (env & 63u)) & 1ull)) {
             // (the dense rows are written by lane pairs: a lane whose neighbour is being reset writes its rows alone)
             const bool alone = D16 != 0 && ((resets >> ((env ^ 1ull) & 63u)) & 1ull);
-            fin = qm_step1_body<HAS_Z, FEAT, D16>(step1_front(a), a, Rows::G, env, nullptr, alone);
+            fin = qm_step1_body<HAS_Z, FEAT, D16, false, true>(step1_front(a), a, Rows::G, env, nullptr, alone);  // (PLAIN_BACK: qm_step1.hpp)
         }
         done_mask_store(a.done_mask, a.B, fin, env, a.done_epoch);  // (an env being reset: bit clear -- if it is final again after its first step the reset's lane appends it to the list)
         return;
@@ -1077,7 +1077,7 @@ __global__ __launch_bounds__(256) void qm_reset_step_kernel(ResetStepArgs ra) {
     // (plain configuration: the tree's wave takes the env's first step on the rows it holds -- qm_init_finish_wave_step; otherwise the lane
     // that has just written the env's fresh episode -- state, depth, bad mask, log lengths -- takes it, as qm_step1_body)
     qm_init_block<NXP, HAS_Z, false, 1>(ra.reset, role_index, WAVE ? &a : nullptr, [&](uint64_t env, bool stepped, bool fin) {
-        if (!stepped) fin = qm_step1_body<HAS_Z, FEAT, D16>(step1_front(a), a, Rows::G, env, nullptr, true);
+        if (!stepped) fin = qm_step1_body<HAS_Z, FEAT, D16, false, true>(step1_front(a), a, Rows::G, env, nullptr, true);
         if (fin) {  // (rare: one atomic per env that is final again after its first step)
             const uint32_t slot = atomicAdd(a.done_count, 1u);
             if (slot < a.B) a.done_list[slot] = (uint32_t)env;

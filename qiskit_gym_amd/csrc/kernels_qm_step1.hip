@@ -24,6 +24,13 @@ constexpr uint32_t QM_STEP1_BLOCK = 256;  // 64- and 128-thread blocks measured 
 // loads are issued without a scalar load in front of them; the rest of StepArgs follows by value and is fetched while those loads fly (one batch,
 // waited for where the gate entry is consumed: a cold scalar line must not surface between the rows and the stores).  On firmware
 // that does not preload, the compiler's compatibility prologue loads the same SGPRs first: correct, without the gain.
+// Between those waits a lone wave pays every instruction (1.3-3 ns each: EXPERIMENTS.md round 7, round 2's issue microbenchmark), so the body keeps
+// them few where nothing hides them: the gate word is decoded into 0 / -1 lane masks while the row loads fly, the rows go through one v_bitop3_b32 per select, merge and
+// term of the 4x4 GF(2) map, `bad` is updated by shifts, "no gate" takes no branch, and what depends on the env's index alone (its place in the
+// tile, the output addresses) is computed under the first loads and under the gate entry's.  The headline instantiation
+// <16, true, false, false, false>: first row wait -> last output store 143 -> 68 instructions, gate entry's arrival -> row loads 28 -> 12,
+// 269 -> 216 in all (profiles/r07/qm_step1_listing.txt); 2.817 -> 2.677 us per step at B = 65 536, 1.41 -> 1.24 us on the kernel's own clock
+// (profiles/r07/NUMBERS.md).
 // LIST: also record the envs that finish, one bit each in StepArgs::done_mask (F_DONE_LIST; its own instantiation: the plain kernel's code stays as it is)
 // DENSE (qg_vec_track_dense, N == NXP, D % 16 == 0): the rows the gate rewrote also go to the resident dense int8 observation
 template <int NXP, bool HAS_Z, bool FEAT, bool LIST = false, bool DENSE = false>

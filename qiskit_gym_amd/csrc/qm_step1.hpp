@@ -51,9 +51,79 @@ __device__ inline Step1Front step1_front(const StepArgs &a) { return Step1Front{
 // QG_STEP1_ABLATE (development, tools/build_variant.sh; EXPERIMENTS.md round 6) puts one avoidable round trip back: bit 0 -- the front in its old
 // order (action, then depth and bad, then the gate entry behind the in_range branch), bit 1 -- a wait for the row stores in front of the output
 // stores, bit 2 -- blockDim.x instead of the constant block size (kernels_qm_step1.hip)
+// Round 7 (EXPERIMENTS.md): bit 3 -- the gate's arithmetic as the compiler makes it from selects and compares (and the "no gate" branch around the
+// rows), bit 4 -- the tile base and the output addresses wherever the compiler computes them (and the gate entry's load behind its branch),
+// bit 5 -- the kernel clock's record count fetched at the kernel's end (below, beside the pinned statement).  Bits 3 and 4 each undo two things that
+// only work together -- the masks need the rows' wait in one block with their decode, the early addresses need the gate entry's load outside a
+// branch -- so a variant measures the pair
 #ifndef QG_STEP1_ABLATE
 #define QG_STEP1_ABLATE 0
 #endif
+
+// The gate word decoded into full-word 0 / -1 masks, and the two qubits' rows moved through them with one instruction per select and per term:
+// bit_select (v_bfi_b32 / v_bitop3_b32) and xor_and (v_bitop3_b32, device_common.hpp).  The masks depend on the gate entry alone: qm_step1_body
+// computes them while the row loads fly.  Written with the builtins on purpose -- from plain mask arithmetic the compiler goes back to
+// v_and -> v_cmp_ne -> v_cndmask -> v_xor per term, three to four instructions each, all behind the rows' arrival.
+// An address that went through an integer or an `asm` operand has lost its address space: dereferenced as it is it becomes a flat_ instruction
+// (slower, and counted with the scalar loads).  These put it back.
+template <class T>
+using global_ptr = __attribute__((address_space(1))) T *;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ inline uint4 global_load4(const uint4 *p) {
+    const u32x4 v = *(global_ptr<const u32x4>)p;
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ inline void global_store4(uint4 *p, const uint4 &v) { *(global_ptr<u32x4>)p = u32x4{v.x, v.y, v.z, v.w}; }
+template <class T>
+__device__ inline void global_store(uintptr_t at, T v) { *(global_ptr<T>)at = v; }
+
+__device__ inline uint32_t gate_bit_mask(uint32_t ops, uint32_t bit) { return (uint32_t)__builtin_amdgcn_sbfe((int32_t)ops, bit, 1u); }  // v_bfe_i32
+template <bool HAS_Z>
+struct GateMasks {
+    uint32_t m[16];   // m[4 k + i]: matrix bit M[k][i], in = {x0, z0, x1, z1}
+    uint32_t o0, o1;  // the qubit's parity (HAS_Z: which half of its group; else bit 0 of its place among the group's four rows)
+    uint32_t h0, h1;  // !HAS_Z: bit 1 of that place
+    uint32_t same;    // both qubits in one group
+    __device__ inline GateMasks(uint32_t ops, uint32_t g0, uint32_t g1) {
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) m[i] = gate_bit_mask(ops, 10u + i);
+        o0 = gate_bit_mask(ops, 0u); o1 = gate_bit_mask(ops, 5u);
+        h0 = HAS_Z ? 0u : gate_bit_mask(ops, 1u); h1 = HAS_Z ? 0u : gate_bit_mask(ops, 6u);
+        same = 0u - (uint32_t)(g0 == g1);
+    }
+    __device__ inline void pin() {  // (compiler only: the masks are values in registers from here on, not expressions to be folded into their uses)
+        asm volatile("" : "+v"(m[0]), "+v"(m[1]), "+v"(m[2]), "+v"(m[3]), "+v"(m[4]), "+v"(m[5]), "+v"(m[6]), "+v"(m[7]), "+v"(m[8]), "+v"(m[9]),
+                          "+v"(m[10]), "+v"(m[11]), "+v"(m[12]), "+v"(m[13]), "+v"(m[14]), "+v"(m[15]));
+        asm volatile("" : "+v"(o0), "+v"(o1), "+v"(h0), "+v"(h1), "+v"(same));
+    }
+    __device__ inline uint32_t get(const uint4 &u, uint32_t o, uint32_t h, uint32_t &z) const {
+        if constexpr (HAS_Z) {  // {X[2g], Z[2g], X[2g+1], Z[2g+1]}
+            z = bit_select(o, u.w, u.y);
+            return bit_select(o, u.z, u.x);
+        } else {                // rows 4g .. 4g+3
+            z = 0u;
+            return bit_select(h, bit_select(o, u.w, u.z), bit_select(o, u.y, u.x));
+        }
+    }
+    __device__ inline uint32_t mix(uint32_t k, uint32_t x0, uint32_t z0, uint32_t x1, uint32_t z1) const {  // out_k = xor_i M[k][i] * in_i
+        uint32_t o = m[4 * k] & x0;
+        if constexpr (HAS_Z) o = xor_and(o, m[4 * k + 1], z0);
+        o = xor_and(o, m[4 * k + 2], x1);
+        if constexpr (HAS_Z) o = xor_and(o, m[4 * k + 3], z1);
+        return o;
+    }
+};
+// ... the put-back: `e` = the qubit's parity mask (HAS_Z) / its four place masks
+template <bool HAS_Z>
+__device__ inline void gate_put(uint4 &u, const uint32_t (&e)[4], uint32_t x, uint32_t z) {
+    if constexpr (HAS_Z) {
+        u.x = bit_select(e[0], u.x, x); u.y = bit_select(e[0], u.y, z);
+        u.z = bit_select(e[0], x, u.z); u.w = bit_select(e[0], z, u.w);
+    } else {
+        u.x = bit_select(e[0], x, u.x); u.y = bit_select(e[1], x, u.y);
+        u.z = bit_select(e[2], x, u.z); u.w = bit_select(e[3], x, u.w);
+    }
+}
 
 // The env's action for the one-step kernels in two halves, so that no wait sits inside the width's branch: action_issue only chooses the load
 // instruction (a uniform branch on a flag that sits in an SGPR), action_value extends the sign behind whatever the caller issues in between --
@@ -89,10 +159,24 @@ __device__ inline int64_t action_value(int32_t lo, int32_t hi, bool act64) {
 // PLAIN_FRONT: the front and back as the compiler orders them by itself -- action, then depth and bad, then the gate entry behind the in_range branch,
 // nothing pinned.  The policy kernel (mid_head_sample_kernel) keeps it: it holds the action in a register, sits at its register limit, and the
 // pinned form costs two of its instantiations one VGPR more.
-template <bool HAS_Z, bool FEAT, int D16 = 0, bool PLAIN_FRONT = false>
+// PLAIN_BACK: the gate's arithmetic and the addresses as the compiler makes them from selects and compares, nothing computed ahead of its use
+// (the body before round 7).  The mask form keeps ~25 more values in registers across the rows' wait: the fused reset+step kernels
+// (qm_reset_step_kernel, whose reset workgroups share the SIMDs with these lanes) would drop from 7-8 waves per SIMD to 4-6 with it, so they keep this one.
+template <bool HAS_Z, bool FEAT, int D16 = 0, bool PLAIN_FRONT = false, bool PLAIN_BACK = PLAIN_FRONT>
 __device__ inline bool qm_step1_body(const Step1Front &f, const StepArgs &a, uint32_t G, uint64_t env, const int64_t *act_in, bool alone = false) {
+    static_assert(PLAIN_BACK || !PLAIN_FRONT, "the mask arithmetic is placed against the pinned front");
+    constexpr bool NEW_ALU = !PLAIN_BACK && !(QG_STEP1_ABLATE & 8), EARLY_ADDR = !PLAIN_BACK && !(QG_STEP1_ABLATE & (16 | 1));
     const uint32_t lane = (uint32_t)env & (QG_WAVE - 1);
     uint4 *tile = reinterpret_cast<uint4 *>(f.state) + (env >> 6) * (uint64_t)(G * 64);
+    uint4 *tile_lane = tile + lane;  // EARLY_ADDR: the env's place in its tile, in registers before the gate entry is there
+    auto group_at = [&](uint32_t grp) { return EARLY_ADDR ? tile_lane + grp * 64 : tile + (grp * 64 + lane); };
+    // the addresses of the five per-env outputs (as integers: the two sequence arrays may be null)
+    uintptr_t out_reward = 0, out_done = 0, out_success = 0, out_rseq = 0, out_dseq = 0;
+    auto output_addresses = [&] {
+        out_reward = reinterpret_cast<uintptr_t>(a.reward + env); out_done = reinterpret_cast<uintptr_t>(a.done + env);
+        out_success = reinterpret_cast<uintptr_t>(a.success + env);
+        out_rseq = reinterpret_cast<uintptr_t>(a.rewards_seq) + 4u * env; out_dseq = reinterpret_cast<uintptr_t>(a.dones_seq) + env;
+    };
     int64_t act;
     int32_t depth, sol_n;
     uint32_t bad0;
@@ -120,23 +204,101 @@ __device__ inline bool qm_step1_body(const Step1Front &f, const StepArgs &a, uin
         in_range = (uint64_t)act < (uint64_t)f.num_actions;
         if (in_range) g = f.gates[act];
 #else
+        // what depends on `env` alone is computed here, under these loads: the env's place in its tile now (`state` is a preloaded argument), the
+        // output addresses under the gate entry's load below -- not between the gate entry's arrival and the row loads, or in front of the stores
+        if constexpr (EARLY_ADDR) asm volatile("" : "+v"(tile_lane));
         __builtin_amdgcn_sched_barrier(0);  // (compiler only: the loads above are issued before anything uses the action -- the gate entry's load waits for it alone)
         act = act_in ? *act_in : action_value(act_lo, act_hi, f.flags & F_ACT64);
         in_range = (uint64_t)act < (uint64_t)f.num_actions;  // gateset.get(action) (clifford.rs:324): 0 <= act < num_actions
-        const GateEntry entry = f.gates[in_range ? act : 0];
-        if (in_range) g = entry;
+        if constexpr (EARLY_ADDR) {
+            uint32_t gi = in_range ? (uint32_t)act : 0u;
+            asm volatile("" : "+v"(gi));  // (compiler only: the load stays unconditional, in one block with what runs under it)
+            const GateEntry entry = f.gates[gi];
+            __builtin_amdgcn_sched_barrier(0);
+            output_addresses();
+            asm volatile("" : "+v"(out_reward), "+v"(out_done), "+v"(out_success), "+v"(out_rseq), "+v"(out_dseq));
+            if (in_range) g = entry;
+        } else {
+            const GateEntry entry = f.gates[in_range ? act : 0];
+            if (in_range) g = entry;
+        }
 #endif
         // the gate entry, depth and bad are all here: no later wait for a load.  The StepArgs fields the back of the chain reads are asked for here too:
         // their scalar loads are issued at the top, fly with the vector loads and have long arrived -- left alone the compiler fetches a field right
         // before its first use, a cold scalar line between the rows and the stores
         asm volatile("" : "+v"(g.ops), "+v"(g.penalty), "+v"(depth), "+v"(bad0)
                      : "s"(a.N), "s"(a.rewards_seq), "s"(a.dones_seq), "s"(a.reward), "s"(a.done), "s"(a.success));
+#if !(QG_STEP1_ABLATE & 32)  // ... and the kernel clock's record count: left alone it is a cold scalar load, waited for, in every wave's last instructions
+        if constexpr (!PLAIN_BACK) asm volatile("" : : "s"(a.kclk_waves));
+#endif
         depth = depth > 0 ? depth - 1 : 0;  // clifford.rs:342
     }
+    if constexpr (NEW_ALU && !EARLY_ADDR) output_addresses();
     uint32_t bad = bad0, fault = 0;
-    float penalty = 0.0f;
+    float penalty = 0.0f, r_solved = 0.0f, r_open = 0.0f;
+    uint32_t fin_open = 0;  // NEW_ALU: is_final of an env that is not solved
     uint32_t drow[4] = {0, 0, 0, 0}, dword[4] = {0, 0, 0, 0}, dchg = 0;  // D16: the rows the gate changed (bit k of dchg: entry k)
-    if (in_range) {
+    if constexpr (NEW_ALU) {
+        // No branch around the rows: "no gate" (an out-of-range action, a two-qubit gate on equal qubits) is the identity map on qubit 0 -- its rows are
+        // rewritten as they are and `bad` keeps its bit (`live`) -- so the chain from the gate entry to the stores is one block.  Between the issue of
+        // the row loads and their arrival: the masks, the identity patterns, the cleared `bad`.  Behind it: 4 selects, 16 terms, 12 merges (HAS_Z).
+        penalty = g.penalty;  // (out of range: 0)
+        const bool layered = FEAT && (f.flags & F_LAYERS) && in_range;
+        LayerTxn lt;
+        if (layered) lt = layers_begin(layer_rec(a.layers, env, 2 * a.N + 2), a.N, a.descs[act]);  // its loads fly with the state's
+        constexpr uint32_t gsh = HAS_Z ? 1u : 2u;
+        const uint32_t ops = g.ops, q0 = ops & 31u, q1 = (ops >> 5) & 31u, g0 = q0 >> gsh, g1 = q1 >> gsh;
+        uint4 *pa = group_at(g0), *pb = group_at(g1);
+        uint4 ua = global_load4(pa), ub = global_load4(pb);
+        __builtin_amdgcn_sched_barrier(0);  // (compiler only: everything down to the next one stands between the loads and their wait)
+        GateMasks<HAS_Z> gm(ops, g0, g1);
+        uint32_t e0[4], e1[4];  // the put-back's masks: gate_put
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            e0[k] = HAS_Z ? gm.o0 : 0u - (uint32_t)((q0 & 3u) == k);
+            e1[k] = HAS_Z ? gm.o1 : 0u - (uint32_t)((q1 & 3u) == k);
+        }
+        const uint32_t live = 0u - (uint32_t)(((ops >> 10) & 0xFFFFu) != QM_IDENTITY);
+        const uint32_t zb = 1u << a.N;
+        uint32_t ix0 = 1u << q0, ix1 = 1u << q1, iz0 = zb << q0, iz1 = zb << q1;  // the identity's rows of the two qubits
+        // `bad`: the two qubits' bits cleared here, set again behind the rows as min(difference, 1) << q -- no compare, no select.  "No gate" keeps
+        // both bits (`live`); q0's value wins when q0 == q1, as below
+        uint32_t set0 = live & 1u, set1 = set0 & (uint32_t)(q0 != q1);
+        uint32_t bad_rest = bad0 & ~((set0 << q0) | (set1 << q1));
+        r_solved = 1.0f - penalty; r_open = 0.0f - penalty;  // clifford.rs:345-346, both outcomes
+        fin_open = (uint32_t)(depth == 0);
+        const bool apart = g0 != g1;
+        gm.pin();
+        if constexpr (!HAS_Z) asm volatile("" : "+v"(e0[0]), "+v"(e0[1]), "+v"(e0[2]), "+v"(e0[3]), "+v"(e1[0]), "+v"(e1[1]), "+v"(e1[2]), "+v"(e1[3]));
+        asm volatile("" : "+v"(ix0), "+v"(ix1), "+v"(iz0), "+v"(iz1), "+v"(set0), "+v"(set1), "+v"(bad_rest), "+v"(r_solved), "+v"(r_open),
+                          "+v"(depth), "+v"(fin_open));
+        __builtin_amdgcn_sched_barrier(0);
+        uint32_t z0, z1;
+        const uint32_t x0 = gm.get(ua, gm.o0, gm.h0, z0), x1 = gm.get(ub, gm.o1, gm.h1, z1);
+        const uint32_t nx0 = gm.mix(0, x0, z0, x1, z1), nx1 = gm.mix(2, x0, z0, x1, z1);
+        const uint32_t nz0 = HAS_Z ? gm.mix(1, x0, z0, x1, z1) : 0u, nz1 = HAS_Z ? gm.mix(3, x0, z0, x1, z1) : 0u;
+        // q1's rows first, then q0's (q0's value wins when q0 == q1, as in qm_apply)
+        gate_put<HAS_Z>(ub, e1, nx1, nz1);
+        ua.x = bit_select(gm.same, ub.x, ua.x); ua.y = bit_select(gm.same, ub.y, ua.y);
+        ua.z = bit_select(gm.same, ub.z, ua.z); ua.w = bit_select(gm.same, ub.w, ua.w);
+        gate_put<HAS_Z>(ua, e0, nx0, nz0);
+        // (one group: q0's store carries q1's rows too.  Storing them twice, to spare this branch, measured 0.17 us per step SLOWER at 65 536 envs:
+        // 47 % of the line gateset's actions stay in one group, and the launch ends when its stores have drained -- EXPERIMENTS.md round 7)
+        if (apart) global_store4(pb, ub);
+        global_store4(pa, ua);
+        if constexpr (D16 > 0) {  // the rows that changed: stored below ("no gate" changes none)
+            drow[0] = q0; dword[0] = nx0; dchg |= (uint32_t)(nx0 != x0);
+            drow[1] = a.N + q0; dword[1] = nz0; dchg |= (uint32_t)(HAS_Z && nz0 != z0) << 1;
+            drow[2] = q1; dword[2] = nx1; dchg |= (uint32_t)(q1 != q0 && nx1 != x1) << 2;
+            drow[3] = a.N + q1; dword[3] = nz1; dchg |= (uint32_t)(HAS_Z && q1 != q0 && nz1 != z1) << 3;
+        }
+        const uint32_t d0 = HAS_Z ? xor_or(nx0, ix0, nz0 ^ iz0) : nx0 ^ ix0, d1 = HAS_Z ? xor_or(nx1, ix1, nz1 ^ iz1) : nx1 ^ ix1;
+        bad = bad_rest | (min(d0, set0) << q0) | (min(d1, set1) << q1);
+        if (layered) {
+            penalty = layers_commit(lt, a.w);
+            r_solved = 1.0f - penalty; r_open = 0.0f - penalty;
+        }
+    } else if (in_range) {
         penalty = g.penalty;
         const bool layered = FEAT && (f.flags & F_LAYERS);
         LayerTxn lt;
@@ -145,7 +307,7 @@ __device__ inline bool qm_step1_body(const Step1Front &f, const StepArgs &a, uin
         if (m != QM_IDENTITY) {  // "no gate" (e.g. a two-qubit gate on equal qubits) changes nothing
             constexpr uint32_t gsh = HAS_Z ? 1u : 2u;
             const uint32_t g0 = q0 >> gsh, g1 = q1 >> gsh;
-            const uint4 va = tile[g0 * 64 + lane], vb = tile[g1 * 64 + lane];
+            const uint4 va = EARLY_ADDR ? global_load4(group_at(g0)) : tile[g0 * 64 + lane], vb = EARLY_ADDR ? global_load4(group_at(g1)) : tile[g1 * 64 + lane];
             uint32_t ua[4] = {va.x, va.y, va.z, va.w}, ub[4] = {vb.x, vb.y, vb.z, vb.w};
             uint32_t x0, z0, x1, z1;
             qm_group_get<HAS_Z>(ua, q0, x0, z0);
@@ -163,8 +325,13 @@ __device__ inline bool qm_step1_body(const Step1Front &f, const StepArgs &a, uin
 #pragma unroll
             for (int k = 0; k < 4; ++k) ua[k] = same ? ub[k] : ua[k];
             qm_group_put<HAS_Z>(ua, q0, nx0, nz0);
-            if (!same) tile[g1 * 64 + lane] = make_uint4(ub[0], ub[1], ub[2], ub[3]);
-            tile[g0 * 64 + lane] = make_uint4(ua[0], ua[1], ua[2], ua[3]);
+            if constexpr (EARLY_ADDR) {
+                if (!same) global_store4(group_at(g1), make_uint4(ub[0], ub[1], ub[2], ub[3]));
+                global_store4(group_at(g0), make_uint4(ua[0], ua[1], ua[2], ua[3]));
+            } else {
+                if (!same) tile[g1 * 64 + lane] = make_uint4(ub[0], ub[1], ub[2], ub[3]);
+                tile[g0 * 64 + lane] = make_uint4(ua[0], ua[1], ua[2], ua[3]);
+            }
             if constexpr (D16 > 0) {  // the rows that changed (S rewrites one of a qubit's two rows, CX two of four, ...): stored below
                 drow[0] = q0; dword[0] = nx0; dchg |= (uint32_t)(nx0 != x0);
                 drow[1] = a.N + q0; dword[1] = nz0; dchg |= (uint32_t)(HAS_Z && nz0 != z0) << 1;
@@ -217,17 +384,32 @@ __device__ inline bool qm_step1_body(const Step1Front &f, const StepArgs &a, uin
     if constexpr (PLAIN_FRONT) depth = depth > 0 ? depth - 1 : 0;  // clifford.rs:342
     const bool solved = bad == 0;       // clifford.rs:344
     const float achieved = solved ? 1.0f : 0.0f;
-    const float reward = achieved - penalty;  // clifford.rs:345-346
-    if (a.rewards_seq) a.rewards_seq[env] = reward;
-    if (a.dones_seq) a.dones_seq[env] = (uint8_t)(depth == 0 || solved);
-    if (bad != bad0) f.bad[env] = bad;
-    f.depth[env] = depth;
-    a.reward[env] = reward;
-    a.done[env] = (uint8_t)(depth == 0 || solved);  // is_final (clifford.rs:353)
-    a.success[env] = (uint8_t)solved;
-    if (FEAT && (f.flags & F_TRACK)) a.sol_len[env * 2] = sol_n;
-    if (FEAT && fault) atomicOr(&a.error[env], fault);
-    return depth == 0 || solved;
+    if constexpr (NEW_ALU || EARLY_ADDR) {
+        const float reward = NEW_ALU ? (solved ? r_solved : r_open) : achieved - penalty;  // clifford.rs:345-346
+        const uint32_t fin = NEW_ALU ? (solved ? 1u : fin_open) : (uint32_t)(depth == 0 || solved);  // is_final (clifford.rs:353)
+        if (a.rewards_seq) global_store(out_rseq, reward);
+        if (a.dones_seq) global_store(out_dseq, (uint8_t)fin);
+        if (bad != bad0) f.bad[env] = bad;
+        f.depth[env] = depth;
+        global_store(out_reward, reward);
+        global_store(out_done, (uint8_t)fin);
+        global_store(out_success, (uint8_t)solved);
+        if (FEAT && (f.flags & F_TRACK)) a.sol_len[env * 2] = sol_n;
+        if (FEAT && fault) atomicOr(&a.error[env], fault);
+        return fin != 0;
+    } else {
+        const float reward = achieved - penalty;  // clifford.rs:345-346
+        if (a.rewards_seq) a.rewards_seq[env] = reward;
+        if (a.dones_seq) a.dones_seq[env] = (uint8_t)(depth == 0 || solved);
+        if (bad != bad0) f.bad[env] = bad;
+        f.depth[env] = depth;
+        a.reward[env] = reward;
+        a.done[env] = (uint8_t)(depth == 0 || solved);  // is_final (clifford.rs:353)
+        a.success[env] = (uint8_t)solved;
+        if (FEAT && (f.flags & F_TRACK)) a.sol_len[env * 2] = sol_n;
+        if (FEAT && fault) atomicOr(&a.error[env], fault);
+        return depth == 0 || solved;
+    }
 }
 // ... for the policy kernel: the action in a register, the front from its StepArgs, the body's order left to the compiler
 template <bool HAS_Z, bool FEAT, int D16 = 0>
