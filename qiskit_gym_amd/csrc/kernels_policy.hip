@@ -39,6 +39,7 @@
 #include "device_common.hpp"
 #include "qgym_host.hpp"
 #include "qm_step1.hpp"
+#include "qm_inv2.hpp"
 
 namespace qg {
 

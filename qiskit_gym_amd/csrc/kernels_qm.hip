@@ -33,6 +33,7 @@
 #include "device_common.hpp"
 #include "qgym_plan.hpp"
 #include "qm_step1.hpp"
+#include "qm_inv2.hpp"
 
 namespace qg {
 
@@ -93,7 +94,7 @@ __device__ inline uint32_t qm_badmask(const QmRows<NXP, HAS_Z> &s, uint32_t N) {
     return bad;
 }
 
-// r[q] for a per-lane q: tree_select (qm_step1.hpp), a binary select tree on the bits of q (depth log2(n) instead of an n-long
+// r[q] for a per-lane q: tree_select (qm_inv2.hpp), a binary select tree on the bits of q (depth log2(n) instead of an n-long
 // dependent chain).
 
 // apply one action; returns a bit mask of the 16-byte groups that were written
@@ -479,12 +480,12 @@ __global__ __launch_bounds__(256) void qm_inv2_kernel(StepArgs a) {
     bool whole = false;  // DENSE: this lane's env was inverted, its rows are parked in dl
     if constexpr (LIST || DENSE) {  // every thread reaches the wave-wide ballot / rewrite; whole lane pairs are in or out together
         bool fin = false;
-        if ((tid >> 1) < a.B) fin = qm_inv2_body<NXP / 2, FEAT, DENSE>(a, NXP / 2, tid >> 1, (uint32_t)tid & 1u, nullptr, dl, &whole);  // qm_step1.hpp
+        if ((tid >> 1) < a.B) fin = qm_inv2_body<NXP / 2, FEAT, DENSE>(a, NXP / 2, tid >> 1, (uint32_t)tid & 1u, nullptr, dl, &whole);  // qm_inv2.hpp
         if constexpr (DENSE) qm_inv2_dense_flush(a.dense, dl, (tid - (threadIdx.x & 63u)) >> 1, whole);
         if constexpr (LIST) done_mask_store_pairs(a.done_mask, a.B, fin, tid, a.done_epoch);
     } else {
         if ((tid >> 1) >= a.B) return;  // whole lane pairs leave together
-        (void)qm_inv2_body<NXP / 2, FEAT, DENSE>(a, NXP / 2, tid >> 1, (uint32_t)tid & 1u, nullptr, dl, &whole);  // qm_step1.hpp
+        (void)qm_inv2_body<NXP / 2, FEAT, DENSE>(a, NXP / 2, tid >> 1, (uint32_t)tid & 1u, nullptr, dl, &whole);  // qm_inv2.hpp
     }
 }
 
@@ -689,7 +690,7 @@ __device__ inline void qm_init_finish_wave(const InitArgs &a, uint64_t env, uint
 // the wave that holds the fresh rows one per lane: the gate's four rows are read across the lanes (the action is uniform), mixed, and put
 // back before anything is stored, so the step costs no trip to memory for what the reset has just written -- as two calls the lane that
 // finished the reset loaded depth, mask, action, gate entry and row groups back, three dependent trips (1.4 us of the launch's 11).
-// `act`, `g`: the env's action and its gate entry (requested during the scramble).  Results are those of qm_init_finish_wave + qm_step1_body.
+// `act`, `g`: the env's action and its gate entry (requested during the scramble).  Results are those of qm_init_finish_wave + qm_step1_plain_body.
 // Returns is_final (on every lane).
 // INV (qm_reset_inv2_step_kernel): the reference-default step -- the solution log's entry, then maybe_random_invert on `coin` -- i.e. qm_inv2_body.
 template <int NXP, bool HAS_Z, bool INV = false>
@@ -699,7 +700,7 @@ __device__ inline bool qm_init_finish_wave_step(const InitArgs &a, const StepArg
     const bool in_range = act >= 0 && act < (int64_t)sa.num_actions;  // gateset.get(action) (clifford.rs:324)
     const float penalty = in_range ? g.penalty : 0.0f;
     const uint32_t q0 = g.ops & 31u, q1 = (g.ops >> 5) & 31u, m = (g.ops >> 10) & 0xFFFFu;
-    if (in_range && m != QM_IDENTITY) {  // (uniform) qm_step1_body's gate on rows held across the lanes
+    if (in_range && m != QM_IDENTITY) {  // (uniform) qm_step1_plain_body's gate on rows held across the lanes
         const uint32_t s0 = HAS_Z ? 2u * q0 : q0, s1 = HAS_Z ? 2u * q1 : q1;
         const uint32_t x0 = (uint32_t)__shfl((int)myrow, (int)s0), x1 = (uint32_t)__shfl((int)myrow, (int)s1);
         const uint32_t z0 = HAS_Z ? (uint32_t)__shfl((int)myrow, (int)(s0 + 1u)) : 0u, z1 = HAS_Z ? (uint32_t)__shfl((int)myrow, (int)(s1 + 1u)) : 0u;
@@ -1069,15 +1070,15 @@ __global__ __launch_bounds__(256) void qm_reset_step_kernel(ResetStepArgs ra) {
         if (env < a.B && !((resets >> (env & 63u)) & 1ull)) {
             // (the dense rows are written by lane pairs: a lane whose neighbour is being reset writes its rows alone)
             const bool alone = D16 != 0 && ((resets >> ((env ^ 1ull) & 63u)) & 1ull);
-            fin = qm_step1_body<HAS_Z, FEAT, D16, false, true>(step1_front(a), a, Rows::G, env, nullptr, alone);  // (PLAIN_BACK: qm_step1.hpp)
+            fin = qm_step1_plain_body<HAS_Z, FEAT, D16, true>(step1_front(a), a, Rows::G, env, 0, alone);  // (pinned front: qm_step1.hpp)
         }
         done_mask_store(a.done_mask, a.B, fin, env, a.done_epoch);  // (an env being reset: bit clear -- if it is final again after its first step the reset's lane appends it to the list)
         return;
     }
     // (plain configuration: the tree's wave takes the env's first step on the rows it holds -- qm_init_finish_wave_step; otherwise the lane
-    // that has just written the env's fresh episode -- state, depth, bad mask, log lengths -- takes it, as qm_step1_body)
+    // that has just written the env's fresh episode -- state, depth, bad mask, log lengths -- takes it, as qm_step1_plain_body)
     qm_init_block<NXP, HAS_Z, false, 1>(ra.reset, role_index, WAVE ? &a : nullptr, [&](uint64_t env, bool stepped, bool fin) {
-        if (!stepped) fin = qm_step1_body<HAS_Z, FEAT, D16, false, true>(step1_front(a), a, Rows::G, env, nullptr, true);
+        if (!stepped) fin = qm_step1_plain_body<HAS_Z, FEAT, D16, true>(step1_front(a), a, Rows::G, env, 0, true);
         if (fin) {  // (rare: one atomic per env that is final again after its first step)
             const uint32_t slot = atomicAdd(a.done_count, 1u);
             if (slot < a.B) a.done_list[slot] = (uint32_t)env;
@@ -1107,7 +1108,7 @@ __global__ __launch_bounds__(256) void qm_reset_inv2_step_kernel(ResetStepArgs r
             if ((e >> 6) == (uint32_t)(env >> 6)) resets |= 1ull << (e & 63u);
         }
         bool fin = false;
-        if (env < a.B && !((resets >> (env & 63u)) & 1ull)) fin = qm_inv2_body<NXP / 2, FEAT, false>(a, NXP / 2, env, (uint32_t)tid & 1u, nullptr);  // qm_step1.hpp
+        if (env < a.B && !((resets >> (env & 63u)) & 1ull)) fin = qm_inv2_body<NXP / 2, FEAT, false>(a, NXP / 2, env, (uint32_t)tid & 1u, nullptr);  // qm_inv2.hpp
         done_mask_store_pairs(a.done_mask, a.B, fin, tid, a.done_epoch);
         return;
     }
@@ -1119,7 +1120,7 @@ __global__ __launch_bounds__(256) void qm_reset_inv2_step_kernel(ResetStepArgs r
             // earlier (not __threadfence(): its release half writes the XCD's whole L2 back)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            fin = qm_inv2_body<NXP / 2, FEAT, false>(a, NXP / 2, env, h, nullptr);  // qm_step1.hpp
+            fin = qm_inv2_body<NXP / 2, FEAT, false>(a, NXP / 2, env, h, nullptr);  // qm_inv2.hpp
         }
         if (fin && h == 0) {  // (rare: final again after its first step)
             const uint32_t slot = atomicAdd(a.done_count, 1u);

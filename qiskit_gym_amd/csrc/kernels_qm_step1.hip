@@ -19,7 +19,7 @@ constexpr uint32_t QM_STEP1_BLOCK = 256;  // 64- and 128-thread blocks measured 
 // measured 3.77 -> 3.15 us per step at B = 65 536 and 34.9 -> 30.0 us at B = 2^20 (CliffordEnv 16q).
 //
 // At one wave per SIMD nothing overlaps a lane's memory round trips, so their number is what the kernel costs (EXPERIMENTS.md round 6).  Four are
-// left, all needed (qm_step1_body, qm_step1.hpp): {action, depth, bad} -> gate entry -> row groups -> every store.  What the front of that chain
+// left, all needed (qm_step1_mask_body, qm_step1.hpp): {action, depth, bad} -> gate entry -> row groups -> every store.  What the front of that chain
 // reads comes as the kernel's leading parameters -- 14 dwords, the most the preload delivers in SGPRs beside the kernarg pointer -- so the first vector
 // loads are issued without a scalar load in front of them; the rest of StepArgs follows by value and is fetched while those loads fly (one batch,
 // waited for where the gate entry is consumed: a cold scalar line must not surface between the rows and the stores).  On firmware
@@ -36,24 +36,18 @@ constexpr uint32_t QM_STEP1_BLOCK = 256;  // 64- and 128-thread blocks measured 
 template <int NXP, bool HAS_Z, bool FEAT, bool LIST = false, bool DENSE = false>
 __global__ __launch_bounds__(QM_STEP1_BLOCK) void qm_step1_kernel(const void *actions, int32_t *depth, uint32_t *bad, const GateEntry *gates, void *state,
                                                                    uint64_t B, uint32_t flags, uint32_t num_actions, StepArgs a) {
-#if QG_STEP1_ABLATE & 4
-    const uint32_t block = blockDim.x;
-    KernelClock kclk(a.kclk, a.kclk_waves);  // device_common.hpp
-#else
-    constexpr uint32_t block = QM_STEP1_BLOCK;
     KernelClock kclk(a.kclk, a.kclk_waves, QM_STEP1_BLOCK);  // device_common.hpp
-#endif
     constexpr int R = HAS_Z ? 2 * NXP : NXP, G = R / 4;  // row slots and 16-byte groups per env (QmRows, kernels_qm.hip)
     constexpr int D16 = DENSE ? R / 16 : 0;
     const Step1Front f{actions, depth, bad, gates, state, B, flags, num_actions};
-    const uint64_t env = (uint64_t)blockIdx.x * block + threadIdx.x;
+    const uint64_t env = (uint64_t)blockIdx.x * QM_STEP1_BLOCK + threadIdx.x;
     if constexpr (LIST) {  // every thread reaches the wave's ballot
         bool fin = false;
-        if (env < B) fin = qm_step1_body<HAS_Z, FEAT, D16>(f, a, G, env, nullptr);  // qm_step1.hpp
+        if (env < B) fin = qm_step1_mask_body<HAS_Z, FEAT, D16>(f, a, G, env);  // qm_step1.hpp
         done_mask_store(a.done_mask, B, fin, env, a.done_epoch);
     } else {
         if (env >= B) return;
-        (void)qm_step1_body<HAS_Z, FEAT, D16>(f, a, G, env, nullptr);  // qm_step1.hpp
+        (void)qm_step1_mask_body<HAS_Z, FEAT, D16>(f, a, G, env);  // qm_step1.hpp
     }
 }
 

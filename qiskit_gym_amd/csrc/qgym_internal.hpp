@@ -133,7 +133,7 @@ struct StepArgs {
 // all misses in flight at once and keeps the values in SGPRs (CliffordEnv 16q x 65 536: 3.16 -> 3.10 us per step, same box).
 // The trip itself stays in front of the first vector load: a by-value struct cannot be preloaded.  qm_step1_kernel (kernels_qm_step1.hip) does without it --
 // the fields its front reads are leading kernel parameters, preloaded into SGPRs, and the fields its back reads are asked for under the first vector loads
-// (qm_step1_body, qm_step1.hpp) -- so it does not use this macro; the other step kernels do.
+// (qm_step1_mask_body, qm_step1.hpp) -- so it does not use this macro; the other step kernels do.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(QG_NO_ARG_PREFETCH)
 #define QG_PREFETCH_STEP_ARGS(a)                                                                                                          \
     asm volatile("" ::"s"((a).state), "s"((a).actions), "s"((a).gates), "s"((a).depth), "s"((a).bad), "s"((a).B), "s"((a).flags),        \

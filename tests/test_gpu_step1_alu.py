@@ -1,4 +1,4 @@
-"""The arithmetic of the one-step kernel of the TILE layout (qm_step1_body) on lane masks: the gate word decoded once into 0 / -1 words, every
+"""The arithmetic of the one-step kernel of the TILE layout (qm_step1_mask_body) on lane masks: the gate word decoded once into 0 / -1 words, every
 select and merge one bit-select instruction, every term of the 4x4 GF(2) map one a ^ (b & c), `bad` updated by shifts, no branch around "no gate".
 Every case is bit-exact against the CPU oracle: reward bit patterns, success, is_final, depth, final state and observation.  Shapes are the
 smallest at which that arithmetic can go wrong: every gate of the line gateset on every env (so every qubit parity, same-group and cross-group

@@ -2,9 +2,8 @@
 # Development aid: libqgym with ONE translation unit rebuilt under extra -D flags, as qiskit_gym_amd/lib/variants/libqgym_<name>.so
 # (the other objects come from the regular build; run `make -C qiskit_gym_amd/csrc` first).  tools/*.py --lib <path> load it.
 #   tools/build_variant.sh <name> <source.hip> <flags...>
-# One part of the one-step kernel undone (QG_STEP1_ABLATE, qm_step1.hpp: bits 0-2 round 6, bit 3 the mask arithmetic, bit 4 the early
-# addresses, bit 5 the kernel clock's early field), with the flags the Makefile gives that file:
-#   tools/build_variant.sh a8 kernels_qm_step1.hip -DQG_STEP1_ABLATE=8 -mllvm -amdgpu-kernarg-preload-count=16
+# e.g. the TILE kernels without the argument prefetch (qgym_internal.hpp); kernels_qm_step1.hip also takes the flags the Makefile gives that file:
+#   tools/build_variant.sh noprefetch kernels_qm.hip -DQG_NO_ARG_PREFETCH
 set -eu
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 NAME="$1"; SRC="$2"; shift 2
