@@ -31,6 +31,13 @@ constexpr uint32_t QM_STEP1_BLOCK = 256;  // 64- and 128-thread blocks measured 
 // <16, true, false, false, false>: first row wait -> last output store 143 -> 68 instructions, gate entry's arrival -> row loads 28 -> 12,
 // 269 -> 216 in all (profiles/r07/qm_step1_listing.txt); 2.817 -> 2.677 us per step at B = 65 536, 1.41 -> 1.24 us on the kernel's own clock
 // (profiles/r07/NUMBERS.md).
+// The launch ends when its stores have drained, and written bytes cost more than instructions (round 7: a second row store of the same 16 bytes,
+// +0.17 us).  So depth, done and success -- three of a step's seven stores -- leave only in the lanes where the step changed what memory held: depth
+// against the value the step loaded anyway, done and success against two byte loads issued with the first trip (64 B per wave each; a caller may
+// have written either array, so nothing derived stands in for them).  An env at depth 0 stores none of the three; in a rollout success and done
+// change on well under 1 % of the steps.  11 instructions more behind the row stores, 2-3 VGPRs more; written bytes 46.8 -> 41.1 B per env (PMC),
+// 2.675 -> 2.613 us per step at B = 65 536 (profiles/r09/NUMBERS.md; the kernel's own clock rises 1.24 -> 1.29 us: the gain is the launch boundary).
+// Asking for the second row group only in the lanes whose qubits sit in two groups was 0.09 us SLOWER and is not done (EXPERIMENTS.md round 9).
 // LIST: also record the envs that finish, one bit each in StepArgs::done_mask (F_DONE_LIST; its own instantiation: the plain kernel's code stays as it is)
 // DENSE (qg_vec_track_dense, N == NXP, D % 16 == 0): the rows the gate rewrote also go to the resident dense int8 observation
 template <int NXP, bool HAS_Z, bool FEAT, bool LIST = false, bool DENSE = false>

@@ -141,7 +141,7 @@ __device__ inline int64_t action_value(int32_t lo, int32_t hi, bool act64) {
 // FEAT).  Returns is_final.
 // D16 > 0 (qg_vec_track_dense; the matrix has D = 16 * D16 rows, no padding slots): the rows the gate rewrote also go to the env's
 // dense int8 observation -- <= 4 rows of D bytes instead of the D * D bytes a full qg_vec_observe_dense writes.
-// The dependent memory round trips of a lane are four: {action, depth, bad} issued back to back, the action first -- the gate entry (unconditional,
+// The dependent memory round trips of a lane are four: {action, depth, bad, done, success} issued back to back, the action first -- the gate entry (unconditional,
 // clamped index: an out-of-range action reads entry 0 and is given "no gate, penalty 0" afterwards, clifford.rs:324) needs the action alone; the
 // <= 2 row groups; every store.  depth and bad are pinned where the gate entry is consumed: left alone the compiler sinks their first use below the
 // row stores and waits there for ALL outstanding memory operations -- the output stores then leave only after the row stores have been acknowledged.
@@ -154,8 +154,13 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     uint4 *tile_lane = tile + lane;  // the env's place in its tile, in registers before the gate entry is there
     int32_t act_lo = 0, act_hi = 0;
     action_issue(f.actions, env, f.flags & F_ACT64, act_lo, act_hi);
-    int32_t depth = f.depth[env];
+    int32_t depth0 = f.depth[env];
     uint32_t bad0 = f.bad[env];
+    // done and success as memory holds them (a caller may have written either): the stores below leave only where the step changes them.  Two
+    // byte loads behind the action, 64 B per wave each; they arrive ahead of the gate entry, so no wait is theirs.  Their addresses come from
+    // StepArgs, not from the preloaded arguments: (compiler only) the barrier keeps that scalar wait behind the issue of depth and bad
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t done0 = a.done[env], success0 = a.success[env];
     int32_t sol_n = (FEAT && (f.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
     // what depends on `env` alone is computed here, under these loads: the env's place in its tile now (`state` is a preloaded argument), the
     // output addresses under the gate entry's load below -- not between the gate entry's arrival and the row loads, or in front of the stores
@@ -177,10 +182,11 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     // the gate entry, depth and bad are all here: no later wait for a load.  The StepArgs fields the back of the chain reads are asked for here too:
     // their scalar loads are issued at the top, fly with the vector loads and have long arrived -- left alone the compiler fetches a field right
     // before its first use, a cold scalar line between the rows and the stores
-    asm volatile("" : "+v"(g.ops), "+v"(g.penalty), "+v"(depth), "+v"(bad0)
+    asm volatile("" : "+v"(g.ops), "+v"(g.penalty), "+v"(depth0), "+v"(bad0)
                  : "s"(a.N), "s"(a.rewards_seq), "s"(a.dones_seq), "s"(a.reward), "s"(a.done), "s"(a.success));
+    asm volatile("" : "+v"(done0), "+v"(success0));  // ... and the two old bytes, pinned here with depth and bad: their first use is behind the row stores
     asm volatile("" : : "s"(a.kclk_waves));  // ... and the kernel clock's record count: left alone a cold scalar load, waited for, in every wave's last instructions
-    depth = depth > 0 ? depth - 1 : 0;  // clifford.rs:342
+    int32_t depth = depth0 > 0 ? depth0 - 1 : 0;  // clifford.rs:342
     uint32_t bad = bad0, fault = 0;
     // (declared ahead of their values on purpose: declared where they are computed, the compiler pairs r_solved and r_open the other way round)
     float penalty = g.penalty, r_solved = 0.0f, r_open = 0.0f;  // (out of range: 0)
@@ -195,6 +201,9 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     constexpr uint32_t gsh = HAS_Z ? 1u : 2u;
     const uint32_t ops = g.ops, q0 = ops & 31u, q1 = (ops >> 5) & 31u, g0 = q0 >> gsh, g1 = q1 >> gsh;
     uint4 *pa = tile_lane + g0 * 64, *pb = tile_lane + g1 * 64;
+    // (both groups by every lane, also where they are one: the second load under the execution mask of the lanes with two groups -- no request
+    // from the others, which then take `ub` from `ua` behind the wait -- measured 0.09 us per step SLOWER at 65 536 envs: six instructions more in
+    // front of the second load, four selects behind the wait, one wait for both groups.  EXPERIMENTS.md round 9)
     uint4 ua = global_load4(pa), ub = global_load4(pb);
     __builtin_amdgcn_sched_barrier(0);  // (compiler only: everything down to the next one stands between the loads and their wait)
     GateMasks<HAS_Z> gm(ops, g0, g1);
@@ -282,10 +291,13 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     if (a.rewards_seq) global_store(out_rseq, reward);
     if (a.dones_seq) global_store(out_dseq, (uint8_t)fin);
     if (bad != bad0) f.bad[env] = bad;
-    f.depth[env] = depth;
+    // depth, done and success leave only where the step changed what memory held (an env at depth 0 keeps all three; success and done change on
+    // well under 1 % of a rollout's steps): the launch ends when its stores have drained, and three of a step's seven stores were these.
+    // rewards_seq and dones_seq above are a log: always written
+    if (depth != depth0) f.depth[env] = depth;
     global_store(out_reward, reward);
-    global_store(out_done, (uint8_t)fin);
-    global_store(out_success, (uint8_t)solved);
+    if (fin != done0) global_store(out_done, (uint8_t)fin);
+    if ((uint32_t)solved != success0) global_store(out_success, (uint8_t)solved);
     if (FEAT && (f.flags & F_TRACK)) a.sol_len[env * 2] = sol_n;
     if (FEAT && fault) atomicOr(&a.error[env], fault);
     return fin != 0;
