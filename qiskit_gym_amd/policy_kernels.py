@@ -1,0 +1,554 @@
+"""The policy-layer kernels from Python: thin ctypes wrappers around libqgym's sampling, beam, twist and policy-layer entries, the
+reference-shaped `BasicPolicy`, and the kernels' packed operands -- the one layer below both of their callers, the rollout collector
+(`collector.py`) and the batched searches (`synthesis.py`): vec -> policy_kernels -> {collector, synthesis}.
+
+What the two callers share is written once here: `PolicyOperands` (fused head, first-layer bias, packed middle layer and head),
+`FirstLayer` / `first_layer` (the one place that says which route a handle's first layer takes) and `run_first_layer` (the one dispatch
+to `embed`, `embed_observe` and `embed_words`).  Who refreshes them differs: the collector repacks in place at the top of every collection
+(`PolicyOperands.repack_`: the same buffers, so a captured collection follows an in-place parameter update), the searches take a new
+snapshot when a parameter's version counter has moved.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .vec import VecEnv, _stream_ptr
+
+_DT = {torch.float32: _lib.QG_DT_F32, torch.bfloat16: _lib.QG_DT_BF16, torch.float16: _lib.QG_DT_F16, torch.int8: _lib.QG_DT_I8}
+
+
+def sample_actions(logits: torch.Tensor, seed: int, counter: int, num_actions: Optional[int] = None, mask: Optional[torch.Tensor] = None,
+                   value_col: Optional[int] = None, actions: Optional[torch.Tensor] = None, logp: Optional[torch.Tensor] = None,
+                   entropy: Optional[torch.Tensor] = None, values: Optional[torch.Tensor] = None, clock: Optional[torch.Tensor] = None):
+    """One categorical draw per row of `logits[:, :num_actions]` (f32 / bf16 / f16, row stride free).
+    `clock`: optional int64 device scalar added to `counter` on the device (graph replays).
+    Returns (actions int64, logp f32, entropy f32, values f32 or None); see `qg_sample_actions`."""
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [B, >=num_actions] with unit column stride")
+    B, dev = logits.shape[0], logits.device
+    A = int(num_actions) if num_actions is not None else logits.shape[1]
+    actions = torch.empty(B, dtype=torch.int64, device=dev) if actions is None else actions
+    logp = torch.empty(B, dtype=torch.float32, device=dev) if logp is None else logp
+    entropy = torch.empty(B, dtype=torch.float32, device=dev) if entropy is None else entropy
+    if value_col is not None and values is None:
+        values = torch.empty(B, dtype=torch.float32, device=dev)
+    if mask is not None:
+        mask = mask.to(torch.uint8).contiguous()
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    L = _lib.load()
+    _lib.check(L.qg_sample_actions(
+        logits.data_ptr(), _DT[logits.dtype], logits.stride(0), B, A, mask.data_ptr() if mask is not None else None,
+        int(seed) & (2**64 - 1), int(counter), clock.data_ptr() if clock is not None else None, actions.data_ptr(), act_dt, logp.data_ptr(), entropy.data_ptr(),
+        -1 if value_col is None else int(value_col), values.data_ptr() if value_col is not None else None, _stream_ptr()))
+    return actions, logp, entropy, values
+
+
+def beam_select(logp: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, width: int, num_actions: Optional[int] = None,
+                parent: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None, cum_out: Optional[torch.Tensor] = None,
+                live_out: Optional[torch.Tensor] = None):
+    """The selection step of a beam search (`qg_beam_select`): the batch is groups of `width` consecutive envs; from every group's live
+    slots x actions keep the `width` best continuations by `cum[b] + logp[b, a]` (f32; ties by slot, then action; NaN / -inf = no such
+    candidate).  logp: [B, >= num_actions] f32 / bf16 / f16 with unit column stride; cum: f32 [B]; live: uint8 / bool [B].
+    Returns (parent int32 [B] -- batch-wide env indices, for `VecEnv.copy_envs`; actions int32 [B] -- num_actions where a slot stays empty;
+    cum_out f32 [B]; live_out uint8 [B]).  Preallocated outputs may be passed (actions int32 or int64); they may not alias the inputs."""
+    if logp.dim() != 2 or logp.stride(1) != 1:
+        raise ValueError("logp must be [B, >=num_actions] with unit column stride")
+    B, dev, W = logp.shape[0], logp.device, int(width)
+    A = int(num_actions) if num_actions is not None else logp.shape[1]
+    if W < 1 or B % W:
+        raise ValueError(f"beam_select: {B} envs do not divide into groups of {W}")
+    if live.dtype == torch.bool:
+        live = live.view(torch.uint8)
+    for name, t, dt in (("cum", cum, torch.float32), ("live", live, torch.uint8)):
+        if t.dtype != dt or t.numel() != B or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"beam_select: {name} must be a contiguous [B] {dt} tensor on logp's device")
+    parent = torch.empty(B, dtype=torch.int32, device=dev) if parent is None else parent
+    actions = torch.empty(B, dtype=torch.int32, device=dev) if actions is None else actions
+    cum_out = torch.empty(B, dtype=torch.float32, device=dev) if cum_out is None else cum_out
+    live_out = torch.empty(B, dtype=torch.uint8, device=dev) if live_out is None else live_out
+    for name, t, dts in (("parent", parent, (torch.int32,)), ("actions", actions, (torch.int32, torch.int64)), ("cum_out", cum_out, (torch.float32,)),
+                         ("live_out", live_out, (torch.uint8,))):
+        if t.dtype not in dts or t.numel() != B or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"beam_select: {name} must be a contiguous [B] tensor of {' / '.join(str(d) for d in dts)} on logp's device")
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_beam_select(logp.data_ptr(), _DT[logp.dtype], logp.stride(0), A, B // W, W, cum.data_ptr(), live.data_ptr(), parent.data_ptr(),
+                                          actions.data_ptr(), act_dt, cum_out.data_ptr(), live_out.data_ptr(), _stream_ptr()))
+    return parent, actions, cum_out, live_out
+
+
+def beam_seen(n_groups: int, cap: int, device=None) -> torch.Tensor:
+    """An empty history for `beam_merge`: room for `cap` state keys for each of `n_groups` groups (`qg_beam_seen_bytes`), zeroed.  Opaque;
+    `zero_()` empties it again."""
+    if int(n_groups) < 0 or int(cap) < 1:
+        raise ValueError("beam_seen: n_groups >= 0 and cap >= 1")
+    nbytes = int(_lib.load().qg_beam_seen_bytes(int(n_groups), int(cap)))
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device="cuda" if device is None else device)
+
+
+def beam_merge(words: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, width: int, seen: Optional[torch.Tensor] = None, seen_cap: int = 0,
+               keys: Optional[torch.Tensor] = None, dropped: Optional[torch.Tensor] = None, live_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The merge step of a beam search (`qg_beam_merge`): the batch is groups of `width` consecutive envs; a live slot leaves when its state
+    key -- a 64-bit hash of its row of `words` -- is in its group's history `seen` (a revisit), or when another live slot of its group holds
+    the same key with a larger `cum` (ties: the lower slot stays; a duplicate).  The survivors' keys enter the history.
+    words: [B, words_per_env] of 1-, 4- or 8-byte integers (`VecEnv.observe_packed`); cum: f32 [B]; live: uint8 / bool [B]; seen: from
+    `beam_seen(B // width, seen_cap)`, or None to merge within the call only.  keys: optional int64 [B], receives every slot's key;
+    dropped: optional int32 [B // width, 2], (revisits, duplicates) are added to it.  Returns live_out uint8 [B] (not `live` itself)."""
+    if words.dim() != 2 or not words.is_contiguous() or words.is_floating_point() or words.element_size() not in (1, 4, 8):
+        raise ValueError("beam_merge: words must be a contiguous [B, words_per_env] tensor of 1-, 4- or 8-byte integers")
+    B, dev, W = words.shape[0], words.device, int(width)
+    if W < 1 or B % W:
+        raise ValueError(f"beam_merge: {B} envs do not divide into groups of {W}")
+    if live.dtype == torch.bool:
+        live = live.view(torch.uint8)
+    live_out = torch.empty(B, dtype=torch.uint8, device=dev) if live_out is None else live_out
+    for name, t, dt, numel in (("cum", cum, (torch.float32,), B), ("live", live, (torch.uint8,), B), ("live_out", live_out, (torch.uint8,), B),
+                               ("keys", keys, (torch.int64, torch.uint64), B), ("dropped", dropped, (torch.int32, torch.uint32), 2 * (B // W))):
+        if t is not None and (t.dtype not in dt or t.numel() != numel or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"beam_merge: {name} must be a contiguous tensor of {numel} {' / '.join(str(d) for d in dt)} on the device of words")
+    L = _lib.load()
+    if seen is not None and (seen.dtype != torch.int64 or not seen.is_contiguous() or seen.device != dev
+                             or seen.numel() * 8 != L.qg_beam_seen_bytes(B // W, int(seen_cap))):
+        raise ValueError("beam_merge: seen must come from beam_seen(B // width, seen_cap) on the device of words")
+    _lib.check(L.qg_beam_merge(words.data_ptr(), words.element_size(), words.shape[1], B // W, W, cum.data_ptr(), live.data_ptr(),
+                               seen.data_ptr() if seen is not None else None, int(seen_cap) if seen is not None else 0, live_out.data_ptr(),
+                               keys.data_ptr() if keys is not None else None, dropped.data_ptr() if dropped is not None else None, _stream_ptr()))
+    return live_out
+
+
+def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,
+        gae_lambda: float, advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None):
+    """GAE(lambda) over a [T, B] rollout; `dones[t]` = the episode ended with step t.  Returns (advantages, returns)."""
+    T, B = rewards.shape
+    for x, dt in ((rewards, torch.float32), (values, torch.float32), (dones, torch.uint8)):
+        if x.shape != (T, B) or x.dtype != dt or not x.is_contiguous():
+            raise ValueError("gae: rewards/values must be contiguous f32 [T, B], dones uint8 [T, B]")
+    advantages = torch.empty_like(rewards) if advantages is None else advantages
+    returns = torch.empty_like(rewards) if returns is None else returns
+    lv = None
+    if last_values is not None:
+        lv = last_values.to(torch.float32).contiguous()
+    _lib.check(_lib.load().qg_gae(rewards.data_ptr(), values.data_ptr(), dones.data_ptr(), lv.data_ptr() if lv is not None else None,
+                                  float(gamma), float(gae_lambda), T, B, advantages.data_ptr(), returns.data_ptr(), _stream_ptr()))
+    return advantages, returns
+
+
+def expand_packed(packed: torch.Tensor, cols: int, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Bit-packed observation rows (`VecEnv.observe_packed`, any leading shape) -> dense {0,1} [..., rows, cols] in `dtype`."""
+    packed = packed.contiguous()
+    if out is None:
+        out = torch.empty((*packed.shape, cols), dtype=dtype, device=packed.device)
+    _lib.check(_lib.load().qg_expand_packed(packed.data_ptr(), packed.element_size(), packed.numel(), int(cols), out.data_ptr(), _DT[dtype],
+                                            _stream_ptr()))
+    return out
+
+
+def _twist_operands(name: str, perms: torch.Tensor, twist_idx: torch.Tensor, batch: int, width: int, dev):
+    if perms.dtype != torch.int32 or perms.dim() != 2 or perms.shape[1] != width or perms.shape[0] < 1 or not perms.is_contiguous() or perms.device != dev:
+        raise ValueError(f"{name}: the permutation table must be a contiguous int32 [n_twists, {width}] tensor on the device of the input")
+    if twist_idx.dtype != torch.int32 or twist_idx.numel() != batch or not twist_idx.is_contiguous() or twist_idx.device != dev:
+        raise ValueError(f"{name}: twist_idx must be a contiguous int32 [{batch}] tensor on the device of the input")
+
+
+def twist_expand_packed(packed: torch.Tensor, cols: int, obs_perms: torch.Tensor, twist_idx: torch.Tensor, dtype: torch.dtype,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Symmetry views of packed observations (`qg_twist_expand_packed`): out[e, i] = element obs_perms[twist_idx[e]][i] of what
+    `expand_packed` writes for env e -- a gather through the table, made while the bits are expanded.  packed: [B, rows] of 1-, 4- or 8-byte
+    integers (`VecEnv.observe_packed`); obs_perms: int32 [n_twists, rows*cols] (any table: the kernel knows no env); twist_idx: int32 [B],
+    an index outside [0, n_twists) gives that env its untwisted observation.  Returns dense {0,1} [B, rows*cols] in `dtype`."""
+    if packed.dim() != 2 or not packed.is_contiguous() or packed.is_floating_point() or packed.element_size() not in (1, 4, 8):
+        raise ValueError("twist_expand_packed: packed must be a contiguous [B, rows] tensor of 1-, 4- or 8-byte integers")
+    B, rows = packed.shape
+    _twist_operands("twist_expand_packed", obs_perms, twist_idx, B, rows * int(cols), packed.device)
+    if out is None:
+        out = torch.empty((B, rows * int(cols)), dtype=dtype, device=packed.device)
+    if out.dtype != dtype or out.numel() != B * rows * int(cols) or not out.is_contiguous() or out.device != packed.device:
+        raise ValueError("twist_expand_packed: `out` must be a contiguous [B, rows*cols] tensor of the requested dtype on the device of packed")
+    _lib.check(_lib.load().qg_twist_expand_packed(packed.data_ptr(), packed.element_size(), B, rows, int(cols), obs_perms.data_ptr(), obs_perms.shape[0],
+                                                  twist_idx.data_ptr(), out.data_ptr(), _DT[dtype], _stream_ptr()))
+    return out
+
+
+def twist_pack_words(packed: torch.Tensor, cols: int, obs_perms: torch.Tensor, twist_idx: torch.Tensor, rows_out: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`twist_expand_packed` with the view left packed (`qg_twist_pack_words`): int64 [B, rows_out], bit c of out[e, r] = element
+    obs_perms[twist_idx[e]][r*cols + c] of what `expand_packed` writes for env e; bits past `cols` and the words rows .. rows_out-1 are 0.
+    The operands are those of `twist_expand_packed` (cols <= 64); rows_out defaults to rows rounded up to even, the row count
+    `embed_words` takes -- with a first layer packed from the weight padded by `cols` zero columns when rows is odd."""
+    if packed.dim() != 2 or not packed.is_contiguous() or packed.is_floating_point() or packed.element_size() not in (1, 4, 8):
+        raise ValueError("twist_pack_words: packed must be a contiguous [B, rows] tensor of 1-, 4- or 8-byte integers")
+    B, rows = packed.shape
+    _twist_operands("twist_pack_words", obs_perms, twist_idx, B, rows * int(cols), packed.device)
+    rows_out = (rows + 1) // 2 * 2 if rows_out is None else int(rows_out)
+    if rows_out < rows:
+        raise ValueError(f"twist_pack_words: rows_out must be at least the {rows} rows of the input")
+    if out is None:
+        out = torch.empty((B, rows_out), dtype=torch.int64, device=packed.device)
+    if out.dtype != torch.int64 or out.numel() != B * rows_out or not out.is_contiguous() or out.device != packed.device:
+        raise ValueError("twist_pack_words: `out` must be a contiguous int64 [B, rows_out] tensor on the device of packed")
+    _lib.check(_lib.load().qg_twist_pack_words(packed.data_ptr(), packed.element_size(), B, rows, int(cols), obs_perms.data_ptr(), obs_perms.shape[0],
+                                               twist_idx.data_ptr(), out.data_ptr(), rows_out, _stream_ptr()))
+    return out
+
+
+def untwist_actions(actions: torch.Tensor, act_perms: torch.Tensor, twist_idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Actions chosen on views -> real actions (`qg_untwist_actions`): out[e] = act_perms[twist_idx[e]][actions[e]].  actions: int32 / int64
+    [B]; act_perms: int32 [n_twists, num_actions]; twist_idx: int32 [B].  An action outside [0, num_actions) and every action of an env whose
+    twist index is out of range pass through unchanged.  `out` may be `actions` itself."""
+    if actions.dtype not in (torch.int32, torch.int64) or actions.dim() != 1 or not actions.is_contiguous():
+        raise ValueError("untwist_actions: actions must be a contiguous int32 / int64 [B] tensor")
+    B = actions.numel()
+    _twist_operands("untwist_actions", act_perms, twist_idx, B, act_perms.shape[1] if act_perms.dim() == 2 else 0, actions.device)
+    out = torch.empty_like(actions) if out is None else out
+    if out.dtype != actions.dtype or out.numel() != B or not out.is_contiguous() or out.device != actions.device:
+        raise ValueError("untwist_actions: `out` must match actions in dtype, size and device")
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_untwist_actions(actions.data_ptr(), act_dt, B, act_perms.shape[1], act_perms.data_ptr(), act_perms.shape[0],
+                                              twist_idx.data_ptr(), out.data_ptr(), _stream_ptr()))
+    return out
+
+
+def pack_embedding(env: VecEnv, weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """First-layer weight [hidden, rows*cols] (f32 / bf16) in the k order `embed` consumes (`qg_vec_pack_embedding`);
+    repack after every optimiser step (pass `out` to rewrite the same buffer: graph-safe)."""
+    if weight.dim() != 2 or weight.stride(1) != 1:
+        raise ValueError("weight must be [hidden, obs_size] with unit column stride")
+    L = _lib.load()
+    hidden = weight.shape[0]
+    nbytes = L.qg_vec_embed_packed_bytes(env._h, hidden)
+    if nbytes == 0:
+        raise ValueError("embed needs a TILE-layout env (CliffordEnv N <= 16, LinearFunctionEnv 8 < N <= 32) and hidden % 64 == 0")
+    if out is None:
+        out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+    _lib.check(L.qg_vec_pack_embedding(env._h, weight.data_ptr(), _DT[weight.dtype], weight.stride(0), hidden, out.data_ptr(), env._stream()))
+    return out
+
+
+def embed(env: VecEnv, packed: torch.Tensor, bias: Optional[torch.Tensor], hidden: int, relu: bool = True, out: Optional[torch.Tensor] = None,
+          obs_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(obs @ W.T + bias) in bf16 [B, hidden], computed from the env's resident bit-packed state (`qg_vec_embed`).  `obs_out`: also
+    `env.observe_packed(out=obs_out)` of the same state (`qg_vec_embed_observe`: one launch for small batches)."""
+    if out is None:
+        out = torch.empty((env.batch, hidden), dtype=torch.bfloat16, device=env.device)
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous f32 vector")
+    L = _lib.load()
+    if obs_out is not None:
+        if (not obs_out.is_contiguous() or obs_out.numel() != env.batch * env.packed_words_per_env or obs_out.element_size() != env.packed_word_bytes
+                or obs_out.device != out.device):
+            raise ValueError("obs_out must be a contiguous [batch, packed_words_per_env] tensor of the env's packed word type on its device")
+        _lib.check(L.qg_vec_embed_observe(env._h, packed.data_ptr(), bias.data_ptr() if bias is not None else None, hidden, int(relu), out.data_ptr(),
+                                          out.stride(0), obs_out.data_ptr(), env._stream()))
+        return out
+    _lib.check(L.qg_vec_embed(env._h, packed.data_ptr(), bias.data_ptr() if bias is not None else None, hidden, int(relu), out.data_ptr(),
+                              out.stride(0), env._stream()))
+    return out
+
+
+def pack_embed_words(weight: torch.Tensor, rows: int, cols: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """First-layer weight [hidden, rows*cols] (f32 / bf16) in the order `embed_words` consumes (`qg_policy_pack_embed_words`)."""
+    if weight.dim() != 2 or weight.stride(1) != 1:
+        raise ValueError("weight must be [hidden, rows*cols] with unit column stride")
+    L = _lib.load()
+    nbytes = L.qg_policy_embed_words_packed_bytes(int(rows), int(cols), weight.shape[0])
+    if nbytes == 0:
+        raise ValueError("embed_words needs an even number of rows, cols <= 64 and hidden % 128 == 0")
+    if out is None:
+        out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+    _lib.check(L.qg_policy_pack_embed_words(weight.data_ptr(), _DT[weight.dtype], weight.stride(0), int(rows), int(cols), weight.shape[0], out.data_ptr(),
+                                            _stream_ptr()))
+    return out
+
+
+def embed_words(words: torch.Tensor, cols: int, packed: torch.Tensor, bias: Optional[torch.Tensor], hidden: int, relu: bool = True,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(obs @ W.T + bias) in bf16 [B, hidden] from packed observation rows [B, rows] int64 (`VecEnv.observe_packed` of a handle with
+    64-bit row words, a packed rollout buffer, a gathered shard): `qg_policy_embed_words`."""
+    if words.dim() != 2 or words.dtype != torch.int64 or not words.is_contiguous():
+        raise ValueError("words must be a contiguous int64 [B, rows] tensor")
+    B, rows = words.shape
+    if out is None:
+        out = torch.empty((B, hidden), dtype=torch.bfloat16, device=words.device)
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        raise ValueError("bias must be a contiguous f32 vector")
+    _lib.check(_lib.load().qg_policy_embed_words(words.data_ptr(), B, rows, int(cols), packed.data_ptr(), bias.data_ptr() if bias is not None else None, hidden,
+                                                 int(relu), out.data_ptr(), out.stride(0), _stream_ptr()))
+    return out
+
+
+def pack_head(weight: torch.Tensor, bias: Optional[torch.Tensor], num_actions: int, value_row: int, out: Optional[torch.Tensor] = None,
+              after_mid: bool = False) -> torch.Tensor:
+    """Last-layer weight [rows, in_features] (+ bias [rows]; f32 or bf16, same dtype) in the order `head_sample` (or, with
+    after_mid, `mid_head_sample`) consumes: rows 0..num_actions-1 are the actions, row `value_row` the value head (`qg_policy_pack_head`)."""
+    L = _lib.load()
+    nbytes = L.qg_policy_head_packed_bytes(num_actions, weight.shape[1])
+    if nbytes == 0:
+        raise ValueError("fused head needs num_actions <= 222 and in_features % 64 == 0, <= 512")
+    if weight.stride(1) != 1 or (bias is not None and (bias.dtype != weight.dtype or not bias.is_contiguous())):
+        raise ValueError("weight must have unit column stride; bias contiguous and of the same dtype")
+    if out is None:
+        out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+    _lib.check(L.qg_policy_pack_head(weight.data_ptr(), bias.data_ptr() if bias is not None else None, _DT[weight.dtype], weight.stride(0), weight.shape[1],
+                                     int(num_actions), int(value_row), int(after_mid), out.data_ptr(), _stream_ptr()))
+    return out
+
+
+def pack_mid(weight: torch.Tensor, bias: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Middle-layer weight [256, in_features] (+ bias) in the order `mid_head_sample` consumes (`qg_policy_pack_mid`)."""
+    L = _lib.load()
+    nbytes = L.qg_policy_mid_packed_bytes(weight.shape[1], weight.shape[0])
+    if nbytes == 0:
+        raise ValueError("fused middle layer needs 256 output features and in_features % 32 == 0, <= 2048")
+    if weight.stride(1) != 1 or (bias is not None and (bias.dtype != weight.dtype or not bias.is_contiguous())):
+        raise ValueError("weight must have unit column stride; bias contiguous and of the same dtype")
+    if out is None:
+        out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+    _lib.check(L.qg_policy_pack_mid(weight.data_ptr(), bias.data_ptr() if bias is not None else None, _DT[weight.dtype], weight.stride(0), weight.shape[1],
+                                    weight.shape[0], out.data_ptr(), _stream_ptr()))
+    return out
+
+
+def mid_head_sample(h: torch.Tensor, packed_mid: torch.Tensor, mid_features: int, packed_head: torch.Tensor, num_actions: int, seed: int, counter: int,
+                    actions: Optional[torch.Tensor] = None, logp: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
+                    values: Optional[torch.Tensor] = None, clock: Optional[torch.Tensor] = None):
+    """relu(h W2^T + b2) -> last layer -> categorical draw in one kernel (`qg_policy_mid_head_sample`); the head packed with after_mid=True."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+        raise ValueError("h must be bf16 [B, in_features] with unit column stride")
+    B, dev = h.shape[0], h.device
+    actions = torch.empty(B, dtype=torch.int64, device=dev) if actions is None else actions
+    logp = torch.empty(B, dtype=torch.float32, device=dev) if logp is None else logp
+    entropy = torch.empty(B, dtype=torch.float32, device=dev) if entropy is None else entropy
+    values = torch.empty(B, dtype=torch.float32, device=dev) if values is None else values
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_policy_mid_head_sample(h.data_ptr(), h.stride(0), B, h.shape[1], packed_mid.data_ptr(), int(mid_features), packed_head.data_ptr(),
+                                                     int(num_actions), int(seed) & (2**64 - 1), int(counter), clock.data_ptr() if clock is not None else None,
+                                                     actions.data_ptr(), act_dt, logp.data_ptr(), entropy.data_ptr(), values.data_ptr(), _stream_ptr()))
+    return actions, logp, entropy, values
+
+
+def mid_head_sample_step(env: VecEnv, h: torch.Tensor, packed_mid: torch.Tensor, mid_features: int, packed_head: torch.Tensor, seed: int, counter: int,
+                         actions: torch.Tensor, logp: torch.Tensor, entropy: torch.Tensor, values: torch.Tensor,
+                         rewards: Optional[torch.Tensor] = None, dones: Optional[torch.Tensor] = None, reset_seed: Optional[int] = None):
+    """`mid_head_sample` followed, in the same launch, by `env.step(actions)` and by the compaction of the finished envs for the next
+    `env.reset_done` (`qg_vec_mid_head_sample_step`): same draws, same env results, two launches less per collection step.  The env's
+    device clock (`env.set_clock`) is the sampling clock.  `reset_seed`: also `env.reset_done(reset_seed)` (`..._step_reset`: inside the
+    same launch for small batches)."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1 or h.shape[0] != env.batch:
+        raise ValueError("h must be bf16 [env.batch, in_features] with unit column stride")
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    args = (env._h, h.data_ptr(), h.stride(0), h.shape[1], packed_mid.data_ptr(), int(mid_features), packed_head.data_ptr(), int(seed) & (2**64 - 1),
+            int(counter), actions.data_ptr(), act_dt, logp.data_ptr(), entropy.data_ptr(), values.data_ptr(),
+            rewards.data_ptr() if rewards is not None else None, dones.data_ptr() if dones is not None else None)
+    if reset_seed is None:
+        _lib.check(_lib.load().qg_vec_mid_head_sample_step(*args, env._stream()))
+    else:
+        _lib.check(_lib.load().qg_vec_mid_head_sample_step_reset(*args, int(reset_seed) & (2**64 - 1), env._stream()))
+    return actions, logp, entropy, values
+
+
+def head_sample(h: torch.Tensor, packed: torch.Tensor, num_actions: int, seed: int, counter: int, actions: Optional[torch.Tensor] = None,
+                logp: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None, values: Optional[torch.Tensor] = None,
+                clock: Optional[torch.Tensor] = None):
+    """Last layer + categorical draw in one kernel (`qg_policy_head_sample`): h bf16 [B, in_features] -> (actions, logp, entropy, values)."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+        raise ValueError("h must be bf16 [B, in_features] with unit column stride")
+    B, dev = h.shape[0], h.device
+    actions = torch.empty(B, dtype=torch.int64, device=dev) if actions is None else actions
+    logp = torch.empty(B, dtype=torch.float32, device=dev) if logp is None else logp
+    entropy = torch.empty(B, dtype=torch.float32, device=dev) if entropy is None else entropy
+    values = torch.empty(B, dtype=torch.float32, device=dev) if values is None else values
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_policy_head_sample(h.data_ptr(), h.stride(0), B, h.shape[1], packed.data_ptr(), int(num_actions), int(seed) & (2**64 - 1),
+                                                 int(counter), clock.data_ptr() if clock is not None else None, actions.data_ptr(), act_dt,
+                                                 logp.data_ptr(), entropy.data_ptr(), values.data_ptr(), _stream_ptr()))
+    return actions, logp, entropy, values
+
+
+def _logp_outputs(name: str, B: int, A: int, dev, want_rows: bool, logp_rows, actions, best_logp, entropy, values):
+    """Outputs of the two `_logp` wrappers: allocated where None (rows with a stride rounded up to 4 floats: 16-byte stores), checked otherwise."""
+    if want_rows and logp_rows is None:
+        logp_rows = torch.empty((B, (A + 3) // 4 * 4), dtype=torch.float32, device=dev)[:, :A]
+    if not want_rows:
+        logp_rows = None
+    elif (logp_rows.dtype != torch.float32 or logp_rows.dim() != 2 or logp_rows.shape[0] != B or logp_rows.shape[1] < A or logp_rows.device != dev
+          or (logp_rows.stride(1) != 1 and logp_rows.shape[1] > 1) or (B > 1 and logp_rows.stride(0) < A)):
+        raise ValueError(f"{name}: logp_rows must be f32 [B, >= num_actions] with unit column stride on the device of h")
+    actions = torch.empty(B, dtype=torch.int64, device=dev) if actions is None else actions
+    best_logp = torch.empty(B, dtype=torch.float32, device=dev) if best_logp is None else best_logp
+    entropy = torch.empty(B, dtype=torch.float32, device=dev) if entropy is None else entropy
+    values = torch.empty(B, dtype=torch.float32, device=dev) if values is None else values
+    if actions.dtype not in (torch.int32, torch.int64) or actions.numel() != B or not actions.is_contiguous() or actions.device != dev:
+        raise ValueError(f"{name}: actions must be a contiguous int32 / int64 [B] tensor on the device of h")
+    for nm, t in (("best_logp", best_logp), ("entropy", entropy), ("values", values)):
+        if t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name}: {nm} must be a contiguous f32 [B] tensor on the device of h")
+    return logp_rows, actions, best_logp, entropy, values
+
+
+def mid_head_logp(h: torch.Tensor, packed_mid: torch.Tensor, mid_features: int, packed_head: torch.Tensor, num_actions: int, want_rows: bool = True,
+                  logp_rows: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None, best_logp: Optional[torch.Tensor] = None,
+                  entropy: Optional[torch.Tensor] = None, values: Optional[torch.Tensor] = None):
+    """`mid_head_sample` without the draw (`qg_policy_mid_head_logp`): relu(h W2^T + b2) -> last layer -> the whole row of log-probabilities
+    and the arg-max (equal logits: the lowest action), in one kernel, from the same operands.  Returns (logp_rows f32 [B, num_actions] --
+    -inf where an action is masked, ready for `beam_select`; None with want_rows=False, which writes no row: the greedy step --, actions,
+    best_logp = logp_rows[e, actions[e]], entropy, values).  Preallocated outputs may be passed; `logp_rows` may be any f32 [B, >= num_actions]
+    view with unit column stride (rows of 16-byte aligned base and stride are written 16 bytes at a time)."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+        raise ValueError("h must be bf16 [B, in_features] with unit column stride")
+    B, A = h.shape[0], int(num_actions)
+    logp_rows, actions, best_logp, entropy, values = _logp_outputs("mid_head_logp", B, A, h.device, want_rows, logp_rows, actions, best_logp, entropy, values)
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_policy_mid_head_logp(h.data_ptr(), h.stride(0), B, h.shape[1], packed_mid.data_ptr(), int(mid_features), packed_head.data_ptr(), A,
+                                                   logp_rows.data_ptr() if logp_rows is not None else None,
+                                                   (logp_rows.stride(0) if B > 1 else logp_rows.shape[1]) if logp_rows is not None else A,
+                                                   actions.data_ptr(), act_dt, best_logp.data_ptr(), entropy.data_ptr(), values.data_ptr(), _stream_ptr()))
+    return (logp_rows[:, :A] if logp_rows is not None else None), actions, best_logp, entropy, values
+
+
+def head_logp(h: torch.Tensor, packed: torch.Tensor, num_actions: int, want_rows: bool = True, logp_rows: Optional[torch.Tensor] = None,
+              actions: Optional[torch.Tensor] = None, best_logp: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
+              values: Optional[torch.Tensor] = None):
+    """`head_sample` without the draw (`qg_policy_head_logp`): last layer -> log-prob rows and arg-max; arguments and results as `mid_head_logp`."""
+    if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+        raise ValueError("h must be bf16 [B, in_features] with unit column stride")
+    B, A = h.shape[0], int(num_actions)
+    logp_rows, actions, best_logp, entropy, values = _logp_outputs("head_logp", B, A, h.device, want_rows, logp_rows, actions, best_logp, entropy, values)
+    act_dt = {torch.int32: _lib.ACT_I32, torch.int64: _lib.ACT_I64}[actions.dtype]
+    _lib.check(_lib.load().qg_policy_head_logp(h.data_ptr(), h.stride(0), B, h.shape[1], packed.data_ptr(), A,
+                                               logp_rows.data_ptr() if logp_rows is not None else None,
+                                               (logp_rows.stride(0) if B > 1 else logp_rows.shape[1]) if logp_rows is not None else A,
+                                               actions.data_ptr(), act_dt, best_logp.data_ptr(), entropy.data_ptr(), values.data_ptr(), _stream_ptr()))
+    return (logp_rows[:, :A] if logp_rows is not None else None), actions, best_logp, entropy, values
+
+
+class BasicPolicy(nn.Module):
+    def __init__(self, obs_size: int, num_actions: int, embedding_size: int = 512, common: int = 256):
+        super().__init__()
+        self.embeddings = nn.Linear(obs_size, embedding_size)
+        self.common = nn.Linear(embedding_size, common)
+        self.policy_head = nn.Linear(common, num_actions)
+        self.value_head = nn.Linear(common, 1)
+
+    def forward(self, obs_flat: torch.Tensor):
+        h = torch.relu(self.embeddings(obs_flat))
+        h = torch.relu(self.common(h))
+        return self.policy_head(h), self.value_head(h).squeeze(-1)
+
+    @torch.no_grad()
+    def fused_heads(self) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """Policy and value heads as ONE weight [pad8(A + 1), common] / bias, so a collection step runs
+        three GEMMs; column A of the output is the value.  Rebuild after every optimiser step."""
+        A = self.policy_head.out_features
+        rows = (A + 1 + 7) // 8 * 8
+        w = torch.zeros((rows, self.common.out_features), dtype=self.policy_head.weight.dtype, device=self.policy_head.weight.device)
+        b = torch.zeros(rows, dtype=w.dtype, device=w.device)
+        w[:A], w[A] = self.policy_head.weight, self.value_head.weight[0]
+        b[:A], b[A] = self.policy_head.bias, self.value_head.bias[0]
+        return w, b, A
+
+
+def _linear_relu(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    try:  # bias + ReLU in the GEMM epilogue (hipBLASLt)
+        return torch._addmm_activation(b, x, w.t())
+    except Exception:  # pragma: no cover - older torch
+        return torch.relu_(torch.addmm(b, x, w.t()))
+
+
+@dataclass
+class FirstLayer:
+    """The first layer packed for one route of the kernel forward: "state" is `embed` on the handle's resident bits (TILE layout), "words"
+    `embed_words` on `observe_packed` (64-bit row words: PauliEnv, wide CliffordEnv), "views" `embed_words` on `observe_twisted_words`."""
+    route: str
+    weight: torch.Tensor
+
+
+def pack_first(route: str, vec: VecEnv, weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The first-layer weight [hidden, rows*cols] packed for `route` on the handle `vec`, into `out` if given; ValueError (or the
+    library's error) where the route does not take the handle or the shape.  "state" packs through the handle that will read it.  The two
+    words routes read one 64-bit word per observation row; a view's row count is the env's rounded up to even, so at an odd row count
+    the weight gets `cols` zero columns for the pad word (a padded copy: that route is not repacked in place)."""
+    rows, cols = vec.obs_shape_
+    if route == "state":
+        return pack_embedding(vec, weight, out=out)
+    if route == "words":
+        if vec.packed_word_bytes != 8 or vec.packed_words_per_env != rows:
+            raise ValueError("embed_words reads one 64-bit word per observation row")
+        return pack_embed_words(weight, rows, cols, out=out)
+    if cols > 64 or vec.packed_words_per_env != rows:
+        raise ValueError("a row of the view is one 64-bit word")
+    w = weight.detach()
+    if rows % 2:
+        w = torch.nn.functional.pad(w, (0, cols))
+    return pack_embed_words(w, rows + rows % 2, cols, out=out)
+
+
+def first_layer(vec: VecEnv, weight: torch.Tensor, routes: Tuple[str, ...] = ("state", "words")) -> FirstLayer:
+    """The one place that chooses a handle's first-layer route: the first of `routes` whose packer accepts the handle and the shape
+    ("state" before "words"; ("views",) for a search under twists; the collector leaves "words" out where it stores no packed row).
+    ValueError with the last packer's reason where none does."""
+    reason = "no route to try"
+    for route in routes:
+        try:
+            return FirstLayer(route, pack_first(route, vec, weight))
+        except (ValueError, _lib.QGymError) as e:
+            reason = str(e)
+    raise ValueError(reason)
+
+
+def run_first_layer(first: FirstLayer, vec: VecEnv, bias: torch.Tensor, hidden: int, out: torch.Tensor, words: Optional[torch.Tensor] = None,
+                    obs_out: Optional[torch.Tensor] = None, tw: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """relu(obs W1^T + b1) of the handle's current state into `out` (bf16 [B, hidden]): the single dispatch to `embed`, `embed_observe`
+    and `embed_words`.  "state": `obs_out`, if given, also receives the packed observation, in the same launch.  "words": the packed
+    observation is written to `words` (a rollout row, a scratch buffer) and read from there.  "views": so is the view under `tw`."""
+    if first.route == "state":
+        return embed(vec, first.weight, bias, hidden, relu=True, out=out, obs_out=obs_out)
+    if first.route == "words":
+        words = vec.observe_packed(out=words)
+    else:
+        words = vec.observe_twisted_words(tw, words.shape[1], out=words)
+    return embed_words(words, vec.obs_shape_[1], first.weight, bias, hidden, relu=True, out=out)
+
+
+class PolicyOperands:
+    """What the kernels (and the library GEMMs of the collector's other tails) read of a `BasicPolicy` beside a handle's first layer:
+    `w`, `b`, `A` the fused head (`BasicPolicy.fused_heads`); `bias` the first layer's, f32; `mid` the packed middle layer, None where
+    `pack_mid` refuses the shape; `head` the packed last layer, for `mid_head_sample` where `mid` is there and for `head_sample` where
+    not, None where `pack_head` refuses -- and then `mid` is None too: there is no kernel for it alone.  `why` keeps the first refusal.
+    fused_tail=False packs neither (the collector: another dtype than bf16, or switched off)."""
+
+    def __init__(self, policy: BasicPolicy, fused_tail: bool = True):
+        self.w, self.b, self.A = policy.fused_heads()
+        self.bias = policy.embeddings.bias.detach().float().contiguous()
+        self.mid = self.head = self.why = None
+        if not fused_tail:
+            return
+        try:
+            self.mid = pack_mid(policy.common.weight, policy.common.bias)
+        except ValueError as e:
+            self.why = str(e)
+        try:
+            self.head = pack_head(self.w, self.b, self.A, self.A, after_mid=self.mid is not None)
+        except ValueError as e:
+            self.mid, self.why = None, self.why or str(e)
+
+    @torch.no_grad()
+    def repack_(self, policy: BasicPolicy, first: Optional[FirstLayer] = None, vec: Optional[VecEnv] = None):
+        """Every buffer again from the policy's current weights, in place -- and `first`, packed for `vec`, with the first layer's bias:
+        no allocation, every `data_ptr()` stays, so this can run inside a captured collection and a replay follows an in-place
+        parameter update."""
+        w, b, A = self.w, self.b, self.A
+        w[:A].copy_(policy.policy_head.weight)
+        w[A].copy_(policy.value_head.weight[0])
+        b[:A].copy_(policy.policy_head.bias)
+        b[A : A + 1].copy_(policy.value_head.bias)
+        if first is not None:
+            pack_first(first.route, vec, policy.embeddings.weight, out=first.weight)
+            self.bias.copy_(policy.embeddings.bias)
+        if self.head is not None:
+            pack_head(w, b, A, A, out=self.head, after_mid=self.mid is not None)
+        if self.mid is not None:
+            pack_mid(policy.common.weight, policy.common.bias, out=self.mid)

@@ -29,8 +29,9 @@ which is what `embed_words` reads.
 
 How the policy's opinion about a handle's current state is obtained is one decision, taken once per `solve`: the step loops ask a forward
 object (`_TorchForward`, `_KernelForward`) for the row of log-probabilities, the arg-max or the draw, and know nothing else about it.  The
-kernels' operands are a snapshot of the weights (`_Packed`); the first layer packed through a handle stays with the handle's owner
-(`_Handles.first`) and goes when the handle is closed or the snapshot dropped.
+kernels' operands are a snapshot of the weights (`_Packed`: the `policy_kernels.PolicyOperands` the collector also holds, plus the version
+counters they were taken at); the first layer packed through a handle (`policy_kernels.first_layer` names its route) stays with the
+handle's owner (`_Handles.first`) and goes when the handle is closed or the snapshot dropped.
 """
 from __future__ import annotations
 
@@ -41,9 +42,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .collector import (BasicPolicy, beam_merge, beam_seen, beam_select, embed, embed_words, mid_head_logp, mid_head_sample, pack_embed_words, pack_embedding,
-                        pack_head, pack_mid, sample_actions)
 from .envs.gyms import ROTATION_MARKER
+from .policy_kernels import (BasicPolicy, FirstLayer, PolicyOperands, beam_merge, beam_seen, beam_select, first_layer, mid_head_logp, mid_head_sample,
+                             run_first_layer, sample_actions)
 from .vec import VecEnv
 
 
@@ -60,24 +61,18 @@ def policy_from_reference_state_dict(sd: Dict[str, "np.ndarray | torch.Tensor"])
     return pol
 
 
-@dataclass
-class _FirstLayer:
-    """The first layer packed for one route of the kernel forward: "state" is `embed` on the handle's resident bits (TILE layout), "words"
-    `embed_words` on `observe_packed` (64-bit row words: PauliEnv, wide CliffordEnv), "views" `embed_words` on `observe_twisted_words`."""
-    route: str
-    weight: torch.Tensor
+class _Packed(PolicyOperands):
+    """The policy-layer kernels' operands (`bias`, `mid`, `head`: packed once, shared by every handle and by the views): a snapshot of the
+    policy's weights at `at`, the parameters' version counters, never repacked.  An in-place update of the policy drops all of it, the
+    per-handle first layers (`_Handles.first`) included, so the kernels never run one layer of the new weights with another of the old,
+    and follow the policy as the torch forward does.  ValueError where the packers refuse the middle layer or the head."""
 
-
-@dataclass
-class _Packed:
-    """The policy-layer kernels' operands: a snapshot of the policy's weights at `at`, the parameters' version counters.  An in-place
-    update of the policy drops all of it, the per-handle first layers (`_Handles.first`) included, so the kernels never run one layer of the
-    new weights with another of the old, and follow the policy as the torch forward does."""
-    at: tuple
-    bias: torch.Tensor  # of the first layer, f32
-    mid: torch.Tensor  # packed middle layer and head: packed once, shared by every handle and by the views
-    head: torch.Tensor
-    views: Optional[_FirstLayer] = None  # twist_kernels: the first layer for the views' words (no handle in it: packed once)
+    def __init__(self, policy: BasicPolicy, at: tuple):
+        super().__init__(policy)
+        if self.mid is None:
+            raise ValueError(self.why)
+        self.at = at
+        self.views: Optional[FirstLayer] = None  # twist_kernels: the first layer for the views' words (no handle in it: packed once)
 
 
 @dataclass
@@ -86,7 +81,7 @@ class _Handles:
     through the handle that will read it), in the route the handle takes: closed and dropped together."""
     key: tuple
     vecs: Tuple[VecEnv, ...]
-    first: Dict[VecEnv, _FirstLayer] = field(default_factory=dict)
+    first: Dict[VecEnv, FirstLayer] = field(default_factory=dict)
 
 
 def _winner(solved: torch.Tensor, ret: torch.Tensor):
@@ -140,7 +135,7 @@ class _KernelForward(_Forward):
     allocated here, once per search; `greedy` and `draw` return the same buffer every step."""
     kernels = True
 
-    def __init__(self, packed: _Packed, first: Dict[VecEnv, _FirstLayer], policy: BasicPolicy, seed: int, tw: Optional[torch.Tensor], rows: bool):
+    def __init__(self, packed: _Packed, first: Dict[VecEnv, FirstLayer], policy: BasicPolicy, seed: int, tw: Optional[torch.Tensor], rows: bool):
         super().__init__(seed, tw)
         self.packed, self.first = packed, first
         vec = next(iter(first))  # the handles of a search are alike
@@ -157,14 +152,7 @@ class _KernelForward(_Forward):
 
     def _first_layer(self, vec: VecEnv) -> torch.Tensor:
         """relu(obs W1^T + b1) of the handle's current state into `h1` (bf16)."""
-        first, bias = self.first[vec], self.packed.bias
-        if first.route == "state":
-            return embed(vec, first.weight, bias, self.hidden, relu=True, out=self.h1)
-        if first.route == "words":
-            words = vec.observe_packed(out=self.words)
-        else:
-            words = vec.observe_twisted_words(self.tw, self.words.shape[1], out=self.words)
-        return embed_words(words, vec.obs_shape_[1], first.weight, bias, self.hidden, relu=True, out=self.h1)
+        return run_first_layer(self.first[vec], vec, self.packed.bias, self.hidden, out=self.h1, words=self.words, tw=self.tw)
 
     def logp(self, vec: VecEnv) -> torch.Tensor:
         p, s = self.packed, self.scratch
@@ -234,15 +222,13 @@ class BatchedSynthesis:
             self._packed = None
             for held in self._held.values():
                 held.first.clear()
-            w, b, A = pol.fused_heads()
-            self._packed = _Packed(at, pol.embeddings.bias.detach().float().contiguous(), pack_mid(pol.common.weight, pol.common.bias),
-                                   pack_head(w, b, A, A, after_mid=True))
+            self._packed = _Packed(pol, at)
         return self._packed
 
-    def _first_layer(self, vec: VecEnv, kept: Dict[VecEnv, _FirstLayer], views: bool) -> _FirstLayer:
+    def _first_layer(self, vec: VecEnv, kept: Dict[VecEnv, FirstLayer], views: bool) -> FirstLayer:
         """The first layer of the policy-layer kernels (qg_vec_embed / qg_policy_embed_words in front of qg_policy_mid_head_sample / _logp) for
-        `vec`, packed on first use: through the handle and kept in `kept`, its owner's `_Handles.first`; or, `views`, for `embed_words` on
-        `observe_twisted_words`, whose row count is the env's rounded up to even -- the weight gets `cols` zero columns for the pad word.
+        `vec`, packed on first use (`policy_kernels.first_layer` chooses the route): through the handle and kept in `kept`, its owner's
+        `_Handles.first`; or, `views`, for `embed_words` on `observe_twisted_words`, kept with the snapshot.
         ValueError where the kernels do not apply: another policy class or shape, no TILE layout nor 64-bit row words, a view too wide."""
         pol = self._policy
         if not isinstance(pol, BasicPolicy):
@@ -253,21 +239,10 @@ class BatchedSynthesis:
             packed = self._snapshot()
             if views:
                 if packed.views is None:
-                    rows, cols = vec.obs_shape_
-                    if cols > 64 or vec.packed_words_per_env != rows:
-                        raise ValueError("a row of the view is one 64-bit word")
-                    w = pol.embeddings.weight.detach()
-                    if rows % 2:
-                        w = torch.nn.functional.pad(w, (0, cols))
-                    packed.views = _FirstLayer("views", pack_embed_words(w, rows + rows % 2, cols))
+                    packed.views = first_layer(vec, pol.embeddings.weight, ("views",))
                 return packed.views
             if vec not in kept:
-                try:
-                    kept[vec] = _FirstLayer("state", pack_embedding(vec, pol.embeddings.weight))
-                except (ValueError, _lib.QGymError):
-                    if vec.packed_word_bytes != 8 or vec.packed_words_per_env != vec.obs_shape_[0]:
-                        raise
-                    kept[vec] = _FirstLayer("words", pack_embed_words(pol.embeddings.weight, *vec.obs_shape_))
+                kept[vec] = first_layer(vec, pol.embeddings.weight)
             return kept[vec]
         except caught as e:
             raise ValueError(f"{self._NO_TWIST_KERNELS} ({e})" if views else self._NO_KERNELS) from None

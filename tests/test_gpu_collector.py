@@ -26,7 +26,7 @@ def test_collector_trajectories_replay_on_the_oracle(store_obs, dtype_name):
     dtype = getattr(torch, dtype_name)
     col = RolloutCollector(env, pol, dtype=dtype, seed=77, gamma=0.99, gae_lambda=0.9, store_obs=store_obs, use_bit_embedding=True, use_fused_head=True)
     # in bf16 the first layer reads the env's bit-packed state directly (qg_vec_embed), no dense policy input exists
-    assert (col._embed is not None) == (dtype == torch.bfloat16)
+    assert col.route.first == ("state" if dtype == torch.bfloat16 else "dense") and col.route.tail == "heads_gemm"  # common=32: pack_head refuses
     tol = 1e-4 if dtype == torch.float32 else 6e-2  # bf16 activations: 2^-8 relative per layer
     ro = col.collect(T)
     torch.cuda.synchronize()
@@ -153,7 +153,7 @@ def test_graph_replay_with_the_bit_consuming_first_layer(kind, n, inverts, B):
     torch.manual_seed(5)
     pol = BasicPolicy(env.obs_shape_[0] * env.obs_shape_[1], len(gs), embedding_size=128, common=64)
     col = RolloutCollector(env, pol, dtype=torch.bfloat16, seed=9, store_obs="packed", use_graph=True, use_bit_embedding=True, use_fused_head=True)
-    assert col._embed is not None
+    assert col.route.first == "state" and col.route.tail == "head"  # common=64: pack_mid refuses
     for call in range(3):
         ro = col.collect(T)
         torch.cuda.synchronize()
@@ -185,7 +185,7 @@ def test_first_layer_from_the_packed_observation_words(kind, n, kw, use_graph):
     torch.manual_seed(5)
     pol = BasicPolicy(rows * cols, len(gs), embedding_size=128, common=64)
     col = RolloutCollector(env, pol, dtype=torch.bfloat16, seed=9, store_obs="packed", use_graph=use_graph, use_bit_embedding=True, use_fused_head=True)
-    assert col._embed is None and col._embed_words is not None
+    assert col.route.first == "words" and col.route.tail == "head"
     for call in range(3):
         ro = col.collect(T)
         torch.cuda.synchronize()
@@ -226,7 +226,7 @@ def test_sampling_kernel_that_also_steps_the_env_equals_the_separate_launches(ki
         pol = BasicPolicy(obs_size, A, embedding_size=128, common=256)  # the fused tail needs the reference's 256 middle features
         col = RolloutCollector(env, pol, dtype=torch.bfloat16, seed=5, store_obs="packed", use_graph=use_graph, use_bit_embedding=True,
                                use_fused_head=True, use_fused_step=fused)
-        assert col._mid is not None and col._fused_step == fused
+        assert col.route.tail == "mid_head" and col.route.fused_step == fused
         got = []
         for call in range(2):
             ro = col.collect(T)

@@ -159,6 +159,11 @@ def test_twist_kernels_argument_errors():
     # 64 columns), so the operands are asked for a handle-shaped stand-in
     import types
 
+    from qiskit_gym_amd.policy_kernels import first_layer
+
     wide = BatchedSynthesis(syn.env, BasicPolicy(4 * 66, 8).cuda(), seed=1)
-    with pytest.raises(ValueError, match="twist_kernels=True needs"):
-        wide._first_layer(types.SimpleNamespace(obs_shape_=(4, 66), packed_words_per_env=4), {}, views=True)
+    stand_in = types.SimpleNamespace(obs_shape_=(4, 66), packed_words_per_env=4)
+    with pytest.raises(ValueError, match="a row of the view is one 64-bit word"):  # the shared function: the packer's reason
+        first_layer(stand_in, wide._policy.embeddings.weight, ("views",))
+    with pytest.raises(ValueError, match=r"twist_kernels=True needs .* \(a row of the view is one 64-bit word\)"):  # the searches' wording around it
+        wide._first_layer(stand_in, {}, views=True)

@@ -24,5 +24,4 @@ for _ in range(3):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 env.sync()
-kinds = f"embed={'bits' if col._embed is not None else 'words' if col._embed_words is not None else 'library'}, tail={'fused' if col._mid is not None else 'library'}, step={'fused' if col._fused_step else 'own launch'}"
-print(f"LinearFunctionGym {NQ}q add_inverts={inv} B={B}{' hipGraph' if graph else ''}: {3 * T * B / dt:.3e} env-steps/s with the policy in the loop ({dt / (3 * T) * 1e6:.0f} us per step) [{kinds}]")
+print(f"LinearFunctionGym {NQ}q add_inverts={inv} B={B}{' hipGraph' if graph else ''}: {3 * T * B / dt:.3e} env-steps/s with the policy in the loop ({dt / (3 * T) * 1e6:.0f} us per step) [{col.route}]")
