@@ -34,7 +34,7 @@ extern "C" {
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
- *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words (additions only) */
+ *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -427,6 +427,42 @@ size_t qg_beam_seen_bytes(uint64_t n_groups, uint64_t seen_cap);
 int qg_beam_merge(const void *words_dev, int word_bytes, uint32_t words_per_env, uint64_t n_groups, uint32_t width, const float *cum_dev,
                   const uint8_t *live_dev, void *seen_dev, uint64_t seen_cap, uint8_t *live_out_dev, uint64_t *keys_out_dev,
                   uint32_t *dropped_dev, void *stream);
+/* What a beam search does with the results of a step, between qg_vec_step and qg_beam_merge: the beams' returns, every group's winner, which
+ * beams go on -- and, on request, the bound: a beam that can no longer beat its group's winner is hopeless.  Groups as in qg_beam_select:
+ * group g owns slots g*width .. g*width + width-1 of a batch of n_groups*width envs.
+ * Operands, all on the device.  In: parent_dev i32[batch] (qg_beam_select's), ret_in_dev f32[batch] the returns before the step, reward_dev
+ * f32[batch], success_dev / done_dev u8[batch] the step's results.  In and out: live_dev u8[batch] != 0 where a slot holds a beam, best_dev
+ * f32[n_groups] the return of each group's winner (-inf without one), found_dev u8[n_groups] != 0 where a group has a winner.  Out: ret_out_dev
+ * f32[batch], win_src_dev i32[n_groups] (src_idx_dev of the qg_vec_copy_envs that saves the winners), group_live_dev u8[n_groups].
+ * bounded_dev (optional) i32[n_groups]: ADDED to by every call.  `skip`: what win_src says where a group's winner stays (a caller passes an
+ * index qg_vec_copy_envs skips, e.g. batch).  `bonus`: the most a beam's return can still grow by.  `mode`: a qg_bound_mode.
+ * The rules, per group g, in this order (tests/beambound_model.py restates them in numpy; results agree bit for bit):
+ *   1. For a slot b with live[b] != 0: r[b] = ret_in[parent[b]] + reward[b], one f32 addition, round to nearest, not contracted with
+ *      anything, and ret_out[b] = r[b] (the sum's own bits).  A slot that is not live gets ret_out[b] = 0, and its parent, reward, success
+ *      and done are not read.  parent[b] is a batch-wide env index; one outside [0, batch) is outside the contract (it is not followed: r[b]
+ *      is then NaN).
+ *   2. solved[b] = live[b] && success[b].  The pick j is the solved slot of the largest r in qg_beam_select's order (-0 = +0; an r of NaN
+ *      or -inf is no pick), the lowest slot among equals.  If there is a pick and r[j] > best[g] -- strictly, as floats -- then best[g] =
+ *      r[j] (its own bits), found[g] = 1 and win_src[g] = g*width + j.  Otherwise win_src[g] = skip, and best[g] and found[g] stay.
+ *   3. live[b] = live[b] && !done[b].
+ *   4. With mode != QG_BOUND_NONE and found[g] != 0 after rule 2: hopeful[b] = live[b] && (r[b] + bonus > best[g]) -- the sum one f32
+ *      addition of its own, against the best[g] rule 2 left; r[b] + bonus == best[g] is hopeless, and so is a NaN.  QG_BOUND_STOP: if no slot
+ *      of the group is hopeful, every live[b] of the group becomes 0; else nothing changes.  QG_BOUND_PRUNE: live[b] = hopeful[b].
+ *      bounded[g] grows by the number of beams ended this way.  A group with found[g] == 0 is never touched, nor is any with QG_BOUND_NONE.
+ *   5. live_dev is written back as 0 / 1, and group_live[g] = the number of slots of the group still live.
+ *   6. No randomness; the result does not depend on the launch geometry.
+ * Why QG_BOUND_STOP changes no result of a search whose step rewards are at most `bonus` in total from any state on (CliffordEnv,
+ * LinearFunctionEnv, PermutationEnv with metrics weights >= 0: 1.0 for reaching the target, minus penalties): f32 addition is monotone, so no
+ * descendant of b ever holds a return above fl(r[b] + bonus); rule 2 replaces a winner only on a strictly greater return; best only rises.
+ * ret_out_dev may not alias ret_in_dev (a slot's parent is another slot).  Limits: width <= 64 (one lane of a wave per slot), n_groups * width
+ * < 2^31; QG_ERR_UNSUPPORTED beyond, QG_ERR_INVALID for a null required pointer, width 0, an unknown mode, a misaligned 32-bit array or
+ * ret_out_dev == ret_in_dev.  Stream-ordered on `stream`, one launch (one wave per group, several groups per workgroup), plain loads and
+ * stores only, no synchronisation, capturable into a hipGraph. */
+typedef enum { QG_BOUND_NONE = 0, QG_BOUND_STOP = 1, QG_BOUND_PRUNE = 2 } qg_bound_mode;
+int qg_beam_advance(uint64_t n_groups, uint32_t width, const int32_t *parent_dev, const float *ret_in_dev, const float *reward_dev,
+                    const uint8_t *success_dev, const uint8_t *done_dev, uint8_t *live_dev, float *best_dev, uint8_t *found_dev,
+                    float *ret_out_dev, int32_t *win_src_dev, uint8_t *group_live_dev, int32_t *bounded_dev, int32_t skip, float bonus, int mode,
+                    void *stream);
 /* Twists, batched: the symmetries of the coupling map as views of the observation (Env::twists, clifford.rs:370-372; symmetry.rs:205-295).
  * For CliffordEnv, LinearFunctionEnv and PermutationEnv twist t is a pair: obs_perms[t] over the flat dense observation (rows * cols entries)
  * and act_perms[t] over the actions.  THE DEFINITION, proved on the oracle env for every kind, twist and action (tests/test_twist_views.py):

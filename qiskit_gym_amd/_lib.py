@@ -91,7 +91,7 @@ EXPORTED_SYMBOLS = [
     "qg_vec_solutions",
     "qg_vec_set_kernel_clock",
     "qg_kernel_clock_rate_khz",
-    "qg_vec_observe_dense_as", "qg_expand_packed", "qg_widen_dense", "qg_sample_actions", "qg_beam_select", "qg_beam_seen_bytes", "qg_beam_merge", "qg_gae",
+    "qg_vec_observe_dense_as", "qg_expand_packed", "qg_widen_dense", "qg_sample_actions", "qg_beam_select", "qg_beam_seen_bytes", "qg_beam_merge", "qg_beam_advance", "qg_gae",
     "qg_vec_twists", "qg_twist_expand_packed", "qg_vec_observe_twisted", "qg_untwist_actions", "qg_twist_pack_words", "qg_vec_observe_twisted_words",
     "qg_vec_embed_packed_bytes", "qg_vec_pack_embedding", "qg_vec_embed", "qg_vec_embed_observe",
     "qg_policy_embed_words_packed_bytes", "qg_policy_pack_embed_words", "qg_policy_embed_words",
@@ -176,6 +176,7 @@ def load():
     L.qg_beam_seen_bytes.argtypes = [u64, u64]
     L.qg_beam_seen_bytes.restype = sz
     L.qg_beam_merge.argtypes = [vp, C.c_int, C.c_uint32, u64, C.c_uint32, vp, vp, vp, u64, vp, vp, vp, vp]
+    L.qg_beam_advance.argtypes = [u64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_float, C.c_int, vp]
     L.qg_widen_dense.argtypes = [vp, u64, vp, C.c_int, vp]
     L.qg_vec_twists.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.qg_vec_twists.restype = i64
@@ -270,6 +271,7 @@ def load():
 
 
 QG_DT_I8, QG_DT_F32, QG_DT_BF16, QG_DT_F16 = 0, 1, 2, 3
+BOUND_MODES = {None: 0, "stop": 1, "prune": 2}  # qg_bound_mode
 
 
 def check(status: int):

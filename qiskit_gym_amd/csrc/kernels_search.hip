@@ -1,5 +1,6 @@
-// kernels_search.hip -- the device-side steps of a beam search over a policy's log-probabilities: qg_beam_select and, at the end of this
-// file, qg_beam_merge (which beams of a target hold a state the target has already got).
+// kernels_search.hip -- the device-side steps of a beam search over a policy's log-probabilities: qg_beam_select, then qg_beam_merge (which
+// beams of a target hold a state the target has already got) and, at the end of this file, qg_beam_advance (returns, winners, and which
+// beams can still beat their target's winner).
 //
 // qg_beam_select: the selection step.  From the W beams x A actions
 // of one target pick the W best continuations as (parent env, action) pairs, the operands of qg_vec_copy_envs and qg_vec_step, without
@@ -260,6 +261,96 @@ __global__ __launch_bounds__(64 * MERGE_WAVES) void beam_merge_kernel(const Merg
     }
 }
 
+// ---- qg_beam_advance -------------------------------------------------------------------------------------------------------------------------
+// One WAVE per group, lane s = slot s, ADVANCE_WAVES groups per workgroup (the waves of the last workgroup past n_groups leave at once); the
+// rules are stated in include/qgym.h, tests/beambound_model.py restates them in numpy.  Every lane of a group's wave stays to the end -- the
+// lanes past the width hold "not live" -- so the cross-lane steps see all 64:
+//   - the pick is one 64-lane max of key = order(r) << 32 | ~slot over the solved slots (qg_beam_select's order word and key: -0 = +0, the
+//     lowest slot among equals, the same whatever lane a slot sits in); the winner's own r comes back by a lane read;
+//   - "is any slot hopeful", the beams ended and the group's live count are ballots.
+// One wave owns its group's best, found, win_src, group_live and bounded entries for the whole launch: plain vector loads and stores, no
+// atomics, no LDS, no barrier.  r + bonus is an f32 addition of its own (the file is built without contraction, and there is no product).
+constexpr uint32_t ADVANCE_WAVES = 4;
+
+struct AdvanceArgs {
+    const int32_t *parent;
+    const float *ret_in, *reward;
+    const uint8_t *success, *done;
+    uint8_t *live;
+    float *best;
+    uint8_t *found;
+    float *ret_out;
+    int32_t *win_src;
+    uint8_t *group_live;
+    int32_t *bounded;  // or nullptr
+    uint64_t n_groups;
+    uint32_t W, batch;  // batch = n_groups * W
+    int32_t skip, mode;
+    float bonus;
+};
+
+__global__ __launch_bounds__(64 * ADVANCE_WAVES) void beam_advance_kernel(const AdvanceArgs a) {
+    const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
+    const uint64_t g = (uint64_t)blockIdx.x * ADVANCE_WAVES + wave;
+    if (g >= a.n_groups) return;  // (the whole wave)
+    const bool in = lane < a.W;
+    const uint64_t b = g * a.W + lane;  // < batch where `in`
+
+    // 1. returns
+    bool lv = in && a.live[b] != 0, solved = false, ended = false;
+    float r = 0.0f;
+    if (lv) {
+        const uint32_t p = (uint32_t)a.parent[b];
+        // a parent outside the batch is outside the contract: it is not followed
+        r = (p < a.batch ? a.ret_in[p] : __builtin_nanf("")) + a.reward[b];
+        solved = a.success[b] != 0;
+        ended = a.done[b] != 0;
+    }
+    if (in) a.ret_out[b] = r;
+    float best = a.best[g];  // (one address per wave)
+    bool found = a.found[g] != 0;
+
+    // 2. the group's winner
+    const uint32_t o = solved ? beam_order(r) : 0u;  // NaN and -inf have no word: such a result is never > best
+    const uint64_t top = wave_max_u64(o ? beam_key(o, lane) : 0ull);
+    const uint32_t j = top ? 0xFFFFFFFFu - (uint32_t)top : 0u;
+    const float rj = __shfl(r, (int)j, 64);
+    const bool better = top != 0 && rj > best;
+    if (better) {
+        best = rj;
+        found = true;
+    }
+    if (lane == 0) {
+        a.win_src[g] = better ? (int32_t)(g * a.W + j) : a.skip;
+        if (better) {
+            a.best[g] = rj;
+            a.found[g] = 1;
+        }
+    }
+
+    // 3. beams that ended leave
+    lv = lv && !ended;
+
+    // 4. the bound
+    uint32_t n_bounded = 0;
+    if (a.mode != 0 && found) {
+        const bool hopeful = lv && (r + a.bonus > best);
+        const uint64_t hopefuls = __ballot(hopeful), lives = __ballot(lv);
+        if (a.mode == 2 || hopefuls == 0) {
+            n_bounded = (uint32_t)__popcll(lives & ~hopefuls);
+            lv = hopeful;
+        }
+    }
+    if (in) a.live[b] = lv ? 1 : 0;
+
+    // 5.
+    const uint32_t n_live = (uint32_t)__popcll(__ballot(lv));
+    if (lane == 0) {
+        a.group_live[g] = (uint8_t)n_live;
+        if (a.bounded && n_bounded) a.bounded[g] += (int32_t)n_bounded;
+    }
+}
+
 }  // namespace qg
 
 using namespace qg;
@@ -340,6 +431,47 @@ extern "C" int qg_beam_merge(const void *words_dev, int word_bytes, uint32_t wor
     case 4: hipLaunchKernelGGL(beam_merge_kernel<uint32_t>, grid, block, lds, s, a); break;
     default: hipLaunchKernelGGL(beam_merge_kernel<uint64_t>, grid, block, lds, s, a); break;
     }
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}
+
+extern "C" int qg_beam_advance(uint64_t n_groups, uint32_t width, const int32_t *parent_dev, const float *ret_in_dev, const float *reward_dev,
+                               const uint8_t *success_dev, const uint8_t *done_dev, uint8_t *live_dev, float *best_dev, uint8_t *found_dev,
+                               float *ret_out_dev, int32_t *win_src_dev, uint8_t *group_live_dev, int32_t *bounded_dev, int32_t skip, float bonus,
+                               int mode, void *stream) {
+    if (!parent_dev || !ret_in_dev || !reward_dev || !success_dev || !done_dev || !live_dev || !best_dev || !found_dev || !ret_out_dev || !win_src_dev ||
+        !group_live_dev)
+        return set_error(QG_ERR_INVALID, "null argument");
+    if (width == 0) return set_error(QG_ERR_INVALID, "bad shape: width must be positive");
+    if (mode != QG_BOUND_NONE && mode != QG_BOUND_STOP && mode != QG_BOUND_PRUNE) return set_error(QG_ERR_INVALID, "mode must be 0 (none), 1 (stop) or 2 (prune)");
+    if (ret_out_dev == ret_in_dev) return set_error(QG_ERR_INVALID, "input and output arrays may not alias");
+    if (((uintptr_t)parent_dev % 4) || ((uintptr_t)ret_in_dev % 4) || ((uintptr_t)reward_dev % 4) || ((uintptr_t)best_dev % 4) || ((uintptr_t)ret_out_dev % 4) ||
+        ((uintptr_t)win_src_dev % 4) || ((uintptr_t)bounded_dev % 4))
+        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (width > BEAM_MAX_WIDTH) return set_error(QG_ERR_UNSUPPORTED, "beam_advance: width <= %u supported", BEAM_MAX_WIDTH);
+    if (n_groups * width > 0x7FFFFFFFull || n_groups > 0x7FFFFFFFull) return set_error(QG_ERR_UNSUPPORTED, "beam_advance: too many envs for 32-bit env indices");
+    if (n_groups == 0) return QG_OK;
+    AdvanceArgs a;
+    a.parent = parent_dev;
+    a.ret_in = ret_in_dev;
+    a.reward = reward_dev;
+    a.success = success_dev;
+    a.done = done_dev;
+    a.live = live_dev;
+    a.best = best_dev;
+    a.found = found_dev;
+    a.ret_out = ret_out_dev;
+    a.win_src = win_src_dev;
+    a.group_live = group_live_dev;
+    a.bounded = bounded_dev;
+    a.n_groups = n_groups;
+    a.W = width;
+    a.batch = (uint32_t)(n_groups * width);
+    a.skip = skip;
+    a.mode = mode;
+    a.bonus = bonus;
+    const dim3 grid((unsigned)((n_groups + ADVANCE_WAVES - 1) / ADVANCE_WAVES)), block(64u * ADVANCE_WAVES);
+    hipLaunchKernelGGL(beam_advance_kernel, grid, block, 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return QG_OK;
 }

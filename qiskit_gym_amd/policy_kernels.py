@@ -120,6 +120,43 @@ def beam_merge(words: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, width
     return live_out
 
 
+def beam_advance(parent: torch.Tensor, ret_in: torch.Tensor, reward: torch.Tensor, success: torch.Tensor, done: torch.Tensor, live: torch.Tensor,
+                 best: torch.Tensor, found: torch.Tensor, width: int, skip: int, bonus: float = 1.0, mode: Optional[str] = None,
+                 ret_out: Optional[torch.Tensor] = None, win_src: Optional[torch.Tensor] = None, group_live: Optional[torch.Tensor] = None,
+                 bounded: Optional[torch.Tensor] = None):
+    """What a beam search does with a step's results (`qg_beam_advance`): the batch is groups of `width` consecutive envs.  Per live slot
+    `ret_out[b] = ret_in[parent[b]] + reward[b]` (f32; 0 where not live); per group the solved slot of the largest return (lowest slot among
+    equals) becomes the winner if its return is strictly above `best[g]` -- `best`, `found` are updated IN PLACE and `win_src[g]` is its env
+    index for `VecEnv.copy_envs`, else `skip` --; `live` (IN PLACE) loses the slots that are `done`.  mode "stop" / "prune" (None: neither)
+    then apply the bound in groups that have a winner: a live slot is hopeful when `ret_out[b] + bonus > best[g]`; "stop" ends a group's
+    beams once none is hopeful, "prune" ends every hopeless beam; `bounded[g]` (optional, int32 [B // width]) is added to.
+    parent: int32 [B]; ret_in, reward: f32 [B]; success, done, live: uint8 / bool [B]; best: f32 [B // width]; found: uint8 / bool [B // width].
+    Returns (ret_out f32 [B] -- not `ret_in` itself --, win_src int32 [B // width], group_live uint8 [B // width]: the live slots left)."""
+    B, dev, W = parent.numel(), parent.device, int(width)
+    if W < 1 or B % W:
+        raise ValueError(f"beam_advance: {B} envs do not divide into groups of {W}")
+    if mode not in _lib.BOUND_MODES:
+        raise ValueError(f"beam_advance: mode must be None, 'stop' or 'prune', not {mode!r}")
+    M = B // W
+    success, done, live, found = (t.view(torch.uint8) if t.dtype == torch.bool else t for t in (success, done, live, found))
+    ret_out = torch.empty(B, dtype=torch.float32, device=dev) if ret_out is None else ret_out
+    win_src = torch.empty(M, dtype=torch.int32, device=dev) if win_src is None else win_src
+    group_live = torch.empty(M, dtype=torch.uint8, device=dev) if group_live is None else group_live
+    for name, t, dt, numel in (("parent", parent, torch.int32, B), ("ret_in", ret_in, torch.float32, B), ("reward", reward, torch.float32, B),
+                               ("success", success, torch.uint8, B), ("done", done, torch.uint8, B), ("live", live, torch.uint8, B),
+                               ("best", best, torch.float32, M), ("found", found, torch.uint8, M), ("ret_out", ret_out, torch.float32, B),
+                               ("win_src", win_src, torch.int32, M), ("group_live", group_live, torch.uint8, M), ("bounded", bounded, torch.int32, M)):
+        if t is not None and (t.dtype != dt or t.numel() != numel or t.dim() != 1 or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"beam_advance: {name} must be a contiguous [{numel}] {dt} tensor on parent's device")
+    if ret_out.data_ptr() == ret_in.data_ptr() and B:
+        raise ValueError("beam_advance: ret_out may not alias ret_in (a slot's parent is another slot)")
+    _lib.check(_lib.load().qg_beam_advance(M, W, parent.data_ptr(), ret_in.data_ptr(), reward.data_ptr(), success.data_ptr(), done.data_ptr(),
+                                           live.data_ptr(), best.data_ptr(), found.data_ptr(), ret_out.data_ptr(), win_src.data_ptr(),
+                                           group_live.data_ptr(), bounded.data_ptr() if bounded is not None else None, int(skip), float(bonus),
+                                           _lib.BOUND_MODES[mode], _stream_ptr()))
+    return ret_out, win_src, group_live
+
+
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,
         gae_lambda: float, advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None):
     """GAE(lambda) over a [T, B] rollout; `dones[t]` = the episode ended with step t.  Returns (advantages, returns)."""

@@ -15,7 +15,8 @@ PauliGym solutions also carry the rotations each gate released (pauli.rs:612-626
 recovered by replaying the winners on a `track_solution` batch.
 
 `solve(..., beam_width=W)` searches differently: a deterministic beam search over the policy's log-probabilities, W beams per target, on
-the batched clone (`VecEnv.copy_envs`) and the device-side selection kernel (`collector.beam_select`); see `solve`.
+the batched clone (`VecEnv.copy_envs`) and the device-side selection kernel (`collector.beam_select`); see `solve`.  `bound="stop"` ends a
+target's search once no beam of it can beat its winner (`collector.beam_advance`, which is also the step's bookkeeping in one launch).
 
 `solve(..., fast=True)` takes the policy off the tensor library: the first layer reads the bit-packed state (`collector.embed` /
 `embed_words`), the rest is one kernel that either draws (`mid_head_sample`: the sampled searches) or, for the greedy and the beam search,
@@ -43,7 +44,7 @@ import torch
 
 from . import _lib
 from .envs.gyms import ROTATION_MARKER
-from .policy_kernels import (BasicPolicy, FirstLayer, PolicyOperands, beam_merge, beam_seen, beam_select, first_layer, mid_head_logp, mid_head_sample,
+from .policy_kernels import (BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer, mid_head_logp, mid_head_sample,
                              run_first_layer, sample_actions)
 from .vec import VecEnv
 
@@ -295,10 +296,12 @@ class BatchedSynthesis:
         tw = torch.tensor([views[g % len(views)] for g in range(groups)], dtype=torch.int32, device=dev).repeat(M)
         return (tw if width is None else tw.repeat_interleave(width)).contiguous()
 
-    def _beam_search(self, states, fwd: _Forward, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv):
+    def _beam_search(self, states, fwd: _Forward, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv,
+                     bound: Optional[str] = None):
         """The search of `solve(beam_width=W)`: `cur` and `oth` take turns, `fwd` reads whichever is current.  `tw` None: V is 1.  Else the
         groups are the (target, view) pairs, V consecutive ones per target, each searched under its own fixed view (and with its own merge
-        history); a target's winner is the best result of its V groups, ties to the lowest view."""
+        history); a target's winner is the best result of its V groups, ties to the lowest view.  `bound` "stop" / "prune": returns, winners
+        and `live` come from one `beam_advance` per step, which also ends the beams that cannot beat their group's winner."""
         targets = len(states)
         M = targets * V  # groups
         B, A, dev = cur.batch, cur.num_actions(), cur.device
@@ -315,6 +318,9 @@ class BatchedSynthesis:
         ret = torch.zeros(B, dtype=torch.float32, device=dev)
         nowhere = torch.full((M,), B, dtype=torch.int32, device=dev)  # out of range as a copy source: that entry is skipped
         steps = 0
+        if bound is not None:  # beam_advance updates best, found and live in place; the returns alternate between two buffers
+            found_u8, spare, bounded = found.view(torch.uint8), torch.empty_like(ret), torch.zeros(M, dtype=torch.int32, device=dev)
+            win_src, group_live = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, dtype=torch.uint8, device=dev)
         if merge:  # the targets' own keys open the histories (one live slot per unsolved target: nothing to drop), so coming back to a target is a revisit
             cap = T * W + 1  # a step adds at most W keys per target: the history of a search never fills
             seen, dropped = beam_seen(M, cap, dev), torch.zeros((M, 2), dtype=torch.int32, device=dev)
@@ -325,15 +331,22 @@ class BatchedSynthesis:
             fwd.real_actions(cur, act)  # a child lives in its parent's group, hence under its view
             oth.copy_envs(cur, parent)
             oth.step(act)
-            ret = ret[parent.long()] + oth.reward  # the return `solve` ranks by: the parent's plus this step's reward
-            solved = (live.bool() & oth.success.bool()).view(M, W)
-            live = live & (1 - oth.done)
-            score, j = _winner(solved, ret.view(M, W))  # the lowest slot among equals
-            val = score.gather(1, j.view(M, 1)).view(M)
-            better = val > best
-            win.copy_envs(oth, torch.where(better, group * W + j.to(torch.int32), nowhere))
-            best = torch.where(better, val, best)
-            found |= better
+            if bound is None:
+                ret = ret[parent.long()] + oth.reward  # the return `solve` ranks by: the parent's plus this step's reward
+                solved = (live.bool() & oth.success.bool()).view(M, W)
+                live = live & (1 - oth.done)
+                score, j = _winner(solved, ret.view(M, W))  # the lowest slot among equals
+                val = score.gather(1, j.view(M, 1)).view(M)
+                better = val > best
+                win.copy_envs(oth, torch.where(better, group * W + j.to(torch.int32), nowhere))
+                best = torch.where(better, val, best)
+                found |= better
+            else:  # the same in one launch, and the bound: no reward after this step exceeds 1.0 in total (`solve` has checked the weights)
+                prev = ret
+                ret = beam_advance(parent, prev, oth.reward, oth.success, oth.done, live, best, found_u8, W, skip=B, bonus=1.0, mode=bound,
+                                   ret_out=spare, win_src=win_src, group_live=group_live, bounded=bounded)[0]
+                spare = prev
+                win.copy_envs(oth, win_src)  # B, out of range, where the winner stays
             if merge:  # beams that ended (the step's results among them) have left `live`: they are neither merged nor recorded
                 live = beam_merge(oth.observe_packed(out=words), cum, live, W, seen, cap, dropped=dropped)
             cur, oth = oth, cur
@@ -359,12 +372,14 @@ class BatchedSynthesis:
         if merge:
             n_rev, n_dup = (int(x) for x in dropped.sum(dim=0).cpu())
             self.last_stats.update(merged=n_dup, revisits=n_rev)
+        if bound is not None:
+            self.last_stats.update(bound=bound, bounded=int(bounded.sum()))
         return out
 
     @torch.no_grad()
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
               beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None,
-              twist_kernels: bool = False) -> List[Optional[List[int]]]:
+              twist_kernels: bool = False, bound: Optional[str] = None) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         fast: run the forward pass on the policy-layer kernels (bf16 products, f32 accumulation; `last_stats["kernels"]` says whether they
         ran).  Sampled searches: forward pass and draw (default, fast=None: when the kernels apply and the batch has at least 4 096 envs).
@@ -390,6 +405,21 @@ class BatchedSynthesis:
         at least as much depth left, so nothing is lost but slots are freed for distinct states; which targets are solved, and with how
         many gates, may still change either way, since other beams survive.  `last_stats` then also counts the beams dropped: "merged"
         (same state within a step) and "revisits".
+
+        bound="stop" or "prune" (with beam_width; default None: the search exactly as above) uses what the rewards of CliffordGym,
+        LinearFunctionGym and PermutationGym have in common: a step earns 1.0 when it reaches the target, minus penalties that are never
+        negative while no metrics weight is, so a running beam with return r can end with at most r + 1.0 (in f32, as the search adds).  A
+        target's winner changes only for a strictly greater return, so a beam with r + 1.0 <= the winner's return is hopeless, and so is
+        everything that descends from it.  "stop": once every running beam of a target (under twists: of a (target, view) group) is
+        hopeless they all leave; this returns exactly what bound=None returns, in fewer steps where every target has found its winner early
+        -- the loop still ends only when no beam is left anywhere, looked at every 8th step, so a target nobody solves keeps it running to
+        max_depth.  "prune": every hopeless beam leaves on its own and its slot goes to other continuations of the target; like
+        merge_duplicates this may change which targets are solved and with how many gates, either way.  Either mode also replaces the
+        step's bookkeeping (returns, winners, `live`) by one kernel, `collector.beam_advance`, and combines with fast, twists,
+        twist_kernels and merge_duplicates.  `last_stats` gains "bound" (the mode) and "bounded" (beams ended by the bound).  ValueError:
+        without beam_width, an unknown mode, a metrics weight below 0 (the bound needs rewards that cannot exceed 1), or PauliGym -- its step
+        adds pauli_layer_reward per released rotation (pauli.rs:634) and a target may hold rotations beyond the observed columns, so the
+        reward still to come has no bound the search can see: the reason merge_duplicates refuses it.
 
         twists=V >= 1: V symmetry views per target (None: none of this; every code path, handle and `last_stats` as without the argument).
         View 0 is the untwisted observation, views 1 .. V-1 the env's non-identity twists in `VecEnv.twists()` order; V is cut to what the
@@ -433,6 +463,14 @@ class BatchedSynthesis:
                 raise ValueError("merge_duplicates: a PauliGym observation does not determine its state (rotations beyond the observed columns, DAG order)")
         elif merge_duplicates:
             raise ValueError("merge_duplicates needs beam_width")
+        if bound is not None:
+            if bound not in ("stop", "prune"):
+                raise ValueError(f"bound must be None, 'stop' or 'prune', not {bound!r}")
+            if beam_width is None:
+                raise ValueError("bound needs beam_width")
+            if self.env.env_kind == "pauli":
+                raise ValueError("bound: a PauliGym step adds pauli_layer_reward per released rotation (pauli.rs:634), and a target may hold rotations "
+                                 "beyond the observed columns: the reward still to come has no bound the search can see")
         views = None if twists is None else self._views(int(twists))
         V = 1 if views is None else len(views)
         if beam_width is not None:
@@ -440,8 +478,13 @@ class BatchedSynthesis:
             held = self._handles("beam", (M * V * W, M * V * W, M * V), views is not None)
             cur, oth, win = held.vecs
             tw = None if views is None else self._twist_index(views, V, M, W, cur.device)
+            if bound is not None:  # the handle's config: the caller's metrics weights over the reference's defaults
+                low = {k: float(getattr(cur._cfg, "w_" + k)) for k in ("n_cnots", "n_layers_cnots", "n_layers", "n_gates")}
+                low = {k: w for k, w in low.items() if not w >= 0.0}
+                if low:
+                    raise ValueError(f"bound needs rewards that cannot exceed 1: every metrics weight must be >= 0, got {low}")
             fwd = self._forward(held, 2, tw, bool(twist_kernels) or fast is True, rows=True)  # on request only: the kernels or a ValueError
-            return self._beam_search(states, fwd, V, tw, W, bool(merge_duplicates), cur, oth, win)
+            return self._beam_search(states, fwd, V, tw, W, bool(merge_duplicates), cur, oth, win, bound)
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
         if views is not None and deterministic:
             S = V  # ... but for the view they are seen through
@@ -503,10 +546,10 @@ class BatchedSynthesis:
         return out
 
     def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
-              twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False):
+              twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False, bound: Optional[str] = None):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
         sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, fast=fast, beam_width=beam_width,
-                          merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels)
+                          merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels, bound=bound)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):

@@ -4,7 +4,11 @@ the selection kernel (`collector.beam_select`) beside the torch expression it re
 --merge: instead, beam_width 4 / 16 / 64 with and without merge_duplicates on the same targets: solved, mean gates, time per solve and the share
 of the live beams that the merge drops (revisits and duplicates apart); under `rocprofv3 --kernel-trace --stats` the same run gives
 beam_merge_kernel beside beam_select_kernel and copy_envs_kernel.
-Run on the GPU box: python tools/bench_beam.py [--targets 1024] [--merge [--widths 4 16 64]]"""
+--bound: instead, bound=None / "stop" / "prune" in one process on the same targets -- the three trained policies and CliffordGym 16q under a seeded
+random policy, beam_width 1 / 4 / 16, with and without merge_duplicates, clifford_3q_custom once more with fast=True: solved, mean gates, steps,
+beams ended by the bound, time per solve (the three bounds alternate, best of the windows); then the `collector.beam_advance` launch beside the
+tensor-library lines of the search that it replaces.
+Run on the GPU box: python tools/bench_beam.py [--targets 1024] [--merge [--widths 4 16 64] | --bound [--widths 1 4 16]]"""
 import argparse
 import os
 import sys
@@ -19,7 +23,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from test_reference_policies import MODELS, load  # noqa: E402
 
 import qiskit_gym_amd.envs as envs  # noqa: E402
-from qiskit_gym_amd.collector import beam_select  # noqa: E402
+from qiskit_gym_amd.collector import BasicPolicy, beam_advance, beam_select  # noqa: E402
+from qiskit_gym_amd.envs.gateset import gateset_from_coupling_map, line_edges  # noqa: E402
 from qiskit_gym_amd.synthesis import BatchedSynthesis, policy_from_reference_state_dict  # noqa: E402
 
 GYMS = {"clifford": "CliffordGym", "linear_function": "LinearFunctionGym", "permutation": "PermutationGym"}
@@ -134,16 +139,115 @@ def select_times(reps: int = 200):
               f"torch expression {best['torch topk']:.1f} us per call; same result: {same}", flush=True)
 
 
+def bound_table(M: int, difficulty: int, widths, reps: int = 3):
+    cases = []
+    for name in ("clifford_3q_custom", "lf_5_line", "perm_square_3x3"):
+        cfg, gateset, w = load(name)
+        gym = getattr(envs, GYMS[MODELS[name]])(cfg["num_qubits"], gateset, depth_slope=cfg["depth_slope"], max_depth=cfg["max_depth"])
+        cases.append((name, gym, policy_from_reference_state_dict(w), (False,) if name != "clifford_3q_custom" else (False, True)))
+    n, gs = gateset_from_coupling_map(line_edges(16, True), None, ["H", "S", "Sdg", "SX", "SXdg", "CX", "CZ", "SWAP"])
+    torch.manual_seed(16)
+    cases.append(("CliffordGym 16q (random policy, max_depth 40)", envs.CliffordGym(n, gs, max_depth=40), BasicPolicy(4 * n * n, len(gs)), (False,)))
+    for name, gym, policy, fasts in cases:
+        syn = BatchedSynthesis(gym, policy, seed=1)
+        v = gym.vec(M, add_inverts=False, add_perms=False, track_solution=False, difficulty=difficulty)
+        v.reset(3)
+        states = v.get_state("i64").cpu().numpy()
+        v.close()
+        for fast in fasts:
+            for W in widths:
+                for merge in (False, True):
+                    kws = {b: dict(beam_width=W, merge_duplicates=merge, bound=b, fast=True if fast else None) for b in (None, "stop", "prune")}
+                    best, stats, sols = {b: float("inf") for b in kws}, {}, {}
+                    for kw in kws.values():
+                        syn.solve(states, **kw)  # warm-up: the handles of this batch shape, every code path
+                    torch.cuda.synchronize()
+                    for _ in range(reps):  # the three alternate
+                        for b, kw in kws.items():
+                            t0 = time.perf_counter()
+                            sols[b] = syn.solve(states, **kw)
+                            torch.cuda.synchronize()
+                            best[b] = min(best[b], time.perf_counter() - t0)
+                            stats[b] = dict(syn.last_stats)
+                    for b in kws:
+                        st = stats[b]
+                        same = "" if b is None else f", solutions equal to bound=None: {sols[b] == sols[None]}"
+                        print(f"{name} x {M} targets (scrambles of {difficulty} gates), beam_width={W}, merge_duplicates={merge}, fast={fast}, bound={b}: "
+                              f"solved {st['solved']}/{M}, mean gates {st['mean_gates']:.3f}, {st['steps']} steps, bounded {st.get('bounded', '-')}, "
+                              f"{best[b] * 1e3:.1f} ms per solve (best of {reps}), {best[b] * 1e6 / max(1, st['steps']):.0f} us per step{same}", flush=True)
+
+
+def torch_advance(parent, ret, reward, success, done, live, best, found, W, group, nowhere):
+    """The lines of `BatchedSynthesis._beam_search` that `beam_advance` stands for (bound=None), up to the source index of the winners' copy."""
+    M = best.shape[0]
+    ret = ret[parent.long()] + reward
+    solved = (live.bool() & success.bool()).view(M, W)
+    live = live & (1 - done)
+    score = torch.where(solved, ret.view(M, W), torch.full((M, W), -float("inf"), device=ret.device))
+    j = score.argmax(dim=1)
+    val = score.gather(1, j.view(M, 1)).view(M)
+    better = val > best
+    src = torch.where(better, group * W + j.to(torch.int32), nowhere)
+    return ret, live, torch.where(better, val, best), found | better, src
+
+
+def advance_times(reps: int = 200):
+    for M, W in ((1024, 4), (1024, 16), (4096, 16)):
+        B = M * W
+        g = torch.Generator(device="cuda").manual_seed(M + W)
+        parent = (torch.arange(B, device="cuda") // W * W + torch.randint(0, W, (B,), device="cuda", generator=g)).to(torch.int32)
+        ret, reward = -torch.rand(B, device="cuda", generator=g), -torch.rand(B, device="cuda", generator=g) * 0.02
+        success = (torch.rand(B, device="cuda", generator=g) < 0.05).to(torch.uint8)
+        reward += success
+        live0 = (torch.rand(B, device="cuda", generator=g) < 0.9).to(torch.uint8)
+        best0, found0 = torch.full((M,), -float("inf"), device="cuda"), torch.zeros(M, dtype=torch.bool, device="cuda")
+        group, nowhere = torch.arange(M, dtype=torch.int32, device="cuda"), torch.full((M,), B, dtype=torch.int32, device="cuda")
+        live, best, found = live0.clone(), best0.clone(), found0.clone()
+        out = dict(ret_out=torch.empty(B, device="cuda"), win_src=torch.empty(M, dtype=torch.int32, device="cuda"),
+                   group_live=torch.empty(M, dtype=torch.uint8, device="cuda"), bounded=torch.zeros(M, dtype=torch.int32, device="cuda"))
+
+        def kernel(mode):  # live, best and found are updated in place: from the second call on they are their own fixed point, the work is the same
+            return beam_advance(parent, ret, reward, success, success, live, best, found, W, B, 1.0, mode, **out)
+
+        def lines():
+            return torch_advance(parent, ret, reward, success, success, live0, best0, found0, W, group, nowhere)
+
+        t = lines()
+        k = kernel(None)
+        torch.cuda.synchronize()
+        on = live0.bool()
+        same = bool((k[0][on] == t[0][on]).all()) and bool((live == t[1]).all()) and bool((best == t[2]).all()) and bool((found == t[3]).all()) and bool((k[1] == t[4]).all())
+        fns = {"beam_advance": lambda: kernel(None), "beam_advance stop": lambda: kernel("stop"), "torch lines": lines}
+        times = {k_: float("inf") for k_ in fns}
+        for _ in range(5):  # alternate; the best of five windows each
+            for k_, fn in fns.items():
+                fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[k_] = min(times[k_], e0.elapsed_time(e1) * 1e3 / reps)
+        print(f"advance {M} targets x {W} beams (eager, the launch alone, {reps} calls per window): "
+              f"beam_advance {times['beam_advance']:.1f} us, with mode stop {times['beam_advance stop']:.1f} us, torch lines {times['torch lines']:.1f} us per call; "
+              f"same result: {same}", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--targets", type=int, default=1024)
     ap.add_argument("--difficulty", type=int, default=32)
     ap.add_argument("--merge", action="store_true", help="the merge_duplicates table instead of the search table and the selection times")
-    ap.add_argument("--widths", type=int, nargs="+", default=[4, 16, 64])
+    ap.add_argument("--bound", action="store_true", help="the bound table (None / stop / prune) and the beam_advance launch beside the torch lines instead")
+    ap.add_argument("--widths", type=int, nargs="+", default=None, help="default: 4 16 64 with --merge, 1 4 16 with --bound")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
-    if args.merge:
-        merge_table(args.targets, args.difficulty, args.widths)
+    if args.bound:
+        bound_table(args.targets, args.difficulty, args.widths or [1, 4, 16])
+        advance_times()
+    elif args.merge:
+        merge_table(args.targets, args.difficulty, args.widths or [4, 16, 64])
     else:
         search_table(args.targets, args.difficulty)
         select_times()
