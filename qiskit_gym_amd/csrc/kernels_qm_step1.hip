@@ -18,8 +18,9 @@ constexpr uint32_t QM_STEP1_BLOCK = 256;  // 64- and 128-thread blocks measured 
 // instructions than the register-resident kernel, which at one wave per SIMD is what a step costs;
 // measured 3.77 -> 3.15 us per step at B = 65 536 and 34.9 -> 30.0 us at B = 2^20 (CliffordEnv 16q).
 //
-// At one wave per SIMD nothing overlaps a lane's memory round trips, so their number is what the kernel costs (EXPERIMENTS.md round 6).  Four are
-// left, all needed (qm_step1_mask_body, qm_step1.hpp): {action, depth, bad} -> gate entry -> row groups -> every store.  What the front of that chain
+// At one wave per SIMD nothing overlaps a lane's memory round trips, so their number is what the kernel costs (EXPERIMENTS.md round 6).  Round 6 left
+// four (the form before round 10, and still the path of a wave without F_GROUP_LANES; today's chain: the round 10 paragraph below):
+// {action, depth, bad} -> gate entry -> row groups -> every store (qm_step1_mask_body, qm_step1.hpp).  What the front of that chain
 // reads comes as the kernel's leading parameters -- 14 dwords, the most the preload delivers in SGPRs beside the kernarg pointer -- so the first vector
 // loads are issued without a scalar load in front of them; the rest of StepArgs follows by value and is fetched while those loads fly (one batch,
 // waited for where the gate entry is consumed: a cold scalar line must not surface between the rows and the stores).  On firmware
@@ -38,6 +39,12 @@ constexpr uint32_t QM_STEP1_BLOCK = 256;  // 64- and 128-thread blocks measured 
 // change on well under 1 % of the steps.  11 instructions more behind the row stores, 2-3 VGPRs more; written bytes 46.8 -> 41.1 B per env (PMC),
 // 2.675 -> 2.613 us per step at B = 65 536 (profiles/r09/NUMBERS.md; the kernel's own clock rises 1.24 -> 1.29 us: the gain is the launch boundary).
 // Asking for the second row group only in the lanes whose qubits sit in two groups was 0.09 us SLOWER and is not done (EXPERIMENTS.md round 9).
+// Round 10 took the gate entry out of the chain: the row loads need its two groups only, and those come from one byte per action held across the wave's
+// lanes (one ds_bpermute_b32; F_GROUP_LANES and a wave with 64 live lanes, else the old path by a uniform branch) -- {action, table dword, depth, bad, done,
+// success} -> row groups -> every store, the gate entry flying beside the rows.  2.617 -> 2.557 us per step at B = 65 536, 1.285 -> 1.225 us on the kernel's own
+// clock (profiles/r10/NUMBERS.md).  Launches of more than three workgroups per compute unit keep the old path (qgym_plan.hpp group_lanes_pays): the gain shrinks
+// as waves share a SIMD and hide each other's trips, is nil at 3.5 workgroups per CU, and at four the permute costs 1.9 %.  So does a wave with fewer than
+// 64 envs -- a batch's last wave, every wave of a batch under 64.
 // LIST: also record the envs that finish, one bit each in StepArgs::done_mask (F_DONE_LIST; its own instantiation: the plain kernel's code stays as it is)
 // DENSE (qg_vec_track_dense, N == NXP, D % 16 == 0): the rows the gate rewrote also go to the resident dense int8 observation
 template <int NXP, bool HAS_Z, bool FEAT, bool LIST = false, bool DENSE = false>
@@ -48,13 +55,15 @@ __global__ __launch_bounds__(QM_STEP1_BLOCK) void qm_step1_kernel(const void *ac
     constexpr int D16 = DENSE ? R / 16 : 0;
     const Step1Front f{actions, depth, bad, gates, state, B, flags, num_actions};
     const uint64_t env = (uint64_t)blockIdx.x * QM_STEP1_BLOCK + threadIdx.x;
+    // the wave's lanes that have an env (the others do not run the body: only a wave with all 64 takes the gate's groups across lanes)
+    const uint64_t wave_envs = __builtin_amdgcn_ballot_w64(env < B);
     if constexpr (LIST) {  // every thread reaches the wave's ballot
         bool fin = false;
-        if (env < B) fin = qm_step1_mask_body<HAS_Z, FEAT, D16>(f, a, G, env);  // qm_step1.hpp
+        if (env < B) fin = qm_step1_mask_body<HAS_Z, FEAT, D16>(f, a, G, env, wave_envs);  // qm_step1.hpp
         done_mask_store(a.done_mask, B, fin, env, a.done_epoch);
     } else {
         if (env >= B) return;
-        (void)qm_step1_mask_body<HAS_Z, FEAT, D16>(f, a, G, env);  // qm_step1.hpp
+        (void)qm_step1_mask_body<HAS_Z, FEAT, D16>(f, a, G, env, wave_envs);  // qm_step1.hpp
     }
 }
 

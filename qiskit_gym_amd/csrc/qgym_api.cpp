@@ -7,6 +7,7 @@
 //   Env trait method set           rust/src/envs/clifford.rs:285-382
 // plus device memory ownership, stream-ordered launches and the hipGraph cache for rollouts.
 // There is deliberately no CPU implementation of the env in this library.
+#include <atomic>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -160,6 +161,21 @@ uint32_t reset_tree_grid(const qg_vec *v, uint32_t most) {
     return (uint32_t)std::min<uint64_t>(most, std::max<uint64_t>(captured ? std::max<uint64_t>(64ull, most / 2) : 64ull, g));
 }
 
+// compute units of a device, asked for once per device (0: not known -- no launch then takes the gate's groups across lanes)
+static uint32_t device_compute_units(int device) {
+    static std::atomic<int> known[64];
+    if (device < 0 || device >= 64) return 0;
+    int n = known[device].load(std::memory_order_relaxed);
+    if (n == 0) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+            (void)hipGetLastError();
+            n = -1;
+        }
+        known[device].store(n, std::memory_order_relaxed);
+    }
+    return n > 0 ? (uint32_t)n : 0u;
+}
+
 void fill_step_args(const qg_vec *v, StepArgs &a) {
     memset(&a, 0, sizeof a);
     a.state = v->state;
@@ -185,6 +201,7 @@ void fill_step_args(const qg_vec *v, StepArgs &a) {
     a.num_actions = (uint32_t)v->gates.size();
     a.T = 1;
     a.flags = v->plan.flags | (v->maybe_nonsymplectic ? F_GJ : 0u);
+    if (plan::group_lanes_pays(v->plan.layout, v->gates.size(), v->B, device_compute_units(v->device))) a.flags |= F_GROUP_LANES;  // (the table: qg_vec_create)
     a.sol_cap = v->sol_cap;
     a.w[0] = v->cfg.w_n_cnots;
     a.w[1] = v->cfg.w_n_layers_cnots;
@@ -476,9 +493,16 @@ int qg_vec_create(const qg_config *cfg, const qg_gate *gates, size_t n_gates, ui
         p->layers_len = 2 * N + 2;
         HIP_TRY_V(hipMalloc(&p->layers, sizeof(int32_t) * (size_t)p->layers_len * (((size_t)batch + 63) & ~(size_t)63)));  // tiles of 64 envs (layer_rec)
     }
-    HIP_TRY_V(hipMalloc(&p->d_gates, sizeof(GateEntry) * table.size()));
+    (void)device_compute_units(device);  // (asked for here, once: fill_step_args reads it on every step)
+    // Behind the gate table, at d_gates + num_actions, the packed group bytes the one-step TILE kernel holds across a wave's lanes (F_GROUP_LANES; zeros
+    // on every other layout: the kernel's address follows from the two arguments it has anyway).  With no gates the copy lands on the table's one
+    // placeholder entry: zeros over zeros, in bounds, and num_actions == 0 never reads that entry as a gate
+    uint32_t group_bytes[plan::GROUP_TABLE_DWORDS] = {};
+    if (hp.layout == LAYOUT_TILE) plan::gate_group_bytes(&table[0].ops, sizeof(GateEntry) / sizeof(uint32_t), n_gates, hp.has_z, group_bytes);
+    HIP_TRY_V(hipMalloc(&p->d_gates, sizeof(GateEntry) * table.size() + sizeof group_bytes));
     HIP_TRY_V(hipMalloc(&p->d_descs, sizeof(uint32_t) * descs.size()));
     HIP_TRY_V(hipMemcpy(p->d_gates, table.data(), sizeof(GateEntry) * table.size(), hipMemcpyHostToDevice));
+    HIP_TRY_V(hipMemcpy(p->d_gates + n_gates, group_bytes, sizeof group_bytes, hipMemcpyHostToDevice));
     HIP_TRY_V(hipMemcpy(p->d_descs, descs.data(), sizeof(uint32_t) * descs.size(), hipMemcpyHostToDevice));
     if (plan::is_tile(hp)) {  // the same gates as <= 2 row operations on tile slots (clifford.rs:89-133)
         std::vector<uint32_t> rowops(table.size(), 0u);

@@ -53,9 +53,11 @@ enum : uint32_t {
     F_TRACK = 1u << 2,     // track_solution (clifford.rs:334-340)
     F_LAYERS = 1u << 3,    // non-zero n_layers / n_layers_cnots weights: track per-qubit layers
     F_GJ = 1u << 4,        // some env may hold a non-symplectic matrix: compile in the Gauss-Jordan inversion
-    F_DONE_LIST = 1u << 5  // the one-step kernel records the envs that finish for the qg_vec_reset_done that follows (no compaction launch): TILE, TILE64
+    F_DONE_LIST = 1u << 5, // the one-step kernel records the envs that finish for the qg_vec_reset_done that follows (no compaction launch): TILE, TILE64
                            // and PauliEnv's compact step store one bit per env in StepArgs::done_mask, the sampling + step kernels append indices to
                            // StepArgs::done_list
+    F_GROUP_LANES = 1u << 6  // qm_step1_kernel takes the gate's two row groups from the packed group bytes behind the gate table, held across a wave's
+                             // lanes (qm_step1.hpp): TILE, num_actions <= 256, at most three workgroups per compute unit (qgym_plan.hpp group_lanes_pays)
 };
 
 // Layout of a done-mask buffer (StepArgs::done_mask, device_common.hpp done_mask_store) for a batch of B: W = 4 * ceil(B / 256) words (one per

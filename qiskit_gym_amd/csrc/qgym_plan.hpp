@@ -185,6 +185,34 @@ inline void copy_kernel_name(const HandlePlan &p, char *out, size_t cap) {
     if (at >= 0 && (size_t)at < cap) snprintf(out + at, cap - (size_t)at, "]");
 }
 
+// ---- the TILE gate table as the one-step kernel reads it (qm_step1_mask_body, qm_step1.hpp) ------------------------------------------------------
+// A TILE action word is q0 | q1 << 5 | M << 10: M the 4x4 GF(2) map on {X[q0], Z[q0], X[q1], Z[q1]}, bit 4 k + i = M[k][i].  A qubit's rows lie in
+// the 16-byte group q >> 1 (Z rows present: two qubits per group) or q >> 2 (X rows only: four).
+constexpr uint32_t tile_group_shift(bool has_z) { return has_z ? 1u : 2u; }
+// One byte per action, g0 | g1 << 4 (at most 8 groups), four to a dword: lane j of a wave holds dword j, so GROUP_LANES_MAX_ACTIONS actions fit.
+// The table is GROUP_TABLE_DWORDS dwords whatever num_actions is (every lane loads its dword) and lies directly behind the gate table.
+constexpr uint32_t GROUP_LANES_MAX_ACTIONS = 256, GROUP_TABLE_DWORDS = 64;
+constexpr uint32_t tile_group_byte(uint32_t ops, bool has_z) {
+    return ((ops & 31u) >> tile_group_shift(has_z)) | ((((ops >> 5) & 31u) >> tile_group_shift(has_z)) << 4);
+}
+// `ops`: the table's action words, `stride` uint32 apart (GateEntry: 2); out[GROUP_TABLE_DWORDS]
+inline void gate_group_bytes(const uint32_t *ops, size_t stride, size_t num_actions, bool has_z, uint32_t *out) {
+    for (uint32_t j = 0; j < GROUP_TABLE_DWORDS; ++j) out[j] = 0;
+    for (size_t i = 0; i < num_actions && i < GROUP_LANES_MAX_ACTIONS; ++i) out[i >> 2] |= tile_group_byte(ops[i * stride], has_z) << (8u * (i & 3u));
+}
+
+// ... and when the kernel uses it (F_GROUP_LANES): the table must hold every action, and the launch must be at most three workgroups of the one-step
+// kernel (256 envs, four waves) per compute unit.  At one wave per SIMD the lane's chain of memory trips is what a step costs and the table takes one
+// out of it; with more waves per SIMD they hide each other's trips and the permute's instructions are only cost.  Measured on MI355X (256 CUs; µs per
+// step, parent -> with the table; profiles/r10/NUMBERS.md): 65 536 envs 2.617 -> 2.557, 98 304 3.297 -> 3.157, 131 072 3.751 -> 3.717, 163 840
+// 4.502 -> 4.428, 196 608 4.936 -> 4.821, 229 376 5.653 -> 5.653 (3.5 per CU: break-even), 262 144 6.116 -> 6.232 (four per CU: 1.9 % slower).
+constexpr uint64_t GROUP_LANES_ENVS_PER_WORKGROUP = 256;  // QM_STEP1_BLOCK (kernels_qm_step1.hip)
+constexpr uint64_t GROUP_LANES_WORKGROUPS_PER_CU = 3;
+inline bool group_lanes_pays(Layout layout, size_t num_actions, uint64_t batch, uint32_t compute_units) {
+    return layout == LAYOUT_TILE && num_actions <= GROUP_LANES_MAX_ACTIONS &&
+           batch <= GROUP_LANES_WORKGROUPS_PER_CU * GROUP_LANES_ENVS_PER_WORKGROUP * compute_units;
+}
+
 // ---- step kernels ------------------------------------------------------------------------------------------------------------------
 enum StepKernel {
     SK_INVALID = 0,

@@ -143,17 +143,25 @@ __device__ inline int64_t action_value(int32_t lo, int32_t hi, bool act64) {
 // dense int8 observation -- <= 4 rows of D bytes instead of the D * D bytes a full qg_vec_observe_dense writes.
 // The dependent memory round trips of a lane are four: {action, depth, bad, done, success} issued back to back, the action first -- the gate entry (unconditional,
 // clamped index: an out-of-range action reads entry 0 and is given "no gate, penalty 0" afterwards, clifford.rs:324) needs the action alone; the
-// <= 2 row groups; every store.  depth and bad are pinned where the gate entry is consumed: left alone the compiler sinks their first use below the
+// <= 2 row groups; every store.  Three where the wave holds the gates' group bytes across its lanes (F_GROUP_LANES, below): the row loads then leave behind a
+// permute, and the gate entry flies beside them.  depth and bad are pinned where the gate entry is consumed: left alone the compiler sinks their first use below the
 // row stores and waits there for ALL outstanding memory operations -- the output stores then leave only after the row stores have been acknowledged.
 // Between those waits a lone wave pays every instruction, so the gate's arithmetic runs on lane masks (GateMasks) decoded while the row loads fly,
 // and what depends on `env` alone is computed under the earlier loads.  Everything here depends on statement order.
 template <bool HAS_Z, bool FEAT, int D16>
-__device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a, uint32_t G, uint64_t env) {
+__device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a, uint32_t G, uint64_t env, uint64_t wave_envs) {
     const uint32_t lane = (uint32_t)env & (QG_WAVE - 1);
     uint4 *tile = reinterpret_cast<uint4 *>(f.state) + (env >> 6) * (uint64_t)(G * 64);
     uint4 *tile_lane = tile + lane;  // the env's place in its tile, in registers before the gate entry is there
     int32_t act_lo = 0, act_hi = 0;
     action_issue(f.actions, env, f.flags & F_ACT64, act_lo, act_hi);
+    // Whether this wave takes the gate's groups across its lanes (below): the flag, and all 64 lanes with an env.  One SGPR, one uniform branch.
+    uint32_t group_lanes = ((uint32_t)__builtin_popcountll(wave_envs) >> 6) & (f.flags / F_GROUP_LANES);
+    asm volatile("" : "+s"(group_lanes));
+    // ... then the group bytes of four actions, lane j holding those of actions 4 j .. 4 j + 3 (the table lies behind the gate table: gate_group_bytes,
+    // qgym_plan.hpp; 64 dwords whatever num_actions is, so every lane's load is in bounds): with the first trip, from an address that depends on the lane alone
+    // (by every wave, also one that does not use it: the load under the branch measured 0.03 us per step slower at 65 536 envs)
+    const uint32_t gtab = reinterpret_cast<const uint32_t *>(f.gates + f.num_actions)[lane];
     int32_t depth0 = f.depth[env];
     uint32_t bad0 = f.bad[env];
     // done and success as memory holds them (a caller may have written either): the stores below leave only where the step changes them.  Two
@@ -163,8 +171,11 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     uint32_t done0 = a.done[env], success0 = a.success[env];
     int32_t sol_n = (FEAT && (f.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
     // what depends on `env` alone is computed here, under these loads: the env's place in its tile now (`state` is a preloaded argument), the
-    // output addresses under the gate entry's load below -- not between the gate entry's arrival and the row loads, or in front of the stores
+    // output addresses under the row loads below -- not between the action's arrival and the row loads, or in front of the stores
     asm volatile("" : "+v"(tile_lane));
+    // (the StepArgs fields the rest of the chain reads are asked for here, with done's and success's: one batch of scalar loads, one wait -- none of
+    // their cold lines is fetched behind the action's arrival)
+    asm volatile("" : : "s"(a.N), "s"(a.rewards_seq), "s"(a.dones_seq), "s"(a.reward), "s"(a.kclk_waves));
     __builtin_amdgcn_sched_barrier(0);  // (compiler only: the loads above are issued before anything uses the action -- the gate entry's load waits for it alone)
     const int64_t act = action_value(act_lo, act_hi, f.flags & F_ACT64);
     const bool in_range = (uint64_t)act < (uint64_t)f.num_actions;  // gateset.get(action) (clifford.rs:324): 0 <= act < num_actions
@@ -172,6 +183,30 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     asm volatile("" : "+v"(gi));  // (compiler only: the load stays unconditional, in one block with what runs under it)
     const GateEntry entry = f.gates[gi];
     __builtin_amdgcn_sched_barrier(0);
+    // The row loads need the gate's two groups and nothing else of its entry.  Where the wave holds the group bytes across its lanes (F_GROUP_LANES:
+    // num_actions <= 256, and every lane of the wave live -- a lane past the batch's end has not loaded its dword, and a permute reads 0 from a lane
+    // that is switched off) one ds_bpermute_b32 by act >> 2 and two v_bfe give them ~100 cycles behind the action: the gate entry's load flies beside
+    // the row loads, not in front of them.  Otherwise (a uniform branch) the groups come from the entry, behind its wait, as before round 10.
+    constexpr uint32_t gsh = HAS_Z ? 1u : 2u;
+    uint32_t g0, g1;
+    if (__builtin_expect(group_lanes != 0u, 1)) {
+        uint32_t gb = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(gi & ~3u), (int)gtab);
+        gb = in_range ? gb : 0u;  // out of range: "no gate" on qubit 0, groups 0 / 0
+        const uint32_t sh = (gi << 3) & 24u;
+        g0 = __builtin_amdgcn_ubfe(gb, sh, 4u); g1 = __builtin_amdgcn_ubfe(gb, sh + 4u, 4u);
+    } else {
+        // (compiler only: a value of its own -- written as the select below, that select and the gate entry's wait are hoisted in front of this branch)
+        uint32_t ops_e = entry.ops;
+        asm volatile("" : "+v"(ops_e));
+        ops_e = in_range ? ops_e : 0u;
+        g0 = (ops_e & 31u) >> gsh; g1 = ((ops_e >> 5) & 31u) >> gsh;
+    }
+    uint4 *pa = tile_lane + g0 * 64, *pb = tile_lane + g1 * 64;
+    // (both groups by every lane, also where they are one: the second load under the execution mask of the lanes with two groups -- no request
+    // from the others, which then take `ub` from `ua` behind the wait -- measured 0.09 us per step SLOWER at 65 536 envs: six instructions more in
+    // front of the second load, four selects behind the wait, one wait for both groups.  EXPERIMENTS.md round 9)
+    uint4 ua = global_load4(pa), ub = global_load4(pb);
+    __builtin_amdgcn_sched_barrier(0);  // (compiler only: everything down to the next one stands between the loads and their wait)
     // the addresses of the five per-env outputs (as integers: the two sequence arrays may be null)
     uintptr_t out_reward = reinterpret_cast<uintptr_t>(a.reward + env), out_done = reinterpret_cast<uintptr_t>(a.done + env);
     uintptr_t out_success = reinterpret_cast<uintptr_t>(a.success + env);
@@ -198,14 +233,7 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     const bool layered = FEAT && (f.flags & F_LAYERS) && in_range;
     LayerTxn lt;
     if (layered) lt = layers_begin(layer_rec(a.layers, env, 2 * a.N + 2), a.N, a.descs[act]);  // its loads fly with the state's
-    constexpr uint32_t gsh = HAS_Z ? 1u : 2u;
-    const uint32_t ops = g.ops, q0 = ops & 31u, q1 = (ops >> 5) & 31u, g0 = q0 >> gsh, g1 = q1 >> gsh;
-    uint4 *pa = tile_lane + g0 * 64, *pb = tile_lane + g1 * 64;
-    // (both groups by every lane, also where they are one: the second load under the execution mask of the lanes with two groups -- no request
-    // from the others, which then take `ub` from `ua` behind the wait -- measured 0.09 us per step SLOWER at 65 536 envs: six instructions more in
-    // front of the second load, four selects behind the wait, one wait for both groups.  EXPERIMENTS.md round 9)
-    uint4 ua = global_load4(pa), ub = global_load4(pb);
-    __builtin_amdgcn_sched_barrier(0);  // (compiler only: everything down to the next one stands between the loads and their wait)
+    const uint32_t ops = g.ops, q0 = ops & 31u, q1 = (ops >> 5) & 31u;
     GateMasks<HAS_Z> gm(ops, g0, g1);
     uint32_t e0[4], e1[4];  // the put-back's masks: gate_put
 #pragma unroll
@@ -238,7 +266,9 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     ua.z = bit_select(gm.same, ub.z, ua.z); ua.w = bit_select(gm.same, ub.w, ua.w);
     gate_put<HAS_Z>(ua, e0, nx0, nz0);
     // (one group: q0's store carries q1's rows too.  Storing them twice, to spare this branch, measured 0.17 us per step SLOWER at 65 536 envs:
-    // 47 % of the line gateset's actions stay in one group, and the launch ends when its stores have drained -- EXPERIMENTS.md round 7)
+    // 128 of the line gateset's 170 actions (75 %) stay in one group, and the launch ends when its stores have drained -- EXPERIMENTS.md round 7.
+    // The two stores split by the group's parity instead -- no 128-byte line asked for twice, 47.3 line requests a wave instead of 56.1 -- measured
+    // no faster: EXPERIMENTS.md round 10)
     if (apart) global_store4(pb, ub);
     global_store4(pa, ua);
     if constexpr (D16 > 0) {  // the rows that changed: stored below ("no gate" changes none)
