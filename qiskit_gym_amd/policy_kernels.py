@@ -129,7 +129,9 @@ def beam_advance(parent: torch.Tensor, ret_in: torch.Tensor, reward: torch.Tenso
     equals) becomes the winner if its return is strictly above `best[g]` -- `best`, `found` are updated IN PLACE and `win_src[g]` is its env
     index for `VecEnv.copy_envs`, else `skip` --; `live` (IN PLACE) loses the slots that are `done`.  mode "stop" / "prune" (None: neither)
     then apply the bound in groups that have a winner: a live slot is hopeful when `ret_out[b] + bonus > best[g]`; "stop" ends a group's
-    beams once none is hopeful, "prune" ends every hopeless beam; `bounded[g]` (optional, int32 [B // width]) is added to.
+    beams once none is hopeful, "prune" ends every hopeless beam; `bounded[g]` (optional, int32 [B // width]) is added to.  Contract:
+    finite returns (the envs' rewards are).  A solved slot whose return is NaN or -inf has no order word and is no pick, where an `argmax`
+    over the scores would have let it shadow its group.
     parent: int32 [B]; ret_in, reward: f32 [B]; success, done, live: uint8 / bool [B]; best: f32 [B // width]; found: uint8 / bool [B // width].
     Returns (ret_out f32 [B] -- not `ret_in` itself --, win_src int32 [B // width], group_live uint8 [B // width]: the live slots left)."""
     B, dev, W = parent.numel(), parent.device, int(width)

@@ -32,7 +32,8 @@ How the policy's opinion about a handle's current state is obtained is one decis
 object (`_TorchForward`, `_KernelForward`) for the row of log-probabilities, the arg-max or the draw, and know nothing else about it.  The
 kernels' operands are a snapshot of the weights (`_Packed`: the `policy_kernels.PolicyOperands` the collector also holds, plus the version
 counters they were taken at); the first layer packed through a handle (`policy_kernels.first_layer` names its route) stays with the
-handle's owner (`_Handles.first`) and goes when the handle is closed or the snapshot dropped.
+handle's owner (`_Handles.first`) and goes when the handle is closed or the snapshot dropped.  What a beam search does with a step's
+results (returns, winners, `live`) is likewise one thing in every mode: `collector.beam_advance`.
 """
 from __future__ import annotations
 
@@ -296,31 +297,35 @@ class BatchedSynthesis:
         tw = torch.tensor([views[g % len(views)] for g in range(groups)], dtype=torch.int32, device=dev).repeat(M)
         return (tw if width is None else tw.repeat_interleave(width)).contiguous()
 
-    def _beam_search(self, states, fwd: _Forward, V: int, tw: Optional[torch.Tensor], W: int, merge: bool, cur: VecEnv, oth: VecEnv, win: VecEnv,
-                     bound: Optional[str] = None):
-        """The search of `solve(beam_width=W)`: `cur` and `oth` take turns, `fwd` reads whichever is current.  `tw` None: V is 1.  Else the
-        groups are the (target, view) pairs, V consecutive ones per target, each searched under its own fixed view (and with its own merge
-        history); a target's winner is the best result of its V groups, ties to the lowest view.  `bound` "stop" / "prune": returns, winners
-        and `live` come from one `beam_advance` per step, which also ends the beams that cannot beat their group's winner."""
-        targets = len(states)
+    def _beam_search(self, states, held: _Handles, views: Optional[List[int]], W: int, kernels: bool, merge: bool, bound: Optional[str]):
+        """The search of `solve(beam_width=W)` on the handles of `held`: `cur` and `oth` take turns, the forward object (`kernels`: the policy-layer
+        kernels or a ValueError, else torch) reads whichever is current.  `views` None: one group per target.  Else the groups are the (target,
+        view) pairs, V consecutive ones per target, each under its own fixed view (and with its own merge history); a target's winner is the best
+        of its V groups, ties to the lowest view.  Returns, winners and `live`: one `beam_advance` per step in mode `bound` (in place on them)."""
+        cur, oth, win = held.vecs
+        targets, V = len(states), 1 if views is None else len(views)
         M = targets * V  # groups
         B, A, dev = cur.batch, cur.num_actions(), cur.device
         T = int(cur._cfg.max_depth)
+        tw = None if views is None else self._twist_index(views, V, targets, W, dev)
+        if bound is not None:  # the handle's config: the caller's metrics weights over the reference's defaults
+            low = {k: float(getattr(cur._cfg, "w_" + k)) for k in ("n_cnots", "n_layers_cnots", "n_layers", "n_gates")}
+            low = {k: w for k, w in low.items() if not w >= 0.0}
+            if low:
+                raise ValueError(f"bound needs rewards that cannot exceed 1: every metrics weight must be >= 0, got {low}")
+        fwd = self._forward(held, 2, tw, kernels, rows=True)
         self._load(win, states, V)  # the targets once per group; a group nobody solves keeps its slot, a solved one is overwritten by its winner
-        group = torch.arange(M, dtype=torch.int32, device=dev)
-        cur.copy_envs(win, group.repeat_interleave(W))
-        found = win.success.bool().clone()  # a target that is already solved needs no gates: its winner is the target itself
-        best = torch.where(found, 0.0, -float("inf")).to(torch.float32)
+        cur.copy_envs(win, torch.arange(M, dtype=torch.int32, device=dev).repeat_interleave(W))
+        found = win.success.bool().to(torch.uint8)  # a target that is already solved needs no gates: its winner is the target itself
+        best = torch.where(found.bool(), 0.0, -float("inf")).to(torch.float32)
         live = torch.zeros((M, W), dtype=torch.uint8, device=dev)
-        live[:, 0] = (~found).to(torch.uint8)
+        live[:, 0] = 1 - found
         live = live.view(B)
         cum = torch.zeros(B, dtype=torch.float32, device=dev)
-        ret = torch.zeros(B, dtype=torch.float32, device=dev)
-        nowhere = torch.full((M,), B, dtype=torch.int32, device=dev)  # out of range as a copy source: that entry is skipped
+        ret, spare = torch.zeros(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)  # the returns alternate between two buffers
+        win_src, group_live = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, dtype=torch.uint8, device=dev)
+        bounded = None if bound is None else torch.zeros(M, dtype=torch.int32, device=dev)
         steps = 0
-        if bound is not None:  # beam_advance updates best, found and live in place; the returns alternate between two buffers
-            found_u8, spare, bounded = found.view(torch.uint8), torch.empty_like(ret), torch.zeros(M, dtype=torch.int32, device=dev)
-            win_src, group_live = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, dtype=torch.uint8, device=dev)
         if merge:  # the targets' own keys open the histories (one live slot per unsolved target: nothing to drop), so coming back to a target is a revisit
             cap = T * W + 1  # a step adds at most W keys per target: the history of a search never fills
             seen, dropped = beam_seen(M, cap, dev), torch.zeros((M, 2), dtype=torch.int32, device=dev)
@@ -331,22 +336,13 @@ class BatchedSynthesis:
             fwd.real_actions(cur, act)  # a child lives in its parent's group, hence under its view
             oth.copy_envs(cur, parent)
             oth.step(act)
-            if bound is None:
-                ret = ret[parent.long()] + oth.reward  # the return `solve` ranks by: the parent's plus this step's reward
-                solved = (live.bool() & oth.success.bool()).view(M, W)
-                live = live & (1 - oth.done)
-                score, j = _winner(solved, ret.view(M, W))  # the lowest slot among equals
-                val = score.gather(1, j.view(M, 1)).view(M)
-                better = val > best
-                win.copy_envs(oth, torch.where(better, group * W + j.to(torch.int32), nowhere))
-                best = torch.where(better, val, best)
-                found |= better
-            else:  # the same in one launch, and the bound: no reward after this step exceeds 1.0 in total (`solve` has checked the weights)
-                prev = ret
-                ret = beam_advance(parent, prev, oth.reward, oth.success, oth.done, live, best, found_u8, W, skip=B, bonus=1.0, mode=bound,
-                                   ret_out=spare, win_src=win_src, group_live=group_live, bounded=bounded)[0]
-                spare = prev
-                win.copy_envs(oth, win_src)  # B, out of range, where the winner stays
+            # The return `solve` ranks by is the parent's plus this step's reward.  A slot that is not live gets 0 instead: it is never a parent
+            # (`beam_select` gives a dead slot its own index and live = 0) and never solved (live & success), so nothing reads it.  The bound, if
+            # any: no reward after this step exceeds 1.0 in total (the weights are checked above); mode None reads neither bonus nor `bounded`.
+            beam_advance(parent, ret, oth.reward, oth.success, oth.done, live, best, found, W, skip=B, bonus=1.0, mode=bound, ret_out=spare,
+                         win_src=win_src, group_live=group_live, bounded=bounded)
+            ret, spare = spare, ret
+            win.copy_envs(oth, win_src)  # B, out of range and skipped, where the winner stays
             if merge:  # beams that ended (the step's results among them) have left `live`: they are neither merged nor recorded
                 live = beam_merge(oth.observe_packed(out=words), cum, live, W, seen, cap, dropped=dropped)
             cur, oth = oth, cur
@@ -356,12 +352,10 @@ class BatchedSynthesis:
         for v in (cur, oth, win):
             v.sync()
         sols, lens = win.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
+        ok = found.bool().cpu().numpy()
         if tw is not None:  # per target the best of its V groups, the lowest view among equals
-            pick = (torch.arange(targets, device=dev) * V + _winner(found.view(targets, V), best.view(targets, V))[1]).cpu().numpy()
-            ok = found.cpu().numpy()[pick]
-            sols, lens = sols[pick], lens[pick]
-        else:
-            ok = found.cpu().numpy()
+            pick = (torch.arange(targets, device=dev) * V + _winner(found.bool().view(targets, V), best.view(targets, V))[1]).cpu().numpy()
+            ok, sols, lens = ok[pick], sols[pick], lens[pick]
         out = [[int(x) for x in sols[m, : lens[m]]] if ok[m] else None for m in range(targets)]
         gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
         self.last_stats = {"beam_width": W, "targets": targets, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0}
@@ -414,8 +408,8 @@ class BatchedSynthesis:
         hopeless they all leave; this returns exactly what bound=None returns, in fewer steps where every target has found its winner early
         -- the loop still ends only when no beam is left anywhere, looked at every 8th step, so a target nobody solves keeps it running to
         max_depth.  "prune": every hopeless beam leaves on its own and its slot goes to other continuations of the target; like
-        merge_duplicates this may change which targets are solved and with how many gates, either way.  Either mode also replaces the
-        step's bookkeeping (returns, winners, `live`) by one kernel, `collector.beam_advance`, and combines with fast, twists,
+        merge_duplicates this may change which targets are solved and with how many gates, either way.  Every beam search, bounded or not, does the
+        step's bookkeeping (returns, winners, `live`) in one kernel, `collector.beam_advance`; either mode combines with fast, twists,
         twist_kernels and merge_duplicates.  `last_stats` gains "bound" (the mode) and "bounded" (beams ended by the bound).  ValueError:
         without beam_width, an unknown mode, a metrics weight below 0 (the bound needs rewards that cannot exceed 1), or PauliGym -- its step
         adds pauli_layer_reward per released rotation (pauli.rs:634) and a target may hold rotations beyond the observed columns, so the
@@ -444,6 +438,19 @@ class BatchedSynthesis:
         ValueError: without `twists`, together with `fast=True`, on PauliGym, with a policy that is not a `BasicPolicy` of the kernels'
         shape, or an observation of more than 64 columns."""
         M = len(states)
+        self._check_options(M == 0, fast, beam_width, merge_duplicates, twists, twist_kernels, bound)
+        if M == 0:
+            return []
+        views = None if twists is None else self._views(int(twists))
+        if beam_width is None:
+            return self._sampled_search(states, deterministic, num_searches, fast, views, twist_kernels)
+        W, groups = int(beam_width), M * (1 if views is None else len(views))
+        held = self._handles("beam", (groups * W, groups * W, groups), views is not None)
+        return self._beam_search(states, held, views, W, bool(twist_kernels) or fast is True, bool(merge_duplicates), bound)  # kernels: on request only
+
+    def _check_options(self, empty: bool, fast, beam_width, merge_duplicates, twists, twist_kernels, bound):
+        """ValueError for a combination of `solve`'s options that does not exist; what needs a handle's config (the metrics weights under `bound`)
+        or the policy (`fast`, `twist_kernels`) is checked where those are at hand.  `empty`: no targets, only the checks on the views are made."""
         if twist_kernels and twists is None:
             raise ValueError("twist_kernels=True needs twists: it is the kernel path of a search under symmetry views")
         if twists is not None:
@@ -454,8 +461,8 @@ class BatchedSynthesis:
             if fast:
                 raise ValueError("fast=True cannot be combined with twists: the policy-layer kernels read the resident state, not a view"
                                  " (twist_kernels=True runs a twisted search on the kernels)")
-        if M == 0:
-            return []
+        if empty:
+            return
         if beam_width is not None:
             if int(beam_width) < 1:
                 raise ValueError("beam_width must be at least 1")
@@ -471,20 +478,11 @@ class BatchedSynthesis:
             if self.env.env_kind == "pauli":
                 raise ValueError("bound: a PauliGym step adds pauli_layer_reward per released rotation (pauli.rs:634), and a target may hold rotations "
                                  "beyond the observed columns: the reward still to come has no bound the search can see")
-        views = None if twists is None else self._views(int(twists))
-        V = 1 if views is None else len(views)
-        if beam_width is not None:
-            W = int(beam_width)
-            held = self._handles("beam", (M * V * W, M * V * W, M * V), views is not None)
-            cur, oth, win = held.vecs
-            tw = None if views is None else self._twist_index(views, V, M, W, cur.device)
-            if bound is not None:  # the handle's config: the caller's metrics weights over the reference's defaults
-                low = {k: float(getattr(cur._cfg, "w_" + k)) for k in ("n_cnots", "n_layers_cnots", "n_layers", "n_gates")}
-                low = {k: w for k, w in low.items() if not w >= 0.0}
-                if low:
-                    raise ValueError(f"bound needs rewards that cannot exceed 1: every metrics weight must be >= 0, got {low}")
-            fwd = self._forward(held, 2, tw, bool(twist_kernels) or fast is True, rows=True)  # on request only: the kernels or a ValueError
-            return self._beam_search(states, fwd, V, tw, W, bool(merge_duplicates), cur, oth, win, bound)
+
+    def _sampled_search(self, states, deterministic: bool, num_searches: int, fast: Optional[bool], views: Optional[List[int]], twist_kernels: bool):
+        """The sampled and the greedy search of `solve`: every (target, search) pair is one env of the "search" handle, one view per search;
+        per target the successful search of the highest return wins.  PauliGym: the winners are replayed for their rotation markers."""
+        M, V = len(states), 1 if views is None else len(views)
         S = 1 if deterministic else max(1, int(num_searches))  # greedy episodes are all alike
         if views is not None and deterministic:
             S = V  # ... but for the view they are seen through

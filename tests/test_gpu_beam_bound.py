@@ -156,6 +156,8 @@ def _winner(solved, ret):
 
 @pytest.mark.parametrize("W,groups", [(1, 300), (4, 1024), (16, 257), (64, 33)])
 def test_mode_none_against_the_torch_lines_it_replaces(W, groups):
+    """The search runs the kernel in every mode now: the torch lines below, with this file's `_winner`, are the only restatement left of
+    what `bound=None` once ran per step."""
     M, B = groups, groups * W
     rng = np.random.default_rng(W + groups)
     x = make_inputs(rng, W, groups, 0)
@@ -167,7 +169,7 @@ def test_mode_none_against_the_torch_lines_it_replaces(W, groups):
     group = torch.arange(M, dtype=torch.int32, device="cuda")
     nowhere = torch.full((M,), B, dtype=torch.int32, device="cuda")
     got = run_kernel(d, W, None)
-    # ---- the lines of BatchedSynthesis._beam_search between `oth.step(act)` and the merge, as they stand for bound=None
+    # ---- the lines of BatchedSynthesis._beam_search between `oth.step(act)` and the merge, as they stood for bound=None
     live_in = live
     ret = ret[parent.long()] + reward
     solved = (live.bool() & success.bool()).view(M, W)

@@ -178,7 +178,8 @@ def bound_table(M: int, difficulty: int, widths, reps: int = 3):
 
 
 def torch_advance(parent, ret, reward, success, done, live, best, found, W, group, nowhere):
-    """The lines of `BatchedSynthesis._beam_search` that `beam_advance` stands for (bound=None), up to the source index of the winners' copy."""
+    """The lines that `BatchedSynthesis._beam_search` ran for bound=None before `beam_advance` took their place, up to the source index of the
+    winners' copy: the record of what the launch replaced."""
     M = best.shape[0]
     ret = ret[parent.long()] + reward
     solved = (live.bool() & success.bool()).view(M, W)

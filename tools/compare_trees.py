@@ -143,7 +143,8 @@ def dump_searches(M):
     from qiskit_gym_amd.synthesis import BatchedSynthesis
 
     modes = [dict(num_searches=4), dict(num_searches=8), dict(deterministic=True), dict(beam_width=2), dict(beam_width=2, merge_duplicates=True),
-             dict(beam_width=4), dict(beam_width=4, merge_duplicates=True)]
+             dict(beam_width=4), dict(beam_width=4, merge_duplicates=True), dict(beam_width=4, bound="stop"), dict(beam_width=4, bound="prune"),
+             dict(beam_width=4, merge_duplicates=True, bound="stop")]
     out = {}
 
     def run(label, syn, states, calls):
