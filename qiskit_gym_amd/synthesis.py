@@ -375,6 +375,10 @@ class BatchedSynthesis:
               beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None,
               twist_kernels: bool = False, bound: Optional[str] = None) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
+        The rules of the sampled and the greedy search -- env m * S + s is search s of target m, the draw of step t is the race of
+        `sample_actions(logits, seed, t)`, a finished env gets no gate and adds no reward, the loop ends at the first step t with
+        t % 8 == 7 and every env finished, the winner is the successful search of the greatest f32 return, the lowest s among equals --
+        are stated in tests/searchmodel.py, which tests/test_gpu_sampled_search.py holds every draw and every answer against.
         fast: run the forward pass on the policy-layer kernels (bf16 products, f32 accumulation; `last_stats["kernels"]` says whether they
         ran).  Sampled searches: forward pass and draw (default, fast=None: when the kernels apply and the batch has at least 4 096 envs).
         deterministic=True and beam_width: only on fast=True (None and False: the torch forward in `dtype`) -- the greedy step takes the
