@@ -67,11 +67,39 @@ __global__ __launch_bounds__(QM_STEP1_BLOCK) void qm_step1_kernel(const void *ac
     }
 }
 
+// The straight-line form (round 11; F_STEP1_STRAIGHT, chosen per launch by qgym_plan.hpp step1_straight): the kernel above decides in every wave of every
+// launch what the host knows before the launch -- the action width, whether the wave takes the gate's groups across lanes, whether the two sequence
+// arrays are null, whether a kernel clock is attached -- and builds ten 64-bit per-lane addresses with vector arithmetic.  A launch with int32 actions,
+// B % 64 == 0, num_actions <= 256, group_lanes_pays, no rewards_seq / dones_seq, no kernel clock attached, and none of FEAT, LIST, DENSE runs this kernel
+// instead: one action load, the permute unconditional, no sequence stores, no KernelClock (neither a.kclk nor a.kclk_waves is read; nothing between the last
+// output store and s_endpgm), and every per-lane address a shared 32-bit offset from an SGPR base (qm_step1_straight_body, qm_step1.hpp).  Every other
+// launch -- a handle with a kernel clock, rollout(..., rewards_out=...), int64 actions, a ragged batch, more than 256 actions, more than three workgroups
+// per compute unit -- runs the kernel above exactly as before.  The leading parameters are the same 14 dwords (flags is not read).
+// What that is worth, measured part by part (profiles/r11/NUMBERS.md): the branch, the sequence code and the clock nothing that can be told from the spread
+// (they are gone because under that predicate they cannot run); everything in front of the action's load and right behind its arrival, all of it.  The
+// action's load is the head of the lane's chain, so it is issued first -- 5 instructions from the entry where the kernel above has 21 -- and the entry's index
+// behind it is one v_min_u32 (qm_step1_straight_body).  260 -> 175 instructions, 71 -> 54 VGPRs (profiles/r11/qm_step1_listing.txt); 2.555 -> 2.512 us per step
+// at B = 65 536 (two more sessions 2.564 -> 2.518, 2.562 -> 2.516), the same vector loads and the same stored bytes.
+template <int NXP, bool HAS_Z>
+__global__ __launch_bounds__(QM_STEP1_BLOCK) void qm_step1_straight_kernel(const void *actions, int32_t *depth, uint32_t *bad, const GateEntry *gates, void *state,
+                                                                            uint64_t B, uint32_t flags, uint32_t num_actions, StepArgs a) {
+    constexpr int R = HAS_Z ? 2 * NXP : NXP, G = R / 4;
+    const Step1Front f{actions, depth, bad, gates, state, B, flags, num_actions};
+    const uint32_t env = blockIdx.x * QM_STEP1_BLOCK + threadIdx.x;
+    if (env >= (uint32_t)B) return;  // B % 64 == 0: a wave leaves as a whole or not at all
+    qm_step1_straight_body<HAS_Z>(f, a, G, env);  // qm_step1.hpp
+}
+
 template <int NXP, bool HAS_Z>
 static hipError_t launch_step1(const StepArgs &a, hipStream_t s) {
     const dim3 grid((unsigned)((a.B + QM_STEP1_BLOCK - 1) / QM_STEP1_BLOCK)), block(QM_STEP1_BLOCK);
     const bool feat = a.flags & (F_TRACK | F_LAYERS);
     const bool list = a.flags & F_DONE_LIST;
+    if (a.flags & F_STEP1_STRAIGHT) {  // (the plan sets it only without FEAT, LIST and DENSE)
+        if (feat || list || a.dense || a.rewards_seq || a.dones_seq || a.kclk || (a.flags & F_ACT64) || a.B % 64u) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((qm_step1_straight_kernel<NXP, HAS_Z>), grid, block, 0, s, a.actions, a.depth, a.bad, a.gates, a.state, a.B, a.flags, a.num_actions, a);
+        return hipGetLastError();
+    }
 #define QM_STEP1_LAUNCH(...) \
     hipLaunchKernelGGL((qm_step1_kernel<NXP, HAS_Z, __VA_ARGS__>), grid, block, 0, s, a.actions, a.depth, a.bad, a.gates, a.state, a.B, a.flags, a.num_actions, a)
     constexpr int R = HAS_Z ? 2 * NXP : NXP;

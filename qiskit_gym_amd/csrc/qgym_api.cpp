@@ -351,6 +351,11 @@ static hipError_t launch_step(const qg_vec *v, const StepArgs &a_in, hipStream_t
     StepArgs a = a_in;
     a.kclk = kernel_clock_slot(v);
     a.kclk_waves = v->kclk_waves;
+    // (everything the choice reads is part of a cached graph's key -- the flags with the action width, the two sequence pointers, the tracked observation --
+    // or drops the graphs when it changes: qg_vec_set_kernel_clock)
+    if (a.T == 1 && a.bad && plan::step1_straight(v->plan.layout, a.flags, a.num_actions, a.B, device_compute_units(v->device),
+                                                  a.rewards_seq || a.dones_seq, v->kclk != nullptr, a.dense != nullptr))
+        a.flags |= F_STEP1_STRAIGHT;
     switch (v->plan.layout) {
     case LAYOUT_LFD: return lfd_step(a, v->plan.w64, v->plan.nxp, s);
     case LAYOUT_LF8: return lf8_step(a, a.T > 1, s);

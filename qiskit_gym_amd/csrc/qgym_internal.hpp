@@ -56,8 +56,10 @@ enum : uint32_t {
     F_DONE_LIST = 1u << 5, // the one-step kernel records the envs that finish for the qg_vec_reset_done that follows (no compaction launch): TILE, TILE64
                            // and PauliEnv's compact step store one bit per env in StepArgs::done_mask, the sampling + step kernels append indices to
                            // StepArgs::done_list
-    F_GROUP_LANES = 1u << 6  // qm_step1_kernel takes the gate's two row groups from the packed group bytes behind the gate table, held across a wave's
+    F_GROUP_LANES = 1u << 6, // qm_step1_kernel takes the gate's two row groups from the packed group bytes behind the gate table, held across a wave's
                              // lanes (qm_step1.hpp): TILE, num_actions <= 256, at most three workgroups per compute unit (qgym_plan.hpp group_lanes_pays)
+    F_STEP1_STRAIGHT = 1u << 7  // this env.step() launch runs qm_step1_straight_kernel, the one-step kernel without the arms whose choice the host has made
+                                // (qgym_plan.hpp step1_straight; set per launch, behind the kernel clock's slot: qgym_api.cpp launch_step)
 };
 
 // Layout of a done-mask buffer (StepArgs::done_mask, device_common.hpp done_mask_store) for a batch of B: W = 4 * ceil(B / 256) words (one per

@@ -213,6 +213,22 @@ inline bool group_lanes_pays(Layout layout, size_t num_actions, uint64_t batch, 
            batch <= GROUP_LANES_WORKGROUPS_PER_CU * GROUP_LANES_ENVS_PER_WORKGROUP * compute_units;
 }
 
+// ... and when an env.step() launch takes the straight-line form of the one-step kernel (qm_step1_straight_kernel, F_STEP1_STRAIGHT): every choice the
+// generic kernel makes per launch from values that are the same in all its waves is known here, so that form carries none of them -- int32 actions, whole
+// waves only (a wave past the batch's end leaves as a whole), the gate's groups across lanes in every wave, no rewards_seq / dones_seq log, no kernel clock, and
+// neither a solution log, layer metrics, a done list nor a tracked dense observation.  Its per-lane addresses are 32-bit offsets from uniform bases:
+// the batch limit of group_lanes_pays keeps them small on any real device, STEP1_STRAIGHT_MAX_ENVS bounds them whatever the device reports
+// (the largest: 16 B x 8 groups per env of the tile, 2^31 bytes at the limit).
+// `flags`: the launch's StepArgs::flags; `seq_outputs`: rewards_seq or dones_seq given; `clock_attached`: qg_vec_set_kernel_clock holds slots;
+// `dense`: the launch keeps a tracked dense observation current.
+constexpr uint64_t STEP1_STRAIGHT_MAX_ENVS = 1ull << 24;
+inline bool step1_straight(Layout layout, uint32_t flags, size_t num_actions, uint64_t batch, uint32_t compute_units, bool seq_outputs, bool clock_attached,
+                           bool dense) {
+    return layout == LAYOUT_TILE && !(flags & (F_ACT64 | F_INVERTS | F_TRACK | F_LAYERS | F_DONE_LIST)) && !dense && batch % 64u == 0 &&
+           batch <= STEP1_STRAIGHT_MAX_ENVS && num_actions <= GROUP_LANES_MAX_ACTIONS && group_lanes_pays(layout, num_actions, batch, compute_units) &&
+           !seq_outputs && !clock_attached;
+}
+
 // ---- step kernels ------------------------------------------------------------------------------------------------------------------
 enum StepKernel {
     SK_INVALID = 0,

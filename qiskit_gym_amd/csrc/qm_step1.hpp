@@ -1,5 +1,6 @@
-// qm_step1.hpp -- one env.step() of the TILE layout (CliffordEnv N <= 16, LinearFunctionEnv 8 < N <= 32, no add_inverts), one lane per env, in its two
-// forms: qm_step1_mask_body for qm_step1_kernel (kernels_qm_step1.hip), qm_step1_plain_body for the step lanes of qm_reset_step_kernel (kernels_qm.hip)
+// qm_step1.hpp -- one env.step() of the TILE layout (CliffordEnv N <= 16, LinearFunctionEnv 8 < N <= 32, no add_inverts), one lane per env, in its
+// forms: qm_step1_mask_body for qm_step1_kernel (kernels_qm_step1.hip), qm_step1_straight_body for qm_step1_straight_kernel (the same file: the mask body
+// without the choices the host has made before the launch), qm_step1_plain_body for the step lanes of qm_reset_step_kernel (kernels_qm.hip)
 // and for the policy kernel that samples an action and steps its env in the same launch (mid_head_sample_kernel, kernels_policy.hip).
 // Reference: Clifford::step rust/src/envs/clifford.rs:321-347.
 // The two bodies share no arithmetic on purpose: with helper lambdas in common five instantiations moved by one VGPR and one took 20 B of scratch
@@ -331,6 +332,118 @@ __device__ inline bool qm_step1_mask_body(const Step1Front &f, const StepArgs &a
     if (FEAT && (f.flags & F_TRACK)) a.sol_len[env * 2] = sol_n;
     if (FEAT && fault) atomicOr(&a.error[env], fault);
     return fin != 0;
+}
+
+// A lane's element of a per-env array as "uniform base + 32-bit lane offset": the base stays in an SGPR pair, the offset is one VGPR that every array of
+// the same element size shares (global_load / global_store with an saddr operand) -- no 64-bit per-lane address is built.  `byte_off` is zero-extended.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <class T>
+__device__ inline T lane_load(const void *base, uint32_t byte_off) { return *(global_ptr<const T>)((global_ptr<const char>)base + byte_off); }
+template <class T>
+__device__ inline void lane_store(void *base, uint32_t byte_off, T v) {
+    // (compiler only: the offset's zero extension stands in the store's own basic block -- extended in an earlier block, as for the loads, the store is
+    // selected with a 64-bit per-lane address made by one more vector add)
+    asm volatile("" : "+v"(byte_off));
+    *(global_ptr<T>)((global_ptr<char>)base + byte_off) = v;
+}
+
+// qm_step1_mask_body for the launches in which the host has made every choice that body makes from values uniform over the launch (qgym_plan.hpp
+// step1_straight; qm_step1_straight_kernel): int32 actions, every wave whole and taking the gate's groups across its lanes, no rewards_seq / dones_seq, no
+// solution log, layer metrics, done list or dense observation.  Same loads, same stores, same arithmetic, same order -- and the same results, bit for bit --
+// without the arms not taken, and with every per-lane address a 32-bit offset (`env`, 4 * env, the lane's place in its tile) from a base held in SGPRs.
+// A body of its own for the reason given at the top of this file: shared helpers move the generic instantiations' code.  Statement order is load-bearing
+// here as there.
+template <bool HAS_Z>
+__device__ inline void qm_step1_straight_body(const Step1Front &f, const StepArgs &a, uint32_t G, uint32_t env) {
+    // The action's load is the head of the chain, and what stands in front of its issue is what round 11 measured as cost (profiles/r11/NUMBERS.md: the
+    // generic kernel has 21 instructions there, the action's 64-bit address and the width's branch among them; putting those back alone gave the whole gain
+    // away).  So it is the body's first instruction but one: its offset, then the load -- (compiler only) the barrier keeps the table's address arithmetic and
+    // the other loads behind it.
+    const uint32_t at4 = env << 2;                                    // the env's 4-byte elements
+    const int32_t act = lane_load<int32_t>(f.actions, at4);
+    __builtin_amdgcn_sched_barrier(0);
+    const uint32_t lane = env & (QG_WAVE - 1);
+    uint32_t at_tile = (env >> 6) * (G * 1024u) + (lane << 4);        // the env's place in its tile (G groups of 1 KiB), group 0
+    // the group bytes of four actions, lane j holding those of actions 4 j .. 4 j + 3 (gate_group_bytes, qgym_plan.hpp)
+    const uint32_t gtab = lane_load<uint32_t>(f.gates + f.num_actions, lane << 2);
+    int32_t depth0 = lane_load<int32_t>(f.depth, at4);
+    uint32_t bad0 = lane_load<uint32_t>(f.bad, at4);
+    // done and success as memory holds them; their bases come from StepArgs, not from the preloaded arguments: (compiler only) the barrier keeps that
+    // scalar wait behind the issue of depth and bad
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t done0 = lane_load<uint8_t>(a.done, env), success0 = lane_load<uint8_t>(a.success, env);
+    asm volatile("" : "+v"(at_tile));
+    // (the StepArgs fields the back of the chain reads are asked for here, in the batch of done's and success's: none of their cold lines behind the action)
+    asm volatile("" : : "s"(a.N), "s"(a.reward));
+    __builtin_amdgcn_sched_barrier(0);  // (compiler only: the loads above are issued before anything uses the action)
+    // The gate entry's index clamped by one v_min_u32: an action out of range (negative ones are large as unsigned) reads "entry" num_actions -- the first
+    // eight bytes of the group table, which lies directly behind the gate table in the same allocation -- and is given "no gate" below whatever it read.
+    // A compare and a select in its place cost two instructions and two hazard waits between the action's arrival and the entry's load.
+    const uint32_t gi = min((uint32_t)act, f.num_actions);
+    const u32x2 entry = lane_load<u32x2>(f.gates, gi << 3);  // GateEntry {ops, penalty}; flies beside the row loads
+    __builtin_amdgcn_sched_barrier(0);
+    // the gate's two groups: one ds_bpermute_b32 by act >> 2 and two v_bfe behind the action (every lane of the wave holds its dword).  The entry's load
+    // stays in front of the permute: behind it the step measured 0.02 us slower (the masks made from the entry are the longer arm under the rows' trip)
+    uint32_t gb = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(gi & ~3u), (int)gtab);
+    const bool in_range = (uint32_t)act < f.num_actions;  // gateset.get(action) (clifford.rs:324): 0 <= act < num_actions
+    gb = in_range ? gb : 0u;  // out of range: "no gate" on qubit 0, groups 0 / 0
+    const uint32_t sh = (gi << 3) & 24u;
+    const uint32_t g0 = __builtin_amdgcn_ubfe(gb, sh, 4u), g1 = __builtin_amdgcn_ubfe(gb, sh + 4u, 4u);
+    const uint32_t at_a = at_tile + (g0 << 10), at_b = at_tile + (g1 << 10);
+    const u32x4 va = lane_load<u32x4>(f.state, at_a), vb = lane_load<u32x4>(f.state, at_b);
+    uint4 ua = make_uint4(va.x, va.y, va.z, va.w), ub = make_uint4(vb.x, vb.y, vb.z, vb.w);
+    __builtin_amdgcn_sched_barrier(0);  // (compiler only: everything down to the next one stands between the loads and their wait)
+    uint32_t g_ops = in_range ? entry.x : QM_IDENTITY << 10;  // "no gate", penalty 0: what an out-of-range action selects (clifford.rs:324)
+    float g_penalty = in_range ? __uint_as_float(entry.y) : 0.0f;
+    // the gate entry, depth and bad are all here: no later wait for a load
+    asm volatile("" : "+v"(g_ops), "+v"(g_penalty), "+v"(depth0), "+v"(bad0) : "s"(a.N), "s"(a.reward), "s"(a.done), "s"(a.success));
+    asm volatile("" : "+v"(done0), "+v"(success0));  // ... and the two old bytes: their first use is behind the row stores
+    int32_t depth = depth0 > 0 ? depth0 - 1 : 0;  // clifford.rs:342
+    float r_solved = 0.0f, r_open = 0.0f;
+    uint32_t fin_open = 0;  // is_final of an env that is not solved
+    const uint32_t ops = g_ops, q0 = ops & 31u, q1 = (ops >> 5) & 31u;
+    GateMasks<HAS_Z> gm(ops, g0, g1);
+    uint32_t e0[4], e1[4];  // the put-back's masks: gate_put
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        e0[k] = HAS_Z ? gm.o0 : 0u - (uint32_t)((q0 & 3u) == k);
+        e1[k] = HAS_Z ? gm.o1 : 0u - (uint32_t)((q1 & 3u) == k);
+    }
+    const uint32_t live = 0u - (uint32_t)(((ops >> 10) & 0xFFFFu) != QM_IDENTITY);
+    const uint32_t zb = 1u << a.N;
+    uint32_t ix0 = 1u << q0, ix1 = 1u << q1, iz0 = zb << q0, iz1 = zb << q1;  // the identity's rows of the two qubits
+    uint32_t set0 = live & 1u, set1 = set0 & (uint32_t)(q0 != q1);  // `bad`: as in qm_step1_mask_body
+    uint32_t bad_rest = bad0 & ~((set0 << q0) | (set1 << q1));
+    r_solved = 1.0f - g_penalty; r_open = 0.0f - g_penalty;  // clifford.rs:345-346, both outcomes
+    fin_open = (uint32_t)(depth == 0);
+    const bool apart = g0 != g1;
+    gm.pin();
+    if constexpr (!HAS_Z) asm volatile("" : "+v"(e0[0]), "+v"(e0[1]), "+v"(e0[2]), "+v"(e0[3]), "+v"(e1[0]), "+v"(e1[1]), "+v"(e1[2]), "+v"(e1[3]));
+    asm volatile("" : "+v"(ix0), "+v"(ix1), "+v"(iz0), "+v"(iz1), "+v"(set0), "+v"(set1), "+v"(bad_rest), "+v"(r_solved), "+v"(r_open),
+                      "+v"(depth), "+v"(fin_open));
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t z0, z1;
+    const uint32_t x0 = gm.get(ua, gm.o0, gm.h0, z0), x1 = gm.get(ub, gm.o1, gm.h1, z1);
+    const uint32_t nx0 = gm.mix(0, x0, z0, x1, z1), nx1 = gm.mix(2, x0, z0, x1, z1);
+    const uint32_t nz0 = HAS_Z ? gm.mix(1, x0, z0, x1, z1) : 0u, nz1 = HAS_Z ? gm.mix(3, x0, z0, x1, z1) : 0u;
+    // q1's rows first, then q0's (q0's value wins when q0 == q1, as in qm_apply)
+    gate_put<HAS_Z>(ub, e1, nx1, nz1);
+    ua.x = bit_select(gm.same, ub.x, ua.x); ua.y = bit_select(gm.same, ub.y, ua.y);
+    ua.z = bit_select(gm.same, ub.z, ua.z); ua.w = bit_select(gm.same, ub.w, ua.w);
+    gate_put<HAS_Z>(ua, e0, nx0, nz0);
+    if (apart) lane_store(f.state, at_b, u32x4{ub.x, ub.y, ub.z, ub.w});  // (one group: q0's store carries q1's rows too)
+    lane_store(f.state, at_a, u32x4{ua.x, ua.y, ua.z, ua.w});
+    const uint32_t d0 = HAS_Z ? xor_or(nx0, ix0, nz0 ^ iz0) : nx0 ^ ix0, d1 = HAS_Z ? xor_or(nx1, ix1, nz1 ^ iz1) : nx1 ^ ix1;
+    const uint32_t bad = bad_rest | (min(d0, set0) << q0) | (min(d1, set1) << q1);
+    const bool solved = bad == 0;       // clifford.rs:344
+    const float reward = solved ? r_solved : r_open;  // clifford.rs:345-346
+    const uint32_t fin = solved ? 1u : fin_open;  // is_final (clifford.rs:353)
+    if (bad != bad0) lane_store(f.bad, at4, bad);
+    // depth, done and success leave only where the step changed what memory held (qm_step1_mask_body)
+    if (depth != depth0) lane_store(f.depth, at4, depth);
+    lane_store(a.reward, at4, reward);
+    if (fin != done0) lane_store(a.done, env, (uint8_t)fin);
+    if ((uint32_t)solved != success0) lane_store(a.success, env, (uint8_t)solved);
 }
 
 // The same step with the gate's arithmetic and the addresses as the compiler makes them from selects and compares, nothing computed ahead of its

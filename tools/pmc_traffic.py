@@ -20,8 +20,11 @@ os.makedirs(dst, exist_ok=True)
 
 # run name -> (kernel name PREFIX -- trailing template arguments vary by call site --, envs, SURVEY 8(d) bytes per env-step, bytes the
 # kernel must move per env-step)
+# the headline's timed steps run the straight-line form since round 11 (bench.py --full's device-clock leg attaches a kernel clock: the generic form);
+# BENCH_KERNEL=<name prefix> reduces one of the two alone
+BENCH_KERNEL = os.environ.get("BENCH_KERNEL", "qm_step1_straight_kernel<16, true>")
 RUNS = {
-    "bench": ("qm_step1_kernel<16, true, false", 65536, 160, 90),
+    "bench": (BENCH_KERNEL, 65536, 160, 90),
     "C3_1048576": ("qm_step1_kernel<16, true, false", 1048576, 160, 90),
     "C3_4194304": ("qm_step1_kernel<16, true, false", 4194304, 160, 90),
     # two lanes per env: Grid_Size is 2 x envs.  Needed: 128 B of state read; the envs whose coin fired (half) rewrite all 128 B, the others the
@@ -113,7 +116,7 @@ for run, (kernel, envs, algo, needed) in RUNS.items():
         if needed:
             e["rocprof_frac_needed"] = needed * envs / st["avg_us"] / 1e3 / 8000
     out["configs"][run] = e
-    if kernel.startswith("qm_step1_kernel") and run != "tracked":
+    if kernel.startswith(("qm_step1_kernel", "qm_step1_straight_kernel")) and run != "tracked":
         out["by_envs"][str(envs)] = e
 json.dump(out, open(os.path.join(dst, "traffic.json"), "w"), indent=1)
 copied = []
