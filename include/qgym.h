@@ -154,7 +154,8 @@ int qg_vec_get_info(const qg_vec *v, qg_vec_info *out);
  * handle is destroyed or re-bound; NULL leaves that array where it is.  Synchronises. */
 int qg_vec_bind_outputs(qg_vec *v, float *reward_dev, uint8_t *done_dev, uint8_t *success_dev, int32_t *depth_dev);
 
-/* Env::set_difficulty / get_difficulty (clifford.rs:296-297) -- one value for the whole batch */
+/* Env::set_difficulty / get_difficulty (clifford.rs:296-297) -- one value for the whole batch, read when a reset is enqueued.
+ * A launch captured by the caller into a graph keeps the difficulty it was captured with. */
 int qg_vec_set_difficulty(qg_vec *v, int64_t difficulty);
 int64_t qg_vec_get_difficulty(const qg_vec *v);
 

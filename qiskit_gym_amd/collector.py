@@ -232,6 +232,9 @@ class RolloutCollector:
     so that graph replays advance it) resets finished episodes with seed `seed + 0x9E3779B9 * (n + 1)`
     and samples with counter n; both modes therefore produce the same trajectories.
 
+    `env.difficulty = d` between two collections holds for every reset of the next one, on every route: a graph captured at another
+    difficulty is captured again (as for a new T).
+
     `route` (a `CollectorRoute`) says which kernels run the policy; `operands` are the `PolicyOperands` of a `BasicPolicy` (None for
     another module), repacked in place at the top of every collection."""
 
@@ -284,6 +287,8 @@ class RolloutCollector:
         self._graph = None
         self._graph_T = 0
         self._graph_ro: Optional[Rollout] = None
+        self._difficulty = env.difficulty  # of the latest collection; a graph keeps the one it was captured with
+        self._last_dones: Optional[torch.Tensor] = None  # the latest collection's last row of `dones`
 
     @property
     def steps_done(self) -> int:
@@ -327,17 +332,29 @@ class RolloutCollector:
 
     @torch.no_grad()
     def collect(self, T: int, out: Optional[Rollout] = None) -> Rollout:
+        env = self.env
+        new_difficulty = env.difficulty != self._difficulty  # `env.difficulty = d` since the latest collection (a curriculum's next stage)
+        if new_difficulty:
+            self._difficulty = env.difficulty
+            # the fused step has already restarted the envs that finished in the latest collection's last step, with the old scramble length:
+            # end those episodes again, and this collection's first reset_done restarts them -- same seed -- at the new difficulty, which is
+            # what the separate launches do
+            if self.route.fused_step and self._last_dones is not None:
+                torch.maximum(env.done, self._last_dones, out=env.done)
         if not self.use_graph:
             ro = self._alloc(T) if out is None else out
             self._body(ro, T)
+            self._last_dones = ro.dones[T - 1] if T else None
             return ro
-        if self._graph is not None and self._graph_T == T:
+        if self._graph is not None and self._graph_T == T and not new_difficulty:
             self._graph.replay()
             return self._graph_ro
-        # first call (or a new T): one eager pass (allocates scratch, warms the GEMM handles, and IS
+        # first call (or a new T, or a new difficulty: the scramble length, the start depth and the choice of reset kernels are arguments the
+        # captured launches keep): one eager pass (allocates scratch, warms the GEMM handles, and IS
         # this call's rollout), then capture the same body for the calls that follow
         ro = self._alloc(T)
         self._body(ro, T)
+        self._last_dones = ro.dones[T - 1] if T else None
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):  # records, does not run: the env state and the clock are untouched

@@ -92,6 +92,8 @@ class VecEnv:
 
     @difficulty.setter
     def difficulty(self, d: int):
+        """The scramble length and start depth of every later reset (`set_difficulty` only stores the number, clifford.rs:296).  A launch
+        captured by the caller into a graph keeps the difficulty it was captured with."""
         _lib.check(self._L.qg_vec_set_difficulty(self._h, int(d)))
 
     def set_env_base(self, first_env: int):
@@ -221,8 +223,11 @@ class VecEnv:
 
     def reset_with(self, actions: torch.Tensor):
         """actions: int32 [difficulty, B] scramble draws (the reference's reset() RNG made explicit)."""
-        a = actions.to(device=self.device, dtype=torch.int32).contiguous().view(-1, self.batch)
-        _lib.check(self._L.qg_vec_reset_with(self._h, a.data_ptr(), a.shape[0], self._stream()))
+        a = actions.to(device=self.device, dtype=torch.int32).contiguous()
+        if a.numel() % self.batch:
+            raise ValueError(f"reset_with: {a.numel()} draws do not divide into {self.batch} envs")
+        n_draws = a.numel() // self.batch  # (0 at difficulty 0: no gates, the identity, final at once)
+        _lib.check(self._L.qg_vec_reset_with(self._h, a.data_ptr() if n_draws else None, n_draws, self._stream()))
 
     def _act(self, actions: torch.Tensor) -> Tuple[int, int]:
         if actions.device != self.device:

@@ -342,7 +342,8 @@ class Model:
     def reset_with(self, draws, mask=None):
         """Env::reset with the scramble's draws given ([n_draws, B]): gates applied to the identity, depth = slope * difficulty."""
         m = np.ones(self.B, bool) if mask is None else np.asarray(mask, bool)
-        draws = np.asarray(draws, dtype=np.int64).reshape(-1, self.B)[:, m]
+        draws = np.asarray(draws, dtype=np.int64)
+        draws = draws.reshape(-1 if draws.size else 0, self.B)[:, m]  # (no draws: the identity, depth 0)
         s = self.identity(int(m.sum()))
         for t in range(draws.shape[0]):
             s = self.apply(s, draws[t])

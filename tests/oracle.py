@@ -356,7 +356,8 @@ class OracleVec:
 
     def reset_with(self, actions: np.ndarray):
         """actions: [n_steps, B] scramble draws."""
-        a = np.ascontiguousarray(np.asarray(actions, dtype=np.int64).reshape(-1, self.batch))
+        a = np.asarray(actions, dtype=np.int64)
+        a = np.ascontiguousarray(a.reshape(-1 if a.size else 0, self.batch))  # (difficulty 0: no draws)
         if lib().og_vec_reset_with(self._h, _ptr(a, C.c_int64), a.shape[0]) != 0:
             raise OracleError(lib().og_last_error().decode())
 

@@ -205,3 +205,54 @@ def test_replayed_targets_succeed_on_the_oracle_at_the_predicted_step(kind, n):
     solved_after = np.stack([suffix.solved(suffix.product(circs[:, k:].tolist())) for k in range(1, T + 1)])
     np.testing.assert_array_equal(first[::2], solved_after.argmax(0)[::2] + 1)
     assert m.solutions() == [o.solution() for o in envs]
+
+
+# ---- a curriculum: the difficulty set through the setter, many times over, on live envs ----------------------------------------------
+@pytest.mark.parametrize("kind,n", [("clifford", 3), ("linear_function", 5), ("permutation", 6)])
+def test_difficulty_set_along_a_ladder_equals_envs_built_at_it(kind, n):
+    """What tests/test_gpu_curriculum.py leans on: an oracle batch whose difficulty is SET, rung after rung (0 included: no gate, depth 0,
+    final at once), resets like fresh oracle envs CONSTRUCTED at that difficulty -- its seeded reset with the draws util.rng_actions makes
+    in numpy -- and like the model, whose start depth follows the number of draws; a reset with another number of draws is refused."""
+    from oracle import OracleEnv, OracleError, OracleVec
+    from util import rng_actions
+
+    ladder = [1, 2, 8, 9, 16, 17, 63, 64, 65, 256, 70, 9, 8, 1, 5, 0, 0, 3]
+    gs = line_gateset(kind, n)
+    A, B = len(gs), 7
+    cfg = dict(add_inverts=0, add_perms=0, track_solution=0, depth_slope=2, max_depth=128)
+    per_env = {"clifford": 4 * n * n, "linear_function": n * n, "permutation": n}[kind]
+    ov = OracleVec(OracleEnv(kind, n, gs, **cfg), B)  # built at the default, 1
+    live = [ov.env(e) for e in range(B)]
+    m = Model(kind, n, gs, B, depth_slope=2, max_depth=128)
+    rng = np.random.default_rng(n)
+    for i, d in enumerate(ladder):
+        for o in live + [ov.proto]:
+            o.difficulty = d
+            assert o.difficulty == d
+        seed = 60 + i
+        draws = rng_actions(seed, B, d, A)
+        assert draws.shape == (d, B)
+        ov.reset_seeded(seed)
+        fresh = OracleVec(OracleEnv(kind, n, gs, difficulty=d, **cfg), B)
+        fresh.reset_with(draws)
+        m.reset_with(draws)
+        lbl = f"{kind} {n} rung {i} (difficulty {d})"
+        np.testing.assert_array_equal(ov.get_state(per_env), fresh.get_state(per_env), err_msg=lbl)
+        np.testing.assert_array_equal(ov.get_state(per_env), m.wire(), err_msg=lbl)
+        np.testing.assert_array_equal([o.depth() for o in live], min(2 * d, 128), err_msg=lbl)  # clifford.rs:317
+        np.testing.assert_array_equal(m.depth, min(2 * d, 128), err_msg=lbl)
+        np.testing.assert_array_equal([o.is_final() for o in live], m.is_final(), err_msg=lbl)
+        if d == 0:
+            assert all(o.is_final() and o.success() for o in live)
+        with pytest.raises(OracleError, match="exactly `difficulty`"):
+            live[0].reset_with(rng.integers(0, A, size=d + 1))
+        for t in range(2):
+            acts = rng.integers(-1, A + 2, size=B)
+            got, want = ov.step(acts), fresh.step(acts)
+            m.step(acts)
+            for g, w, name in zip(got, want, ("reward", "success", "is_final", "depth")):
+                np.testing.assert_array_equal(f32_bits(g) if name == "reward" else g, f32_bits(w) if name == "reward" else w, err_msg=f"{name} {lbl} t={t}")
+            np.testing.assert_array_equal(f32_bits(got[0]), f32_bits(m.reward), err_msg=lbl)
+            np.testing.assert_array_equal(got[2], m.is_final(), err_msg=lbl)
+            np.testing.assert_array_equal(got[3], m.depth, err_msg=lbl)
+            np.testing.assert_array_equal(ov.get_state(per_env), m.wire(), err_msg=lbl)

@@ -19,11 +19,26 @@ def test_notebook_walkthrough_linear_function(golden_dir):
     env = LinearFunctionGym.from_coupling_map(line_edges(3, True), add_inverts=False)  # intro.ipynb cell 3
     assert [(n, tuple(q)) for n, q in env.config["gateset"]] == [(n, tuple(q)) for n, q in d["gateset"]]
     assert repr(env.action_space) == "Discrete(8)" and env.observation_space.shape == (3, 3)  # cells 8-9
-    env.difficulty = 1  # cell 4
-    assert env.difficulty == 1 and env._raw_env.difficulty == 1
+    assert env.difficulty == 1  # the constructor's default
+    env.difficulty = 3  # cell 4 (there with the default, 1: a setter that did nothing would pass)
+    assert env.difficulty == 3 and env._raw_env.difficulty == 3
     obs, info = env.reset(seed=1)
     assert obs.dtype == np.int8 and obs.shape == (3, 3) and info == {}
-    assert int((obs != np.eye(3, dtype=np.int8)).sum()) in (0, 1, 2)  # identity plus one random gate
+    # the reset follows the setter: identity plus THREE random gates, the draws of seed 1 for env 0, and an episode of depth_slope * 3 steps
+    from oracle import OracleEnv
+    from util import rng_actions
+    ora = OracleEnv("linear_function", 3, d["gateset"], add_inverts=0, add_perms=0, difficulty=3)
+    ora.reset_with(rng_actions(1, 1, 3, 8)[:, 0])
+    assert obs.tolist() == ora.dense_obs().tolist()
+    assert not np.array_equal(obs, np.eye(3, dtype=np.int8))  # (these three draws do not cancel)
+    steps = 0
+    while not env._raw_env.is_final():
+        a = (5 * steps + 2) % 8
+        obs, reward, terminated, truncated, info = env.step(a)
+        ora.step(a)
+        steps += 1
+        assert obs.tolist() == ora.dense_obs().tolist() and terminated == ora.is_final()
+    assert steps == 6 or (ora.success() and steps < 6)  # linear_function.rs:298: depth = depth_slope * difficulty
     for seq in d["sequences"]:
         env.set_state(np.array(d["start_state"]).flatten().tolist())  # cell 6 (get_state needs qiskit; matrix given)
         for a, want, fin in zip(seq["actions"], seq["states"], seq["is_final"]):

@@ -39,6 +39,22 @@ def make_pair(kind, num_qubits, gateset, batch, **cfg):
     return ov, gv
 
 
+def oracle_envs(ov):
+    """The envs of an OracleVec as OracleEnv views, made once per batch (for per-env getters and setters)."""
+    if getattr(ov, "_env_views", None) is None:
+        ov._env_views = [ov.env(i) for i in range(ov.batch)]
+    return ov._env_views
+
+
+def set_difficulty(ov, gv, d: int):
+    """Env::set_difficulty on the GPU handle, the oracle's prototype and every oracle env; the GPU handle must report it back."""
+    gv.difficulty = d
+    ov.proto.difficulty = d
+    for e in oracle_envs(ov):
+        e.difficulty = d
+    assert gv.difficulty == d
+
+
 def f32_bits(x) -> np.ndarray:
     return np.asarray(x, dtype=np.float32).view(np.uint32)
 
