@@ -10,9 +10,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-from oracle import OracleEnv  # noqa: E402
+from oracle import OracleEnv, qubit_perms  # noqa: E402
 from qiskit_gym_amd.envs.raw import RawEnv  # noqa: E402
-from util import line_gateset, grid_gateset  # noqa: E402
+from util import line_gateset, grid_gateset, oracle_cfg, rng_actions  # noqa: E402
 
 
 def load(golden_dir, name):
@@ -78,18 +78,53 @@ def test_constructor_state_clone_and_inverts():
     assert full.tolist() == state.flatten().tolist()
 
 
+LAYER_WEIGHTS = {"n_cnots": 0.02, "n_layers_cnots": 0.3, "n_layers": 0.07, "n_gates": 0.0005}  # test_layer_weights_take_the_feature_kernels'
+PERM_SEED_SALT = 0x7065726D  # PauliEnv::observe draws rng_draw(seed ^ salt, env, observe index) (kernels_pauli_tile.hip)
+
+
+def _perm_draw(seed, index, n_perms):
+    """The permutation index observe() number `index` draws on a PauliEnv handle with add_perms whose seed is `seed`."""
+    return int(rng_actions(seed ^ PERM_SEED_SALT, [0], index + 1, n_perms)[index, 0])
+
+
+# ("kind+variant", n, inverts): "layers" -- layer weights, so that the rewards read the env's `layers` tile; "track" -- the two-part solution
+# log of track_solution with add_inverts; "perms" -- PauliEnv with add_perms, whose observe() draws (observe index, current permutation)
 @pytest.mark.parametrize("kind,n,inverts", [("clifford", 5, False), ("clifford", 20, False), ("linear_function", 12, False),
                                             ("linear_function", 40, False), ("clifford", 4, True), ("permutation", 9, False), ("pauli", 4, False),
-                                            ("linear_function", 20, True), ("linear_function", 50, True), ("permutation", 30, True), ("clifford", 20, True)])
+                                            ("linear_function", 20, True), ("linear_function", 50, True), ("permutation", 30, True), ("clifford", 20, True),
+                                            ("clifford+layers", 16, False), ("clifford+track", 4, True), ("pauli+perms", 4, False)])
 def test_clone_mid_episode_continues_like_the_original(kind, n, inverts):
     """Env: DynClone -- a clone taken mid-episode carries every piece of resident state (including the
     incremental solved mask of the one-step kernels) and then evolves independently."""
+    kind, _, variant = kind.partition("+")
     gs = grid_gateset("permutation", 3, 3) if (kind == "permutation" and n == 9) else line_gateset(kind, n)
-    kw = dict(add_perms=False, difficulty=6)
+    kw = dict(add_perms=variant == "perms", difficulty=6)
     if kind != "pauli":
         kw["add_inverts"] = inverts
-    env = RawEnv(kind, n, gs, **kw)
-    ora = OracleEnv(kind, n, gs, **{k: int(v) for k, v in kw.items()})
+    if variant == "layers":
+        kw["metrics_weights"] = LAYER_WEIGHTS
+    if variant == "track":
+        kw["track_solution"] = True
+    seeds, n_perms = {}, 0
+    if variant == "perms":
+        kw.update(pauli_diff_scale=2, max_rotations=4)  # difficulty 6: rotations in the target
+        n_perms = len(qubit_perms(n, gs)[0])
+        assert n_perms == 2
+        # the original's last draw before the clone (observe number 2) is the non-trivial permutation; the probe's own first draw
+        # (observe number 3 under its seed) differs from what an observe index of 0 would give it
+        seeds["env"] = next(s for s in range(100, 200) if _perm_draw(s, 2, n_perms) == 1)
+        seeds["twin"] = 4242
+        seeds["probe"] = next(s for s in range(200, 300) if _perm_draw(s, 3, n_perms) != _perm_draw(s, 0, n_perms))
+    env = RawEnv(kind, n, gs, **kw) if variant != "perms" else RawEnv(kind, n, gs, seed=seeds["env"], **kw)
+    ora = OracleEnv(kind, n, gs, **oracle_cfg(kw))
+    observed = {}  # observe() calls made so far on a handle and on those it was cloned from
+
+    def observations(name, e, o):
+        """(the library's, the oracle's) observation; with add_perms on a PauliEnv the oracle is given the handle's own next draw"""
+        k = observed.get(name, 0)
+        observed[name] = k + 1
+        return e.observe(), o.observe(_perm_draw(seeds[name], k, n_perms) if n_perms else 0)
+
     rng = np.random.default_rng(3)
     if kind == "pauli":
         env.reset(5)
@@ -103,18 +138,114 @@ def test_clone_mid_episode_continues_like_the_original(kind, n, inverts):
         a, coin = int(rng.integers(len(gs))), int(rng.integers(2)) if inverts else 0
         env.step(a, coin) if kind != "pauli" else env.step(a)
         ora.step(a, coin)
-    twin, ora_twin = env.clone(), ora.clone()
+        if n_perms:  # (the next step un-permutes its action with this draw)
+            got, want = observations("env", env, ora)
+            assert got == want, (kind, "before the clone", t)
+    twin, ora_twin = (env.clone(), ora.clone()) if not n_perms else (env.clone(seed=seeds["twin"]), ora.clone())
+    if n_perms:
+        # a clone observed at once: its draw is observe number 3 of its own seed (the observe index travels with the state) ...
+        observed["twin"] = observed["probe"] = observed["env"]
+        probe, ora_probe = env.clone(seed=seeds["probe"]), ora.clone()
+        got, want = observations("probe", probe, ora_probe)
+        assert got == want, "the clone's first observation"
+        # ... while the twin steps first: its action is un-permuted with the permutation the ORIGINAL drew last
+        assert _perm_draw(seeds["env"], observed["env"] - 1, n_perms) == 1
     for t in range(10):
         a, b = int(rng.integers(len(gs))), int(rng.integers(len(gs)))
-        for e, o, act in ((env, ora, a), (twin, ora_twin, b)):
+        for name, e, o, act in (("env", env, ora, a), ("twin", twin, ora_twin, b)):
             coin = int(rng.integers(2)) if inverts else 0  # an inversion: transpose (Clifford), role swap (LinearFunction), scatter (Permutation)
             e.step(act, coin) if kind != "pauli" else e.step(act)
             o.step(act, coin)
-            assert e.observe() == o.observe(), (kind, t)
+            got, want = observations(name, e, o)
+            assert got == want, (kind, t)
             assert np.float32(e.reward()).view(np.uint32) == o.reward_bits(), (kind, t)
             assert e.success() == o.success() and e.is_final() == o.is_final()
+            assert e.solution() == o.solution(), (kind, name, t)  # solution ++ rev(solution_inv) with add_inverts (clifford.rs:376-381)
     # a clone of a solved env reports success; a clone of an unsolved one must not
     assert twin.success() == ora_twin.success()
+
+
+def _hostile_states(kind, n, rng):
+    """(a state only a Gauss-Jordan inversion handles -- invertible, and for CliffordEnv not symplectic: the odd envs' start of
+    test_gpu_envmodel._targets --, a singular state) in set_state's wire format."""
+    d = 2 * n if kind == "clifford" else n
+    m = np.eye(d, dtype=np.int64)
+    for _ in range(3 * d):
+        i, j = rng.integers(0, d, size=2)
+        if i != j:
+            m[i] ^= m[j]
+    singular = np.eye(d, dtype=np.int64)
+    singular[d - 1] = singular[0]  # two equal rows
+    return m.flatten().tolist(), singular.flatten().tolist()
+
+
+@pytest.mark.parametrize("kind,n", [("clifford", 4), ("linear_function", 40)])
+def test_clones_from_the_pool_forget_their_hostile_previous_owners(kind, n):
+    """A pooled handle carries its previous owner's life: the inversion flag, built twists, the Gauss-Jordan kernel variant a non-symplectic
+    state selects, and the fault word of an owner whose last call was the library's QG_ERR_PANIC.  Whatever it was, a clone of a healthy
+    mid-episode prototype -- from the pool or fresh -- continues exactly like OracleEnv.clone()."""
+    from qiskit_gym_amd._lib import QGymError
+
+    RawEnv.release_pool()
+    gs = line_gateset(kind, n)
+    A = len(gs)
+    kw = dict(add_inverts=True, add_perms=True, track_solution=True, difficulty=6)  # CliffordEnv: the reference's defaults
+    proto = RawEnv(kind, n, gs, seed=3, **kw)
+    ora = OracleEnv(kind, n, gs, **oracle_cfg(kw))
+    rng = np.random.default_rng(40 + n)
+    proto.reset(21)
+    ora.reset_with(rng_actions(21, [0], 6, A)[:, 0])
+    for t in range(3):  # mid-episode, with a solution log in both parts
+        a, coin = int(rng.integers(A)), (1, 0, 0)[t]
+        proto.step(a, coin)
+        ora.step(a, coin)
+    assert ora.inverted() and not ora.is_final() and len(ora.solution()) == 3
+    gauss_jordan_only, singular = _hostile_states(kind, n, rng)
+
+    def inverted(c):
+        c.reset(8)
+        c.step(0, 1)  # the coin inverts: `inverted` is set when the handle is parked
+
+    def twisted(c):
+        assert len(c.twists()[0]) >= 2
+
+    def non_symplectic(c):
+        c.set_state(gauss_jordan_only)
+        c.step(1, 1)  # (inverted by Gauss-Jordan)
+
+    def panicked(c):
+        status = message = None
+        try:  # the library's own status from its fault word, at set_state or at the first inversion
+            c.set_state(singular)
+            c.step(0, 1)
+        except QGymError as err:
+            status, message = err.status, err.message
+        assert status == -5 and "singular" in message, (status, message)  # QG_ERR_PANIC
+
+    lives = [inverted, twisted, non_symplectic, panicked]
+    owners = [proto.clone(seed=50 + i) for i in range(len(lives))]  # (all of them live at once: none is another's pooled handle)
+    for live, c in zip(lives, owners):
+        live(c)
+    parked = {c._h.value for c in owners}
+    del owners, c  # parked
+    clones = [proto.clone(seed=60 + i) for i in range(len(lives) + 1)]  # every parked handle, and a fresh one
+    assert parked < {c._h.value for c in clones}
+    for i, c in enumerate(clones):
+        o = ora.clone()
+        assert c.solution() == o.solution() == ora.solution(), i
+        assert (c.observe(), c.is_final(), c.success()) == (o.observe(), o.is_final(), o.success()), i
+        assert np.float32(c.reward()).view(np.uint32) == o.reward_bits(), i
+        for t in range(8):
+            a, coin = int(rng.integers(A)), int(rng.integers(2))
+            c.step(a, coin)  # (raises on any status: a previous owner's fault word would surface here)
+            o.step(a, coin)
+            assert c.observe() == o.observe(), (i, t)
+            assert np.float32(c.reward()).view(np.uint32) == o.reward_bits(), (i, t)
+            assert (c.is_final(), c.success(), c.masks()) == (o.is_final(), o.success(), o.masks()), (i, t)
+            assert c.solution() == o.solution(), (i, t)
+    assert proto.solution() == ora.solution() and proto.observe() == ora.observe()  # the prototype itself is untouched
+    del clones, c
+    RawEnv.release_pool()
 
 
 def test_twists_match_symmetry_rules():
