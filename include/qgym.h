@@ -331,9 +331,15 @@ int qg_vec_sync(qg_vec *v, void *stream);
 
 /* Solution log (Env::solution, clifford.rs:376-381 / pauli.rs:685-719) of env e, host side.
  * Returns the length (may exceed cap) or a negative status.  Entries are kept as 32-bit words on
- * the device: an out-of-range action the reference would log verbatim (clifford.rs:334-340) is
- * reported exactly when it is below 2^32 - 1; negative or larger ones are reported as
- * UINT64_MAX (what `-1 as usize` is). */
+ * the device.  CliffordEnv, LinearFunctionEnv and PermutationEnv spend bit 31 of the word on the
+ * `solution_inv` flag, so an entry is exact up to 2^31 - 2: an out-of-range action that CliffordEnv
+ * and LinearFunctionEnv log verbatim like the reference (clifford.rs:334-340) is reported exactly
+ * up to that value; larger and negative ones are reported as UINT64_MAX (what `-1 as usize` is).
+ * PermutationEnv and PauliEnv log in-range actions only (permutation.rs:210-216, pauli.rs:612-626).
+ * The log holds the first max_depth pushes of an episode (PauliEnv: max_depth + one per rotation):
+ * a later push is dropped, sets QG_FAULT_SOLUTION_OVERFLOW in the env's word and leaves the logged
+ * entries as they are -- the list is then a prefix, in push order, of the reference's (PauliEnv: of
+ * whole steps, a gate with the rotations it released; nothing is logged behind a dropped step). */
 int64_t qg_vec_solution(qg_vec *v, uint64_t env, uint64_t *out, size_t cap);
 /* The same for EVERY env with one copy of the log: out[e * cap + i] = entry i of env e's list (entries beyond cap dropped), lens[e] = its
  * full length (what twisterl's collector does per episode with Env::solution, here once per batch).  Host pointers; synchronises. */
@@ -780,6 +786,8 @@ int qg_env_success(const qg_env *e);
 /* ascending flat indices of set observation entries; returns the count */
 int64_t qg_env_observe(qg_env *e, int64_t *out, size_t cap);
 int qg_env_track_solution(const qg_env *e);
+/* Env::solution; entries and capacity as for qg_vec_solution: exact up to 2^31 - 2 (bit 31 of the stored word is the `solution_inv`
+ * flag), UINT64_MAX beyond and for negative actions; PermutationEnv and PauliEnv log in-range actions only. */
 int64_t qg_env_solution(const qg_env *e, uint64_t *out, size_t cap);
 /* twists(): (obs_perms, act_perms) (clifford.rs:370-372).  Returns the number of twists;
  * obs_perms_out[n * obs_size], act_perms_out[n * num_actions] when non-NULL. */

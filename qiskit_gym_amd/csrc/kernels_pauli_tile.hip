@@ -479,6 +479,9 @@ __global__ __launch_bounds__(256) void ptile_step_kernel(PTArgs pa) {
     pt_load<NQ, RM>(tile, lane, s);
     int32_t depth = a.depth[env];
     int32_t sol_n = (FEAT && (a.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
+    // a log that has dropped a step stays the prefix it is: the fit test below passes again once rotations have gone, and a step logged then
+    // would stand behind a hole
+    const uint32_t log_closed = (FEAT && (a.flags & F_TRACK)) ? a.error[env] & 8u : 0u;
     const uint32_t alive0 = s.alive, count0 = s.count, bad0 = s.bad;
     const PTOrder<RM> order0 = s.order;
     uint32_t touched_rot = 0;   // rotations whose record changed while they were alive
@@ -507,7 +510,7 @@ __global__ __launch_bounds__(256) void ptile_step_kernel(PTArgs pa) {
 #pragma unroll
         for (int i = 0; i < (RM + 7) / 8; ++i) rem_pos[i] = 0;
         SolLog log{nullptr, 0};
-        if (FEAT && (a.flags & F_TRACK) && in_range && (uint32_t)sol_n + 1u + (uint32_t)s.count <= a.sol_cap)
+        if (FEAT && (a.flags & F_TRACK) && in_range && !((log_closed | fault) & 8u) && (uint32_t)sol_n + 1u + (uint32_t)s.count <= a.sol_cap)
             log = SolLog{&sol_at(a, env, (uint32_t)sol_n + 1u), a.B};  // slot sol_n is the gate itself
 
         if (in_range) {
@@ -707,6 +710,7 @@ __global__ __launch_bounds__(256) void ptile_step1_kernel(PTArgs pa) {
     pt_load_rotations<NQ, RM>(tile, lane, s);
     int32_t depth = a.depth[env];
     int32_t sol_n = (FEAT && (a.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
+    const uint32_t log_closed = (FEAT && (a.flags & F_TRACK)) ? a.error[env] & 8u : 0u;  // (ptile_step_kernel: no step is logged behind a dropped one)
     const uint32_t alive0 = s.alive, count0 = s.count, bad0 = s.bad;
     const PTOrder<RM> order0 = s.order;
     uint32_t touched_rot = 0, fault = 0;
@@ -729,7 +733,7 @@ __global__ __launch_bounds__(256) void ptile_step1_kernel(PTArgs pa) {
 #pragma unroll
     for (int i = 0; i < (RM + 7) / 8; ++i) rem_pos[i] = 0;
     SolLog log{nullptr, 0};
-    if (FEAT && (a.flags & F_TRACK) && in_range && (uint32_t)sol_n + 1u + (uint32_t)s.count <= a.sol_cap)
+    if (FEAT && (a.flags & F_TRACK) && in_range && !log_closed && (uint32_t)sol_n + 1u + (uint32_t)s.count <= a.sol_cap)
         log = SolLog{&sol_at(a, env, (uint32_t)sol_n + 1u), a.B};  // slot sol_n is the gate itself
 
     if (in_range) {
@@ -850,6 +854,7 @@ __device__ __forceinline__ bool ptile_step1c_body(const PTArgs &pa, uint64_t env
     s.phi = (pw0.x >> 8) & 0xFFu;
     uint32_t w[5] = {(pw0.x >> 16) & 0xFFu, pw0.x >> 24, pw0.y & 0xFFu, (pw0.y >> 8) & 0xFFu, (pw0.y >> 16) & 0xFFu};
     int32_t sol_n = (FEAT && (a.flags & F_TRACK)) ? a.sol_len[env * 2] : 0;
+    const uint32_t log_closed = (FEAT && (a.flags & F_TRACK)) ? a.error[env] & 8u : 0u;  // (ptile_step_kernel: no step is logged behind a dropped one)
     uint32_t fault = 0;
 
     if (pa.n_perms) {  // actual_action = act_perms[current_perm_idx][action] (pauli.rs:594-599)
@@ -870,7 +875,7 @@ __device__ __forceinline__ bool ptile_step1c_body(const PTArgs &pa, uint64_t env
 #pragma unroll
     for (int i = 0; i < (RM + 7) / 8; ++i) rem_pos[i] = 0;
     SolLog log{nullptr, 0};
-    if (FEAT && (a.flags & F_TRACK) && in_range && (uint32_t)sol_n + 1u + (uint32_t)s.count <= a.sol_cap)
+    if (FEAT && (a.flags & F_TRACK) && in_range && !log_closed && (uint32_t)sol_n + 1u + (uint32_t)s.count <= a.sol_cap)
         log = SolLog{&sol_at(a, env, (uint32_t)sol_n + 1u), a.B};  // slot sol_n is the gate itself
 
     // rotation k's masks outside {qa, qb}, from the transposed bytes (solution log only: a removal is rare)

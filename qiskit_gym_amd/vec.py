@@ -23,6 +23,13 @@ def _stream_ptr(device=None) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+class _DeviceWords:
+    """`count` 32-bit words owned by libqgym as a `__cuda_array_interface__` object (torch.as_tensor makes a view, no copy)."""
+
+    def __init__(self, ptr: int, count: int):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
+
+
 class VecEnv:
     """`batch` copies of one env kind (`"clifford" | "linear_function" | "permutation" | "pauli"`)."""
 
@@ -475,6 +482,14 @@ class VecEnv:
     def sync(self):
         """Wait for the current stream and raise if any env hit a fault the reference panics on."""
         _lib.check(self._L.qg_vec_sync(self._h, self._stream()))
+
+    def faults(self) -> np.ndarray:
+        """The sticky per-env status words (QG_FAULT_* bits, `qg_vec_info.error_dev`) as numpy uint32 [B]: what `sync()` condenses into
+        the first env it names.  Ordered after the earlier launches of the current stream; waits for them.  A reset of an env clears its word."""
+        info = _lib.QGVecInfo()
+        _lib.check(self._L.qg_vec_get_info(self._h, C.byref(info)))  # (asked every time: a scalar env rebinds the array)
+        view = torch.as_tensor(_DeviceWords(info.error_dev, self.batch), device=self.device)  # a view, no copy
+        return view.cpu().numpy().view(np.uint32)  # (the copy runs on the device's current stream and waits for it)
 
     def solution(self, env: int):
         n = self._L.qg_vec_solution(self._h, env, None, 0)

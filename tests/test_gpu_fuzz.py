@@ -9,6 +9,7 @@ SEED_OFFSET = int(os.environ.get("QGYM_FUZZ_SEED_OFFSET", "0"))  # soak runs: sh
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from logcap_model import PushRecorder, reported  # noqa: E402
 from oracle import OracleEnv  # noqa: E402
 from test_gpu_pauli import random_labels, random_tableau  # noqa: E402
 from util import f32_bits, make_pair  # noqa: E402
@@ -207,6 +208,7 @@ def test_random_auto_reset_loops_with_tracked_observations(seed):
     on random gatesets and sizes of the 32-bit-row layout, with and without a tracked dense observation, against a twin handle that only uses
     the plain calls (step + reset_done + observe) and, for the first envs, against the oracle: flags, depths, reward bits after every call,
     states and observations at the end."""
+    from qiskit_gym_amd._lib import QGymError
     from qiskit_gym_amd.vec import VecEnv
 
     seed += SEED_OFFSET + 5000
@@ -226,16 +228,33 @@ def test_random_auto_reset_loops_with_tracked_observations(seed):
     envs = [OracleEnv(kind, n, gs, **{k: int(v) for k, v in cfg.items()}) for _ in range(ne)]
     label = f"seed={seed} {kind} n={n} A={A} B={B} {cfg} dense={dense is not None}"
 
+    # the solution log's pushes of every env's current episode (tests/logcap_model.py): a plain step on a finished env may push past the
+    # max_depth entries the log holds, which drops the entry and sets status bit 8 until the env is reset
+    rec = PushRecorder(kind, B, A)
+    cap = cfg["max_depth"]
+
     def oracle_reset(seed_, only_done):
         from util import rng_actions
         d = rng_actions(seed_, ne, diff, A)
         for e, o in enumerate(envs):
             if not only_done or o.is_final():
                 o.reset_with(d[:, e])
+        rec.clear(finished if only_done else None)
+
+    def oracle_step(actions):
+        for o, x in zip(envs, actions[:ne]):
+            o.step(int(x), 0)
+        rec.note(actions)
 
     def compare(what):
-        a.sync()
-        twin.sync()
+        want = rec.expected_faults(cap) if cfg["track_solution"] else np.zeros(B, np.uint32)
+        for h in (a, twin):
+            np.testing.assert_array_equal(h.faults(), want, err_msg=f"status words {what} {label}")
+            if want.any():
+                with pytest.raises(QGymError, match="solution log overflow"):
+                    h.sync()
+            else:
+                h.sync()
         assert torch.equal(a.reward.view(torch.int32), twin.reward.view(torch.int32)) and torch.equal(a.done, twin.done), (what, label)
         assert torch.equal(a.depth, twin.depth) and torch.equal(a.success, twin.success), (what, label)
         np.testing.assert_array_equal(f32_bits(a.reward.cpu().numpy()[:ne]), np.array([o.reward_bits() for o in envs], dtype=np.uint32), err_msg=f"{what} {label}")
@@ -249,27 +268,23 @@ def test_random_auto_reset_loops_with_tracked_observations(seed):
         acts = rng.integers(-1, A + 1, size=B)
         ta = torch.as_tensor(acts, device="cuda", dtype=torch.int64 if t % 2 else torch.int32)
         s2 = int(rng.integers(1 << 30))
+        finished = a.done.cpu().numpy().astype(bool)  # (the envs a reset_done resets: equal to the twin's and, for the first envs, the oracle's)
         if op < 5:  # the collection loop's pair, as one call
             a.reset_done_step(s2, ta)
             twin.reset_done(s2)
             twin.step(ta)
             oracle_reset(s2, True)
-            for o, x in zip(envs, acts[:ne]):
-                o.step(int(x), 0)
+            oracle_step(acts)
         elif op < 7:  # the two calls
             for h in (a, twin):
                 h.reset_done(s2)
                 h.step(ta)
             oracle_reset(s2, True)
-            for o, x in zip(envs, acts[:ne]):
-                o.step(int(x), 0)
-        elif op == 7:  # a plain step (finished envs keep stepping: the trait allows it) -- unless the log would overflow
-            if cfg["track_solution"]:
-                continue
+            oracle_step(acts)
+        elif op == 7:  # a plain step (finished envs keep stepping: the trait allows it); a full log drops the entry and reports it
             for h in (a, twin):
                 h.step(ta)
-            for o, x in zip(envs, acts[:ne]):
-                o.step(int(x), 0)
+            oracle_step(acts)
         elif op == 8:  # everybody starts over
             for h in (a, twin):
                 h.reset(s2)
@@ -284,13 +299,13 @@ def test_random_auto_reset_loops_with_tracked_observations(seed):
                 h.rollout(tseq)
             oracle_reset(s2, False)
             for k in range(3):
-                for o, x in zip(envs, seq[k][:ne]):
-                    o.step(int(x), 0)
+                oracle_step(seq[k])
         compare(f"t={t} op={op}")
         if dense is not None:
             assert torch.equal(dense, twin.observe()), (t, op, label)
     assert torch.equal(a.get_state("packed"), twin.get_state("packed")), label
     np.testing.assert_array_equal(a.get_state("i64").cpu().numpy()[:ne], np.stack([o.get_state() for o in envs]), err_msg=label)
     if cfg["track_solution"]:
-        for e in (0, ne - 1):
-            assert a.solution(e) == envs[e].solution() == twin.solution(e), (label, e)
+        kept = rec.expected_log(cap)
+        for e in (0, ne - 1):  # (no add_inverts here: the entries a full log keeps are the first `cap` of the reference's list)
+            assert a.solution(e) == [reported(x, kind) for x in envs[e].solution()[:cap]] == twin.solution(e) == kept[e], (label, e)

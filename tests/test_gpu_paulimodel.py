@@ -34,15 +34,19 @@ def _label(x, z, k):
     return ("-" if k == 2 else "") + "".join("IXZY"[int(x[q]) + 2 * int(z[q])] for q in range(n - 1, -1, -1))
 
 
-def replay_target(m, circ, n_rot, rng):
+def replay_target(m, circ, n_rot, rng, paulis=None):
     """(tableau, labels) that replaying `circ` solves: the identity tableau and n_rot signed weight-1 Paulis, conjugated by the
-    circuit's inverse (reversed, S / SX and their inverses exchanged; every action's micro-op sequence is its own reverse)."""
+    circuit's inverse (reversed, S / SX and their inverses exchanged; every action's micro-op sequence is its own reverse).
+    `paulis`: the weight-1 Paulis as (qubit, axis 1 X / 2 Z / 3 Y) instead of random ones."""
     n = m.n
     xs = np.zeros((n, 2 * n + n_rot), np.int64)
     zs = np.zeros((n, 2 * n + n_rot), np.int64)
     xs[:, :n], zs[:, n:2 * n] = np.eye(n, dtype=np.int64), np.eye(n, dtype=np.int64)
-    q = rng.integers(0, n, size=n_rot)
-    ax = rng.integers(1, 4, size=n_rot)
+    if paulis is None:
+        q = rng.integers(0, n, size=n_rot)
+        ax = rng.integers(1, 4, size=n_rot)
+    else:
+        q, ax = (np.array(v, np.int64) for v in zip(*paulis))
     xs[q, 2 * n + np.arange(n_rot)] = ax & 1
     zs[q, 2 * n + np.arange(n_rot)] = ax >> 1
     ks = np.where(rng.random(n_rot) < 0.5, 2, 0)
