@@ -103,7 +103,10 @@ typedef enum {
     QG_FMT_I64 = 0,   /* the trait's `set_state(Vec<i64>)` wire format per env (clifford.rs:299-304:
                          D*D entries, >0 => 1; permutation.rs:168-173: N entries; pauli.rs:517-552:
                          [rot_count, 4N^2 tableau, (len, chars...)*], fixed stride per env) */
-    QG_FMT_U8 = 1,    /* dense 0/1 bytes in observation layout (the Gym int8 observation) */
+    QG_FMT_U8 = 1,    /* dense 0/1 bytes in observation layout (the Gym int8 observation): D*D bytes per env.
+                         Permutation: N bytes, one per entry, exactly as QG_FMT_PACKED (not the N*N one-hot
+                         observation), for qg_vec_set_state and qg_vec_get_state alike.  PauliEnv: get_state
+                         only, the 2N x 2N tableau */
     QG_FMT_PACKED = 2 /* bit-packed rows, reference row order: row r of env e is word e*D + r;
                          word = uint32 when D <= 32 else uint64; bit c = entry (r, c).
                          Permutation: one uint8 per entry. */

@@ -1950,7 +1950,9 @@ static hipError_t ptile_dense_via_words(qg_vec *v, const ObsArgs &a, void *out, 
 
 hipError_t ptile_export(const qg_vec *v, const ObsArgs &a, hipStream_t s) {
     if (!a.B) return hipSuccess;
-    if (a.format == QG_FMT_U8 && a.obs_cols <= 64u && a.out_stride == (uint64_t)a.obs_rows * a.obs_cols && (reinterpret_cast<uintptr_t>(a.out) & 15u) == 0)
+    // (a.out == v->scratch: qg_vec_get_state staging a host destination -- the row words would share the buffer with the output)
+    if (a.format == QG_FMT_U8 && a.obs_cols <= 64u && a.out_stride == (uint64_t)a.obs_rows * a.obs_cols && (reinterpret_cast<uintptr_t>(a.out) & 15u) == 0 &&
+        a.out != v->scratch)
         return ptile_dense_via_words(const_cast<qg_vec *>(v), a, a.out, QG_DT_I8, s);  // the scratch buffer is a cache, not state
     if (a.format == QG_FMT_I64 && a.B >= QG_STREAM_MIN_ENVS && a.obs_cols == 2 * a.N && a.out_stride == (uint64_t)a.obs_cols * a.obs_cols &&
         (reinterpret_cast<uintptr_t>(a.out) & 15u) == 0 && a.out != v->scratch) {

@@ -727,7 +727,11 @@ int qg_vec_get_state(qg_vec *v, void *out, int format, size_t stride, int on_dev
     QG_ON_DEVICE(v);
     hipStream_t s = (hipStream_t)stream;
     void *dst = out;
-    size_t bytes = format_elem_bytes(v, format) * stride * v->B;
+    const size_t elem = format_elem_bytes(v, format);
+    size_t bytes = elem * stride * v->B;
+    // PermutationEnv's byte formats are one byte per entry (QG_FMT_U8 as QG_FMT_PACKED, what set_state reads): the export kernels' U8 is
+    // the dense N x N observation, which does not fit a record of N bytes
+    if ((v->plan.layout == LAYOUT_PERM || v->plan.layout == LAYOUT_PERMB) && format == QG_FMT_U8) format = QG_FMT_PACKED;
     // the trait's Vec<i64> of the bit-matrix layouts: the row words first (8 MiB for CliffordEnv 16q x 65 536), then one expansion kernel whose
     // stores are wave-contiguous -- 537 MB at streaming rate (the export kernels' row-per-thread, entry-by-entry stores reached 0.6 TB/s)
     qg_vec_info info;
@@ -755,7 +759,10 @@ int qg_vec_get_state(qg_vec *v, void *out, int format, size_t stride, int on_dev
         HIP_TRY(launch_export(v, oa, s));
     }
     if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, s));
+        // only the records: the kernels leave the padding of a wider stride unwritten, in the staging buffer too, and the caller's stays as it was
+        const size_t rec = elem * format_min_elems(v, format);
+        if (stride == format_min_elems(v, format)) HIP_TRY(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, s));
+        else HIP_TRY(hipMemcpy2DAsync(out, elem * stride, dst, elem * stride, rec, v->B, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     return QG_OK;

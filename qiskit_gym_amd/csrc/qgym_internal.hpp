@@ -224,8 +224,9 @@ struct ObsArgs {
     uint32_t kclk_waves;
 };
 
-// internal set_state source format (never crosses the C ABI): InitArgs::src is a bit stream, bit e = entry e of the flat [B][D][D] array
-// (pack_bitstream, kernels_collect.hip); src_stride = D * D
+// internal set_state source format (never crosses the C ABI): InitArgs::src is a bit stream, bit e = entry e of the caller's flat
+// [B][src_stride] array, padding entries included (pack_bitstream, kernels_collect.hip); src_stride is the caller's stride (>= D * D, any
+// parity), so env e's row r starts at bit e * src_stride + r * D, wherever in a stream word that falls
 #define QG_FMT_BITS 3u
 // D <= 64 bits of the stream starting at bit `pos` (the word after the stream's last one must be readable: the host pads it)
 __device__ inline uint64_t bits_window(const uint64_t *bs, uint64_t pos, uint32_t D) {
