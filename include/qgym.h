@@ -34,7 +34,8 @@ extern "C" {
 /* 2: + qg_comm_* / learner-shard entry points, qg_vec_step_host, qg_vec_observe_*_host (additions only: version-1 callers keep working)
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
- *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance (additions only) */
+ *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance, qg_mcts_forest_bytes,
+ *      qg_mcts_select, qg_mcts_backup (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -473,6 +474,66 @@ int qg_beam_advance(uint64_t n_groups, uint32_t width, const int32_t *parent_dev
                     const uint8_t *success_dev, const uint8_t *done_dev, uint8_t *live_dev, float *best_dev, uint8_t *found_dev,
                     float *ret_out_dev, int32_t *win_src_dev, uint8_t *group_live_dev, int32_t *bounded_dev, int32_t skip, float bonus, int mode,
                     void *stream);
+/* The tree of a PUCT search (MCTS): one tree per target, rebuilt for every decision, in plain arrays the caller owns -- the kernels know no
+ * env and no policy.  A forest of n_trees trees of at most cap nodes over num_actions actions is a struct of device arrays:
+ *   per (tree m, node j), index m*cap + j:  parent i32 (-1 for node 0) | reward f32, the reward of the step into the node | value f32, the
+ *       value head at the node, 0 for a terminal node | visits i32 | wsum f32 | terminal u8, the env's `done`
+ *   per (tree, node, action), index (m*cap + j)*num_actions + a:  child i32 (-1 = not expanded) | prior f32
+ *   per tree:  n_nodes i32
+ * Node 0 is the root.  A node's env is expected in a pool of n_trees*cap envs at index m*cap + j ("pool index"); for a search of N
+ * simulations per decision cap = N + 1.  qg_mcts_forest_bytes is what the arrays take together.
+ * The rules (tests/mctsmodel.py restates them in numpy; results agree bit for bit):
+ *   root       qg_mcts_backup in mode QG_MCTS_ROOT, per tree from logp_dev[m*ld + a] and values_dev[m]: prior[0][a] = expf(logp), child[0][a]
+ *              = -1, terminal[0] = done_dev[m] != 0 (0 where done_dev is NULL), value[0] = values[m] (0 if terminal), visits[0] = 1,
+ *              parent[0] = -1, reward[0] = wsum[0] = 0, n_nodes = 1.
+ *   selection  qg_mcts_select, one descent per tree from node 0.  At a terminal node x the descent ends there and nothing is expanded.
+ *              Otherwise every action a < num_actions with c = child[x][a] gets
+ *                  Q = c >= 0 ? wsum[c] / f32(visits[c]) : value[x]          n_a = c >= 0 ? visits[c] : 0
+ *                  U = ((c_puct * prior[x][a]) * sqrtf(f32(visits[x]))) / f32(1 + n_a)          score = Q + U
+ *              each operation one IEEE f32 operation rounded to nearest, in this order (no contraction; the plain `/` and sqrtf of the
+ *              build, which are the correctly rounded ones -- not __fsqrt_rn, which here is the native approximation).  The greatest score
+ *              wins (-0 = +0), ties go to the lowest action; scores are finite by contract and a NaN score is no candidate.  If the
+ *              winner has a child the descent goes on there; else it ends with (x, a) and the new node is j = n_nodes.
+ *              Out, i32[n_trees] each: src = pool index of x; dst = pool index of the new node, or n_trees*cap (out of range: what
+ *              qg_vec_copy_envs skips) where nothing is expanded; act = a, or num_actions ("no gate") where nothing is expanded; leaf =
+ *              the node the backup starts from: the new node, or x at a terminal node or where no action is a candidate, or -1 where the
+ *              tree makes no simulation that counts: finished_dev[m] != 0 (optional u8[n_trees]: the tree's real env is final), or a bound
+ *              or a range check below was hit.
+ *   backup     qg_mcts_backup in mode QG_MCTS_BACKUP, from qg_mcts_select's four outputs and the results of the expansion (logp_dev,
+ *              values_dev, reward_dev f32[n_trees], done_dev u8[n_trees]: the new node's env after its step).  leaf < 0: nothing.  Where
+ *              act < num_actions the node j = n_nodes is linked -- child[x][a] = j, parent[j] = x, reward[j], terminal[j] = done,
+ *              value[j] = values (0 if terminal), prior[j][.] = expf(logp), child[j][.] = -1, visits[j] = 0, wsum[j] = 0, n_nodes += 1.
+ *              Then G = value[leaf], and every node y != 0 from the leaf up gets G = reward[y] + G (one f32 addition), visits[y] += 1,
+ *              wsum[y] += G; the root gets visits[0] += 1.
+ * Safety: a descent makes at most cap levels and a walk at most cap steps, and both must move strictly (child > node > parent); every
+ * index read from the forest (a child, a parent, n_nodes, src, dst, leaf) is range-checked before it is used, an expansion must name node
+ * n_nodes < cap over an edge without a child.  A check that fails ends that tree's work for the call: qg_mcts_select gives leaf = -1 (act =
+ * num_actions, dst out of range), qg_mcts_backup returns from that tree (after a broken parent link: without counting the root).
+ * logp_dev: rows of ld >= num_actions floats, columns past num_actions are not read.  Limits: num_actions <= 256 (four actions per lane),
+ * 2 <= cap <= 8192 (qg_mcts_select keeps a tree's visits and wsum in LDS, so a level of the descent is one dependent trip to memory),
+ * n_trees*cap < 2^31 - 1; QG_ERR_UNSUPPORTED beyond, QG_ERR_INVALID for a null required pointer, a zero size, ld < num_actions, an unknown
+ * mode or a misaligned 32-bit array.  Stream-ordered on `stream`, one launch each (one wave per tree, several trees per workgroup), plain
+ * loads and stores only, no host reads, no synchronisation, capturable into a hipGraph. */
+typedef struct qg_mcts_forest {
+    int32_t *parent;
+    float *reward;
+    float *value;
+    int32_t *visits;
+    float *wsum;
+    uint8_t *terminal;
+    int32_t *child;
+    float *prior;
+    int32_t *n_nodes;
+    uint64_t n_trees;
+    uint32_t cap, num_actions;
+} qg_mcts_forest;
+typedef enum { QG_MCTS_ROOT = 0, QG_MCTS_BACKUP = 1 } qg_mcts_mode;
+size_t qg_mcts_forest_bytes(uint64_t n_trees, uint32_t cap, uint32_t num_actions);
+int qg_mcts_select(const qg_mcts_forest *forest, float c_puct, const uint8_t *finished_dev, int32_t *src_dev, int32_t *dst_dev, int32_t *act_dev,
+                   int32_t *leaf_dev, void *stream);
+int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int32_t *src_dev, const int32_t *dst_dev, const int32_t *act_dev,
+                   const int32_t *leaf_dev, const float *logp_dev, uint64_t ld, const float *values_dev, const float *reward_dev,
+                   const uint8_t *done_dev, void *stream);
 /* Twists, batched: the symmetries of the coupling map as views of the observation (Env::twists, clifford.rs:370-372; symmetry.rs:205-295).
  * For CliffordEnv, LinearFunctionEnv and PermutationEnv twist t is a pair: obs_perms[t] over the flat dense observation (rows * cols entries)
  * and act_perms[t] over the actions.  THE DEFINITION, proved on the oracle env for every kind, twist and action (tests/test_twist_views.py):

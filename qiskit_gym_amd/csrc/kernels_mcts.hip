@@ -1,0 +1,302 @@
+// kernels_mcts.hip -- the tree of a PUCT search (MCTS) over a policy's priors and values: qg_mcts_select (one descent per tree: which node to
+// expand, by which action) and qg_mcts_backup (link the new node, carry its value to the root; in mode QG_MCTS_ROOT: start a tree).  The rules
+// are stated in include/qgym.h; tests/mctsmodel.py restates them in numpy and the kernels agree with it bit for bit.
+//
+// The forest is a struct of plain arrays (qg_mcts_forest): per (tree, node) parent, reward, value, visits, wsum, terminal; per (tree, node,
+// action) child and prior; per tree n_nodes.  One WAVE per tree in both kernels, several trees per workgroup; a wave owns its tree for the
+// whole launch: plain vector loads and stores, no atomics, no barrier between waves.
+//
+// qg_mcts_select.  The lanes cover the actions of the node the descent stands on (action lane + 64 k, k < 4).  A level's score needs the
+// node's child and prior rows and, per expanded edge, the child's visits and wsum: the second would be a dependent memory trip behind the
+// first.  So the wave first copies its tree's (visits, wsum) pairs -- n_nodes of them, at most cap -- into LDS, one trip for the whole
+// tree; after that a level is ONE dependent trip to memory (child row, prior row, the node's value and terminal flag, all addressed by the
+// node alone) and LDS reads.  The arg-max is qg_beam_advance's: one 64-lane max of key = order(score) << 32 | ~action (-0 = +0, the lowest
+// action among equals, a NaN has no word), the winner's child index comes back by a lane read.
+//
+// Arithmetic: every operation of the score is one IEEE f32 operation, round to nearest -- the file is built with -ffp-contract=off, and
+// `/` and __builtin_sqrtf are the correctly rounded division and square root of this build (hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt; f32 denormals are kept on gfx950).  __fsqrt_rn is NOT used: without OCML_BASIC_ROUNDED_OPERATIONS
+// it is the native, approximate square root.
+//
+// Every loop is bounded by the data's own size -- a descent makes at most cap levels, a backup walk at most cap steps, and both also move
+// strictly (a child's index is above its parent's): an index read from the forest is range-checked before it is used, and a check that fails
+// ends that tree's work for the call (leaf = -1, which qg_mcts_backup skips).
+#include "device_common.hpp"
+#include "qgym_host.hpp"
+
+namespace qg {
+
+constexpr uint32_t MCTS_WAVES = 4;          // trees per workgroup (fewer where a tree's LDS copy is large)
+constexpr uint32_t MCTS_MAX_ACTIONS = 256;  // four actions per lane
+constexpr uint32_t MCTS_MAX_CAP = 8192;     // 8 bytes of LDS per node, one tree per workgroup at the limit
+
+// larger score <=> larger word; a NaN has no word (0); every other score's word is >= 0x007FFFFF
+__device__ inline uint32_t mcts_order(float score) {
+    if (score != score) return 0u;
+    uint32_t u = __float_as_uint(score);
+    if (u == 0x80000000u) u = 0u;  // -0 ties with +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ inline uint64_t mcts_wave_max(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64), lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+struct SelectArgs {
+    qg_mcts_forest f;
+    const uint8_t *finished;  // or nullptr
+    int32_t *src, *dst, *act, *leaf;
+    float C;
+    uint32_t waves;
+};
+
+__global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_select_kernel(const SelectArgs a) {
+    extern __shared__ uint2 mcts_lds[];  // [waves][cap]: (visits, bits of wsum) of the wave's tree
+    const qg_mcts_forest &f = a.f;
+    const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
+    const uint64_t m = (uint64_t)blockIdx.x * a.waves + wave;
+    if (m >= f.n_trees) return;  // (the whole wave)
+    const uint32_t cap = f.cap, A = f.num_actions;
+    const uint64_t base = m * cap;                    // the tree's node 0, and its env in the pool
+    const int32_t none = (int32_t)(f.n_trees * cap);  // out of range for the pool: qg_vec_copy_envs skips it
+    uint2 *st = mcts_lds + (size_t)wave * cap;
+
+    uint32_t x = 0;
+    int32_t leaf = -1, act = (int32_t)A, dst = none;
+    const uint32_t n = (uint32_t)f.n_nodes[m];
+    const bool run = !(a.finished && a.finished[m] != 0) && n >= 1 && n <= cap;
+    if (run) {
+        for (uint32_t j = lane; j < n; j += QG_WAVE) st[j] = make_uint2((uint32_t)f.visits[base + j], __float_as_uint(f.wsum[base + j]));
+        __builtin_amdgcn_wave_barrier();  // the wave reads what its other lanes wrote: LDS keeps a wave's accesses in order
+        for (uint32_t level = 0; level < cap; ++level) {
+            const uint64_t row = (base + x) * A;
+            // the level's one trip: everything here is addressed by x alone
+            const bool term = f.terminal[base + x] != 0;
+            const float vx = f.value[base + x];
+            int32_t c[4];
+            float p[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t ac = lane + QG_WAVE * k;
+                c[k] = ac < A ? f.child[row + ac] : -1;
+                p[k] = ac < A ? f.prior[row + ac] : 0.0f;
+            }
+            if (term) {  // the descent ends on a terminal node: nothing is expanded
+                leaf = (int32_t)x;
+                break;
+            }
+            const float sq = __builtin_sqrtf((float)(int32_t)st[x].x);
+            uint64_t key = 0;
+            bool bad = false;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t ac = lane + QG_WAVE * k;
+                if (ac >= A) continue;
+                float q = vx;
+                int32_t na = 0;
+                if (c[k] >= 0) {
+                    if ((uint32_t)c[k] >= n || (uint32_t)c[k] <= x) {  // no node of this tree, or no step down
+                        bad = true;
+                        continue;
+                    }
+                    const uint2 s = st[c[k]];
+                    na = (int32_t)s.x;
+                    q = __uint_as_float(s.y) / (float)na;
+                }
+                const float u = ((a.C * p[k]) * sq) / (float)(1 + na);
+                const uint32_t o = mcts_order(q + u);
+                const uint64_t kk = ((uint64_t)o << 32) | (uint64_t)(0xFFFFFFFFu - ac);
+                if (o && kk > key) key = kk;
+            }
+            if (__ballot(bad)) break;  // leaf stays -1: the tree's work ends here
+            const uint64_t top = mcts_wave_max(key);
+            if (top == 0) {  // no candidate (every score a NaN): nothing to expand
+                leaf = (int32_t)x;
+                break;
+            }
+            const uint32_t best = 0xFFFFFFFFu - (uint32_t)top, k = best >> 6;
+            const int32_t mine = k == 0 ? c[0] : k == 1 ? c[1] : k == 2 ? c[2] : c[3];
+            const int32_t next = __shfl(mine, (int)(best & (QG_WAVE - 1)), 64);
+            if (next < 0) {  // an unexpanded edge: the new node is n_nodes, if the tree has room
+                if (n < cap) {
+                    leaf = (int32_t)n;
+                    dst = (int32_t)(base + n);
+                    act = (int32_t)best;
+                }
+                break;
+            }
+            x = (uint32_t)next;  // x < next < n: at most cap - 1 steps down
+        }
+    }
+    if (lane == 0) {
+        a.src[m] = (int32_t)(base + x);
+        a.dst[m] = dst;
+        a.act[m] = act;
+        a.leaf[m] = leaf;
+    }
+}
+
+struct BackupArgs {
+    qg_mcts_forest f;
+    const int32_t *src, *dst, *act, *leaf;
+    const float *logp, *values, *reward;
+    const uint8_t *done;  // mode ROOT: or nullptr
+    uint64_t ld;
+    int32_t mode;
+};
+
+// the rows of node `node`: no child yet, prior = expf(logp)
+__device__ inline void mcts_open_node(const qg_mcts_forest &f, uint64_t node, const float *logp, uint32_t lane) {
+    for (uint32_t ac = lane; ac < f.num_actions; ac += QG_WAVE) {
+        f.child[node * f.num_actions + ac] = -1;
+        f.prior[node * f.num_actions + ac] = expf(logp[ac]);
+    }
+}
+
+__global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_kernel(const BackupArgs a) {
+    const qg_mcts_forest &f = a.f;
+    const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
+    const uint64_t m = (uint64_t)blockIdx.x * MCTS_WAVES + wave;
+    if (m >= f.n_trees) return;  // (the whole wave)
+    const uint32_t cap = f.cap, A = f.num_actions;
+    const uint64_t base = m * cap;
+    const float *logp = a.logp + m * a.ld;
+
+    if (a.mode == QG_MCTS_ROOT) {
+        const bool term = a.done && a.done[m] != 0;
+        mcts_open_node(f, base, logp, lane);
+        if (lane == 0) {
+            f.parent[base] = -1;
+            f.reward[base] = 0.0f;
+            f.value[base] = term ? 0.0f : a.values[m];
+            f.visits[base] = 1;
+            f.wsum[base] = 0.0f;
+            f.terminal[base] = term ? 1 : 0;
+            f.n_nodes[m] = 1;
+        }
+        return;
+    }
+
+    const int32_t leaf = a.leaf[m];
+    uint32_t n = (uint32_t)f.n_nodes[m];
+    if (leaf < 0 || n < 1 || n > cap) return;  // no simulation that counts
+    const uint32_t ac = (uint32_t)a.act[m];
+    const bool expand = ac < A;
+    float g;  // the leaf's value
+    if (expand) {
+        const int64_t x = (int64_t)a.src[m] - (int64_t)base, j = (int64_t)a.dst[m] - (int64_t)base;
+        // the new node is n_nodes, below cap, the child of a node of this tree by an edge that has none
+        if (x < 0 || x >= (int64_t)n || j != (int64_t)n || j >= (int64_t)cap || leaf != (int32_t)j) return;
+        if (f.child[(base + (uint64_t)x) * A + ac] != -1) return;
+        const bool term = a.done[m] != 0;
+        g = term ? 0.0f : a.values[m];
+        mcts_open_node(f, base + (uint64_t)j, logp, lane);
+        if (lane == 0) {
+            f.parent[base + j] = (int32_t)x;
+            f.reward[base + j] = a.reward[m];
+            f.value[base + j] = g;
+            f.visits[base + j] = 0;
+            f.wsum[base + j] = 0.0f;
+            f.terminal[base + j] = term ? 1 : 0;
+            f.child[(base + (uint64_t)x) * A + ac] = (int32_t)j;
+            f.n_nodes[m] = (int32_t)(n + 1);
+        }
+        n += 1;
+    } else {
+        if ((uint32_t)leaf >= n) return;
+        g = f.value[base + (uint32_t)leaf];
+    }
+    if (lane != 0) return;
+    // the walk, on one lane (its own stores above are in program order before these loads): one trip per level, every address is y's
+    uint32_t y = (uint32_t)leaf;
+    for (uint32_t step = 0; step < cap && y != 0; ++step) {
+        const int32_t up = f.parent[base + y];
+        g = f.reward[base + y] + g;
+        f.visits[base + y] += 1;
+        f.wsum[base + y] += g;
+        if (up < 0 || (uint32_t)up >= y) return;  // no step up: the root is not counted
+        y = (uint32_t)up;
+    }
+    if (y == 0) f.visits[base] += 1;
+}
+
+static int mcts_check_forest(const qg_mcts_forest *f, const char *who) {
+    if (!f) return set_error(QG_ERR_INVALID, "null argument");
+    if (!f->parent || !f->reward || !f->value || !f->visits || !f->wsum || !f->terminal || !f->child || !f->prior || !f->n_nodes)
+        return set_error(QG_ERR_INVALID, "%s: a forest array is null", who);
+    if (f->cap < 2 || f->num_actions == 0) return set_error(QG_ERR_INVALID, "%s: bad shape: cap >= 2 (one search) and num_actions >= 1", who);
+    if (((uintptr_t)f->parent % 4) || ((uintptr_t)f->reward % 4) || ((uintptr_t)f->value % 4) || ((uintptr_t)f->visits % 4) || ((uintptr_t)f->wsum % 4) ||
+        ((uintptr_t)f->child % 4) || ((uintptr_t)f->prior % 4) || ((uintptr_t)f->n_nodes % 4))
+        return set_error(QG_ERR_INVALID, "%s: 32-bit arrays must be aligned to their element size", who);
+    if (f->num_actions > MCTS_MAX_ACTIONS || f->cap > MCTS_MAX_CAP)
+        return set_error(QG_ERR_UNSUPPORTED, "%s: num_actions <= %u and cap <= %u supported", who, MCTS_MAX_ACTIONS, MCTS_MAX_CAP);
+    if (f->n_trees > 0x7FFFFFFFull || f->n_trees * f->cap >= 0x7FFFFFFFull) return set_error(QG_ERR_UNSUPPORTED, "%s: too many nodes for 32-bit pool indices", who);
+    return QG_OK;
+}
+
+}  // namespace qg
+
+using namespace qg;
+
+extern "C" size_t qg_mcts_forest_bytes(uint64_t n_trees, uint32_t cap, uint32_t num_actions) {
+    return (size_t)(n_trees * cap * (21ull + 8ull * num_actions) + n_trees * 4ull);
+}
+
+extern "C" int qg_mcts_select(const qg_mcts_forest *forest, float c_puct, const uint8_t *finished_dev, int32_t *src_dev, int32_t *dst_dev, int32_t *act_dev,
+                              int32_t *leaf_dev, void *stream) {
+    if (const int rc = mcts_check_forest(forest, "mcts_select")) return rc;
+    if (!src_dev || !dst_dev || !act_dev || !leaf_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4))
+        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (forest->n_trees == 0) return QG_OK;
+    SelectArgs a;
+    a.f = *forest;
+    a.finished = finished_dev;
+    a.src = src_dev;
+    a.dst = dst_dev;
+    a.act = act_dev;
+    a.leaf = leaf_dev;
+    a.C = c_puct;
+    const uint32_t fit = 65536u / (forest->cap * (uint32_t)sizeof(uint2));  // trees whose LDS copies fit one workgroup: >= 1 by MCTS_MAX_CAP
+    a.waves = fit < MCTS_WAVES ? fit : MCTS_WAVES;
+    const dim3 grid((unsigned)((forest->n_trees + a.waves - 1) / a.waves)), block(64u * a.waves);
+    hipLaunchKernelGGL(mcts_select_kernel, grid, block, (size_t)a.waves * forest->cap * sizeof(uint2), (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}
+
+extern "C" int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int32_t *src_dev, const int32_t *dst_dev, const int32_t *act_dev,
+                              const int32_t *leaf_dev, const float *logp_dev, uint64_t ld, const float *values_dev, const float *reward_dev,
+                              const uint8_t *done_dev, void *stream) {
+    if (const int rc = mcts_check_forest(forest, "mcts_backup")) return rc;
+    if (mode != QG_MCTS_ROOT && mode != QG_MCTS_BACKUP) return set_error(QG_ERR_INVALID, "mode must be 0 (root) or 1 (backup)");
+    if (!logp_dev || !values_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (mode == QG_MCTS_BACKUP && (!src_dev || !dst_dev || !act_dev || !leaf_dev || !reward_dev || !done_dev)) return set_error(QG_ERR_INVALID, "null argument");
+    if (ld < forest->num_actions) return set_error(QG_ERR_INVALID, "bad shape: ld >= num_actions");
+    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4) || ((uintptr_t)logp_dev % 4) ||
+        ((uintptr_t)values_dev % 4) || ((uintptr_t)reward_dev % 4))
+        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (forest->n_trees == 0) return QG_OK;
+    BackupArgs a;
+    a.f = *forest;
+    a.src = src_dev;
+    a.dst = dst_dev;
+    a.act = act_dev;
+    a.leaf = leaf_dev;
+    a.logp = logp_dev;
+    a.values = values_dev;
+    a.reward = reward_dev;
+    a.done = done_dev;
+    a.ld = ld;
+    a.mode = mode;
+    const dim3 grid((unsigned)((forest->n_trees + MCTS_WAVES - 1) / MCTS_WAVES)), block(64u * MCTS_WAVES);
+    hipLaunchKernelGGL(mcts_backup_kernel, grid, block, 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}

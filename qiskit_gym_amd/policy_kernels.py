@@ -1,4 +1,4 @@
-"""The policy-layer kernels from Python: thin ctypes wrappers around libqgym's sampling, beam, twist and policy-layer entries, the
+"""The policy-layer kernels from Python: thin ctypes wrappers around libqgym's sampling, beam, tree-search, twist and policy-layer entries, the
 reference-shaped `BasicPolicy`, and the kernels' packed operands -- the one layer below both of their callers, the rollout collector
 (`collector.py`) and the batched searches (`synthesis.py`): vec -> policy_kernels -> {collector, synthesis}.
 
@@ -157,6 +157,100 @@ def beam_advance(parent: torch.Tensor, ret_in: torch.Tensor, reward: torch.Tenso
                                            group_live.data_ptr(), bounded.data_ptr() if bounded is not None else None, int(skip), float(bonus),
                                            _lib.BOUND_MODES[mode], _stream_ptr()))
     return ret_out, win_src, group_live
+
+
+MCTS_MAX_FOREST_BYTES = 1 << 30  # what `mcts_forest` allocates at most unless told otherwise: 1 GiB
+
+
+class MctsForest:
+    """The trees of a PUCT search as a struct of arrays (`qg_mcts_forest`), one tree per target, torch tensors on one device:
+    `parent` int32, `reward` f32, `value` f32, `visits` int32, `wsum` f32, `terminal` uint8, all [M, cap]; `child` int32 (-1 = not expanded)
+    and `prior` f32, [M, cap, A]; `n_nodes` int32 [M].  `cap` = N + 1 nodes for N simulations; node 0 is the root; node j of tree m goes
+    with env m * cap + j of a pool handle.  Only the nodes below `n_nodes[m]` mean anything.  `mcts_backup(root=True)` starts every tree."""
+    FIELDS = ("parent", "reward", "value", "visits", "wsum", "terminal", "child", "prior", "n_nodes")
+
+    def __init__(self, M: int, N: int, A: int, device):
+        self.M, self.N, self.A, self.cap, self.device = M, N, A, N + 1, torch.device(device)
+        i32, f32, cap = torch.int32, torch.float32, N + 1
+        for name, shape, dt in (("parent", (M, cap), i32), ("reward", (M, cap), f32), ("value", (M, cap), f32), ("visits", (M, cap), i32), ("wsum", (M, cap), f32),
+                                ("terminal", (M, cap), torch.uint8), ("child", (M, cap, A), i32), ("prior", (M, cap, A), f32), ("n_nodes", (M,), i32)):
+            setattr(self, name, torch.zeros(shape, dtype=dt, device=self.device))
+        self._c = _lib.QGMctsForest(*(getattr(self, name).data_ptr() for name in self.FIELDS), M, cap, A)
+
+    @property
+    def skip(self) -> int:
+        """What `mcts_select` writes to `dst` where nothing is expanded: no env of the pool, `copy_envs` skips it."""
+        return self.M * self.cap
+
+
+def mcts_forest(M: int, N: int, A: int, device=None, max_bytes: int = MCTS_MAX_FOREST_BYTES) -> MctsForest:
+    """An empty forest for `mcts_select` / `mcts_backup`: M trees of N + 1 nodes over A actions (`qg_mcts_forest_bytes` says what it takes:
+    (N + 1) * (21 + 8 A) + 4 bytes per tree).  ValueError for M < 1, N < 1, A < 1 or a forest of more than `max_bytes`."""
+    M, N, A = int(M), int(N), int(A)
+    if M < 1 or N < 1 or A < 1:
+        raise ValueError("mcts_forest: M >= 1, N >= 1 and A >= 1")
+    nbytes = int(_lib.load().qg_mcts_forest_bytes(M, N + 1, A))
+    if nbytes > int(max_bytes):
+        raise ValueError(f"mcts_forest: {M} trees of {N + 1} nodes over {A} actions take {nbytes} bytes, more than the limit of {int(max_bytes)}")
+    return MctsForest(M, N, A, "cuda" if device is None else device)
+
+
+def _mcts_vectors(name: str, forest: MctsForest, items):
+    """`items`: (name, tensor or None, dtype); every tensor given must be a contiguous [M] tensor of its dtype on the forest's device."""
+    for nm, t, dt in items:
+        if t is not None and (t.dtype != dt or t.dim() != 1 or t.numel() != forest.M or not t.is_contiguous() or t.device != forest.parent.device):
+            raise ValueError(f"{name}: {nm} must be a contiguous [{forest.M}] {dt} tensor on the forest's device")
+
+
+def mcts_select(forest: MctsForest, C: float, finished: Optional[torch.Tensor] = None, src: Optional[torch.Tensor] = None,
+                dst: Optional[torch.Tensor] = None, act: Optional[torch.Tensor] = None, leaf: Optional[torch.Tensor] = None):
+    """One PUCT descent per tree (`qg_mcts_select`): from the root, at every node the action of the greatest
+    `Q + ((C * prior) * sqrt(visits[node])) / (1 + n_a)` (f32, each operation rounded once; Q = wsum / visits of the child, the node's
+    own value where the edge has no child; ties to the lowest action), down to an edge without a child or a terminal node.
+    finished: optional uint8 / bool [M], trees whose real env is final: they make no simulation.  Returns int32 [M] each: (src, the pool
+    index of the node to expand from; dst, the pool index of the new node -- `forest.skip`, out of range, where nothing is expanded; act,
+    the action -- A where nothing is expanded; leaf, the node `mcts_backup` starts from, -1: none).  Preallocated outputs may be passed."""
+    if not isinstance(forest, MctsForest):
+        raise TypeError("mcts_select: forest must come from mcts_forest")
+    if not float(C) > 0.0:
+        raise ValueError("mcts_select: C must be positive")
+    dev, i32 = forest.parent.device, torch.int32
+    if finished is not None and finished.dtype == torch.bool:
+        finished = finished.view(torch.uint8)
+    src, dst, act, leaf = (torch.empty(forest.M, dtype=i32, device=dev) if t is None else t for t in (src, dst, act, leaf))
+    _mcts_vectors("mcts_select", forest, (("finished", finished, torch.uint8), ("src", src, i32), ("dst", dst, i32), ("act", act, i32), ("leaf", leaf, i32)))
+    _lib.check(_lib.load().qg_mcts_select(forest._c, float(C), finished.data_ptr() if finished is not None else None, src.data_ptr(), dst.data_ptr(),
+                                          act.data_ptr(), leaf.data_ptr(), _stream_ptr()))
+    return src, dst, act, leaf
+
+
+def mcts_backup(forest: MctsForest, logp: torch.Tensor, values: torch.Tensor, reward: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
+                src: Optional[torch.Tensor] = None, dst: Optional[torch.Tensor] = None, act: Optional[torch.Tensor] = None,
+                leaf: Optional[torch.Tensor] = None, root: bool = False) -> MctsForest:
+    """The other half of a simulation (`qg_mcts_backup`), in place on `forest`.  logp: f32 [M, >= A] with unit column stride, the rows of
+    log-probabilities (`mid_head_logp`'s, or `log_softmax`) and values: f32 [M], the value head, of the envs just evaluated.
+    root=True starts every tree from them: node 0 with prior = exp(logp), value (0 if `done`: optional), visits 1, no children.
+    Otherwise src, dst, act, leaf are `mcts_select`'s outputs and reward f32 [M], done uint8 / bool [M] the expanded envs' step results:
+    where act < A the new node is linked under (src, act) with prior = exp(logp), its value (0 if done), reward and terminal flag; then
+    from `leaf` up G = value[leaf], G = reward[y] + G, visits[y] += 1, wsum[y] += G for every node but the root, whose visits grow by 1.
+    Trees with leaf < 0 are left alone."""
+    if not isinstance(forest, MctsForest):
+        raise TypeError("mcts_backup: forest must come from mcts_forest")
+    M, A, dev, i32, f32 = forest.M, forest.A, forest.parent.device, torch.int32, torch.float32
+    if logp.dtype != f32 or logp.dim() != 2 or logp.shape[0] != M or logp.shape[1] < A or logp.device != dev or (logp.stride(1) != 1 and logp.shape[1] > 1) or (
+            M > 1 and logp.stride(0) < A):
+        raise ValueError("mcts_backup: logp must be f32 [M, >= A] with unit column stride on the forest's device")
+    if done is not None and done.dtype == torch.bool:
+        done = done.view(torch.uint8)
+    _mcts_vectors("mcts_backup", forest, (("values", values, f32), ("reward", reward, f32), ("done", done, torch.uint8), ("src", src, i32), ("dst", dst, i32),
+                                         ("act", act, i32), ("leaf", leaf, i32)))
+    if values is None or (not root and any(t is None for t in (reward, done, src, dst, act, leaf))):
+        raise ValueError("mcts_backup: values always; reward, done, src, dst, act and leaf unless root=True")
+    ptr = [t.data_ptr() if t is not None else None for t in (src, dst, act, leaf)]
+    _lib.check(_lib.load().qg_mcts_backup(forest._c, _lib.MCTS_ROOT if root else _lib.MCTS_BACKUP, *ptr, logp.data_ptr(), logp.stride(0) if M > 1 else logp.shape[1],
+                                          values.data_ptr(), reward.data_ptr() if reward is not None else None, done.data_ptr() if done is not None else None,
+                                          _stream_ptr()))
+    return forest
 
 
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,

@@ -18,6 +18,10 @@ recovered by replaying the winners on a `track_solution` batch.
 the batched clone (`VecEnv.copy_envs`) and the device-side selection kernel (`collector.beam_select`); see `solve`.  `bound="stop"` ends a
 target's search once no beam of it can beat its winner (`collector.beam_advance`, which is also the step's bookkeeping in one launch).
 
+`solve(..., deterministic=True, num_mcts_searches=N)` is the reference's third way to search: a PUCT tree search per target, N simulations
+per decision, the trees in plain device arrays (`collector.mcts_forest`), selection and backup on two kernels (`collector.mcts_select`,
+`collector.mcts_backup`), the expansion on the batched clone and one forward pass for all targets; see `solve`.
+
 `solve(..., fast=True)` takes the policy off the tensor library: the first layer reads the bit-packed state (`collector.embed` /
 `embed_words`), the rest is one kernel that either draws (`mid_head_sample`: the sampled searches) or, for the greedy and the beam search,
 writes the arg-max and the row of log-probabilities (`mid_head_logp`), which `beam_select` reads as it stands.
@@ -45,8 +49,8 @@ import torch
 
 from . import _lib
 from .envs.gyms import ROTATION_MARKER
-from .policy_kernels import (BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer, mid_head_logp, mid_head_sample,
-                             run_first_layer, sample_actions)
+from .policy_kernels import (MCTS_MAX_FOREST_BYTES, BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
+                             mcts_backup, mcts_forest, mcts_select, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
 from .vec import VecEnv
 
 
@@ -95,7 +99,8 @@ def _winner(solved: torch.Tensor, ret: torch.Tensor):
 
 class _Forward:
     """What the step loops ask about a handle's current state: `logp(vec)`, the rows of log-probabilities [B, A] f32 (beam search);
-    `greedy(vec)`, the arg-max, int32 [B]; `draw(vec, t)`, the draw of step t from `seed`, int32 [B].  Under twists (`tw` int32 [B]: env e
+    `greedy(vec)`, the arg-max, int32 [B]; `draw(vec, t)`, the draw of step t from `seed`, int32 [B]; `logp_values(vec)`, the rows and the
+    value head, f32 [B] (the tree search: priors and leaf values).  Under twists (`tw` int32 [B]: env e
     is seen through twist tw[e]) the answers are about the view, and `real_actions` maps a choice back.  `kernels` is for `last_stats`."""
 
     def __init__(self, seed: int, tw: Optional[torch.Tensor]):
@@ -114,15 +119,22 @@ class _TorchForward(_Forward):
         super().__init__(seed, tw)
         self.policy, self.dtype = policy, dtype
 
-    def _logits(self, vec: VecEnv) -> torch.Tensor:
-        """The policy on what it reads, in its dtype: the observation, or the view.  A dtype the library does not write (float64) is written
-        as float32 and widened: the entries are 0 and 1."""
+    def _outputs(self, vec: VecEnv):
+        """The policy's two outputs on what it reads, in its dtype: the observation, or the view.  A dtype the library does not write
+        (float64) is written as float32 and widened: the entries are 0 and 1."""
         dt = self.dtype if self.dtype in VecEnv._DTYPES else torch.float32
         x = vec.observe_as(dt) if self.tw is None else vec.observe_twisted(self.tw, dt)
-        return self.policy(x if dt == self.dtype else x.to(self.dtype))[0]
+        return self.policy(x if dt == self.dtype else x.to(self.dtype))
+
+    def _logits(self, vec: VecEnv) -> torch.Tensor:
+        return self._outputs(vec)[0]
 
     def logp(self, vec: VecEnv) -> torch.Tensor:
         return torch.log_softmax(self._logits(vec).float(), dim=1)
+
+    def logp_values(self, vec: VecEnv) -> Tuple[torch.Tensor, torch.Tensor]:
+        logits, value = self._outputs(vec)
+        return torch.log_softmax(logits.float(), dim=1), value.float().reshape(-1).contiguous()
 
     def greedy(self, vec: VecEnv) -> torch.Tensor:
         return self._logits(vec).argmax(dim=1).to(torch.int32)
@@ -160,6 +172,9 @@ class _KernelForward(_Forward):
         p, s = self.packed, self.scratch
         return mid_head_logp(self._first_layer(vec), p.mid, self.common, p.head, self.A, logp_rows=self.rows, actions=self.act, best_logp=s[0],
                              entropy=s[1], values=s[2])[0]
+
+    def logp_values(self, vec: VecEnv) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self.logp(vec), self.scratch[2]  # `mid_head_logp` writes both
 
     def greedy(self, vec: VecEnv) -> torch.Tensor:
         p, s = self.packed, self.scratch
@@ -202,7 +217,8 @@ class BatchedSynthesis:
         """The handles of `kind`, one per entry of `batches`: "search" (the sampled and greedy searches' batch), "replay" (the winners of a
         PauliGym search, replayed with the solution log on) or "beam" (the two batches of targets * width envs that take turns as source and
         destination of the per-step copy, and the winners, all three with the same constructor arguments: the rule of `copy_envs`; no layout
-        choice depends on the batch size).  One batch shape at a time per kind: the handles own device memory."""
+        choice depends on the batch size) or "mcts" (the pool of targets * (N + 1) node envs, the leaf batch and the real batch of one env per
+        target, again all with the same constructor arguments).  One batch shape at a time per kind: the handles own device memory."""
         key = (*batches, perms)  # add_perms: twists() only, the env steps alike
         held = self._held.get(kind)
         if held is not None and held.key != key:
@@ -370,10 +386,64 @@ class BatchedSynthesis:
             self.last_stats.update(bound=bound, bounded=int(bounded.sum()))
         return out
 
+    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool):
+        """The search of `solve(num_mcts_searches=N)` on the handles of `held`: the leaf batch, which is all the forward object reads, the pool
+        (node j of target m is env m * (N + 1) + j) and the real envs.  Per decision one forward pass on the roots and N simulations of `mcts_select`,
+        clone + step, one forward pass, clone back, `mcts_backup`; the rules are stated in include/qgym.h and tests/mctsmodel.py."""
+        leaf, pool, real = held.vecs
+        M, A, dev = real.batch, real.num_actions(), real.device
+        T, cap = int(real._cfg.max_depth), N + 1
+        forest = mcts_forest(M, N, A, dev)
+        fwd = self._forward(held, 1, None, kernels, rows=True)
+        self._load(real, states, 1)
+        ids = torch.arange(M, dtype=torch.int32, device=dev)
+        roots = ids * cap
+        finished = real.success.bool().to(torch.uint8)  # a target that is already solved needs no gates
+        parked = torch.full((M,), A, dtype=torch.int32, device=dev)  # out of range: no gate (clifford.rs:324)
+        picked = tuple(torch.empty(M, dtype=torch.int32, device=dev) for _ in range(4))  # src, dst, act, leaf of a simulation
+        keys = torch.arange(A - 1, -1, -1, dtype=torch.int64, device=dev)  # equal visits: the lowest action has the greatest key
+        nodes, decisions = torch.zeros((), dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
+        steps = 0
+        for t in range(T):
+            leaf.copy_envs(real, ids)
+            rows, values = fwd.logp_values(leaf)
+            pool.copy_envs(leaf, ids, roots)
+            mcts_backup(forest, rows, values, done=finished, root=True)
+            for _ in range(N):
+                src, dst, act, lf = mcts_select(forest, C, finished, *picked)
+                leaf.copy_envs(pool, src)
+                leaf.step(act)  # A where nothing is expanded: no gate, and `dst` names no env of the pool
+                rows, values = fwd.logp_values(leaf)
+                pool.copy_envs(leaf, ids, dst)
+                mcts_backup(forest, rows, values, leaf.reward, leaf.done, src, dst, act, lf)
+            # the decision: the root's expanded action of the most visits, the lowest among equals; A where the root has no child
+            child = forest.child[:, 0, :].to(torch.int64)
+            visits = torch.gather(forest.visits.to(torch.int64), 1, child.clamp(min=0))
+            best = torch.where(child >= 0, visits * A + keys, -1).max(dim=1).values  # a key per (visits, action): no two alike
+            move = torch.where((best >= 0) & (finished == 0), A - 1 - best % A, parked).to(torch.int32)
+            live = finished == 0
+            nodes += (forest.n_nodes * live).sum()
+            decisions += live.sum()
+            real.step(move)
+            finished |= real.done.bool().to(torch.uint8)
+            steps = t + 1
+            if t % 8 == 7 and bool(finished.all()):
+                break
+        real.sync()
+        sols, lens = real.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
+        ok = real.success.bool().cpu().numpy()
+        # a finished env was handed A from then on, which the log of some env kinds records: such entries are no gates and no markers
+        out = [[int(x) for x in sols[m, : lens[m]] if x < A or x >= ROTATION_MARKER] if ok[m] else None for m in range(M)]
+        gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
+        self.last_stats = {"mcts": N, "targets": M, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0,
+                           "nodes": float(nodes) / max(int(decisions), 1), "kernels": fwd.kernels}
+        return out
+
     @torch.no_grad()
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
               beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None,
-              twist_kernels: bool = False, bound: Optional[str] = None) -> List[Optional[List[int]]]:
+              twist_kernels: bool = False, bound: Optional[str] = None, num_mcts_searches: int = 0, C: float = 2 ** 0.5,
+              max_expand_depth: int = 1) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         The rules of the sampled and the greedy search -- env m * S + s is search s of target m, the draw of step t is the race of
         `sample_actions(logits, seed, t)`, a finished env gets no gate and adds no reward, the loop ends at the first step t with
@@ -440,11 +510,34 @@ class BatchedSynthesis:
         torch path, solutions hold real actions, and `last_stats` carries "kernels": True beside "views"; as for `fast`, bf16 products may
         rank two nearly equal actions the other way round than the torch forward, so results can differ from `twists=V` alone.
         ValueError: without `twists`, together with `fast=True`, on PauliGym, with a policy that is not a `BasicPolicy` of the kernels'
-        shape, or an observation of more than 64 columns."""
+        shape, or an observation of more than 64 columns.
+
+        num_mcts_searches=N >= 1, with deterministic=True (default 0: none of this; every code path, handle and `last_stats` as without
+        the argument): a PUCT tree search per target, the reference's `num_mcts_searches`, `C` and `max_expand_depth`
+        (rl/synthesis.py:112-124; here keyword arguments behind the others, with the reference's defaults).  Every target gets a tree of
+        N + 1 nodes, rebuilt for every decision: the root is a clone of the target's real env with the policy's probabilities as priors and
+        its value head as value; each of N simulations descends by the greatest `Q + C * prior * sqrt(visits[node]) / (1 + visits[child])`
+        (Q: the child's mean backed-up return, the node's own value for an edge not yet tried; ties to the lowest action;
+        `collector.mcts_select`), expands one node -- a clone of its parent's env (`VecEnv.copy_envs`) stepped with the action, asked
+        about by one forward pass for all targets -- and adds its value plus the rewards on the way up to every node above it
+        (`collector.mcts_backup`).  After N simulations the real env takes the root's most visited action (the lowest among equals); a real
+        env that is final gets no more gates and its tree no more simulations; the loop ends like the other searches'.  The answer is
+        the real env's solution log where the episode ended in success (PauliGym: rotation markers included), else None.  The exact
+        rules, operation by operation, are in include/qgym.h and restated in tests/mctsmodel.py.  fast=True runs the forward passes on
+        the policy-layer kernels (`mid_head_logp`: rows and values), None / False on the torch forward.  `last_stats`: "mcts" (N),
+        "targets", "steps" (decisions), "solved", "mean_gates", "nodes" (mean nodes per tree and decision) and "kernels".  ValueError:
+        N < 0; C <= 0; max_expand_depth != 1 (not built: what twisterl means by it cannot be read from the reference);
+        deterministic=False (sampling a move from the visit counts is not built); together with beam_width, merge_duplicates, bound,
+        twists or twist_kernels; a forest -- targets * (N + 1) * (21 + 8 * num_actions) bytes -- of more than 1 GiB
+        (`policy_kernels.MCTS_MAX_FOREST_BYTES`; the pool of targets * (N + 1) envs comes on top); N + 1 > 8 192 or more than 256
+        actions is the library's QGymError."""
         M = len(states)
         self._check_options(M == 0, fast, beam_width, merge_duplicates, twists, twist_kernels, bound)
+        N = self._check_mcts(M, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth)
         if M == 0:
             return []
+        if N:
+            return self._mcts_search(states, self._handles("mcts", (M, M * (N + 1), M)), N, float(C), fast is True)  # kernels: on request only
         views = None if twists is None else self._views(int(twists))
         if beam_width is None:
             return self._sampled_search(states, deterministic, num_searches, fast, views, twist_kernels)
@@ -482,6 +575,29 @@ class BatchedSynthesis:
             if self.env.env_kind == "pauli":
                 raise ValueError("bound: a PauliGym step adds pauli_layer_reward per released rotation (pauli.rs:634), and a target may hold rotations "
                                  "beyond the observed columns: the reward still to come has no bound the search can see")
+
+    def _check_mcts(self, targets: int, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth) -> int:
+        """`num_mcts_searches` as an int, after the ValueErrors of `solve`'s tree search; 0: no tree search, and `C` and `max_expand_depth`
+        mean nothing."""
+        N = int(num_mcts_searches)
+        if N < 0:
+            raise ValueError("num_mcts_searches must be at least 0")
+        if N == 0:
+            return 0
+        if not float(C) > 0.0:
+            raise ValueError("C must be positive")
+        if int(max_expand_depth) != 1:
+            raise ValueError("max_expand_depth: only 1 is built (one new node per simulation)")
+        if not deterministic:
+            raise ValueError("num_mcts_searches needs deterministic=True: sampling a move from the visit counts is not built")
+        mixed = [name for name, on in (("beam_width", beam_width is not None), ("merge_duplicates", merge_duplicates), ("bound", bound is not None),
+                                       ("twists", twists is not None), ("twist_kernels", twist_kernels)) if on]
+        if mixed:
+            raise ValueError(f"num_mcts_searches cannot be combined with {', '.join(mixed)}")
+        nbytes = int(_lib.load().qg_mcts_forest_bytes(targets, min(N + 1, 2 ** 32 - 1), len(self.env.config["gateset"])))
+        if nbytes > MCTS_MAX_FOREST_BYTES:
+            raise ValueError(f"num_mcts_searches={N}: the forest of {targets} targets takes {nbytes} bytes, more than the limit of {MCTS_MAX_FOREST_BYTES}")
+        return N
 
     def _sampled_search(self, states, deterministic: bool, num_searches: int, fast: Optional[bool], views: Optional[List[int]], twist_kernels: bool):
         """The sampled and the greedy search of `solve`: every (target, search) pair is one env of the "search" handle, one view per search;
@@ -548,10 +664,12 @@ class BatchedSynthesis:
         return out
 
     def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
-              twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False, bound: Optional[str] = None):
+              twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False, bound: Optional[str] = None,
+              num_mcts_searches: int = 0, C: float = 2 ** 0.5, max_expand_depth: int = 1):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
         sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, fast=fast, beam_width=beam_width,
-                          merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels, bound=bound)
+                          merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels, bound=bound,
+                          num_mcts_searches=num_mcts_searches, C=C, max_expand_depth=max_expand_depth)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):
