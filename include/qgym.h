@@ -35,7 +35,7 @@ extern "C" {
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
  *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance, qg_mcts_forest_bytes,
- *      qg_mcts_select, qg_mcts_backup (additions only) */
+ *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -513,7 +513,26 @@ int qg_beam_advance(uint64_t n_groups, uint32_t width, const int32_t *parent_dev
  * 2 <= cap <= 8192 (qg_mcts_select keeps a tree's visits and wsum in LDS, so a level of the descent is one dependent trip to memory),
  * n_trees*cap < 2^31 - 1; QG_ERR_UNSUPPORTED beyond, QG_ERR_INVALID for a null required pointer, a zero size, ld < num_actions, an unknown
  * mode or a misaligned 32-bit array.  Stream-ordered on `stream`, one launch each (one wave per tree, several trees per workgroup), plain
- * loads and stores only, no host reads, no synchronisation, capturable into a hipGraph. */
+ * loads and stores only, no host reads, no synchronisation, capturable into a hipGraph.
+ *   decision   qg_mcts_decide, after a decision's simulations: the root's visit counts and the move they give.  It writes nothing into the
+ *              forest (tests/mctssample_model.py restates it in integers; results agree bit for bit).
+ *     counts   For every action a < num_actions with c = child[0][a]: n_a = visits[c] where c is a child of this tree's root, that is
+ *              0 < c < n_nodes; n_a = 0 where c < 0 (not expanded).  A child index c >= 0 outside that range, n_nodes outside [1, cap] or
+ *              a negative visits value ends the tree's work for the call: move = num_actions and every count 0.  Nothing read from the
+ *              forest is used as an index before it is range-checked.
+ *     QG_MCTS_MOST_VISITED   the action of the greatest n_a among the expanded edges (c > 0), the lowest action among equals -- one 64-lane
+ *              max of n_a << 32 | ~a; num_actions where the root has no child.
+ *     QG_MCTS_SAMPLE   total = sum of the n_a (at most cap - 1 in a tree the kernels built; summed in 64 bits, so exact whatever the
+ *              arrays hold).  total = 0 gives the answer of QG_MCTS_MOST_VISITED.  Otherwise r = mulhi64(rng_draw(seed ^ 0x6D637473, m,
+ *              counter), total) with m the tree index -- the counter RNG and the integer draw of qg_vec_reset, 0 <= r < total -- and the
+ *              move is the lowest action a with n_0 + ... + n_a > r, the sums in action order.  Integer arithmetic throughout: the
+ *              result is exact and does not depend on the launch geometry; an action with n_a = 0 is never drawn, and action a is drawn
+ *              for n_a of the total values of r.
+ *     finished_dev   optional u8[n_trees]: a tree whose real env is final gets move = num_actions and is otherwise treated alike.
+ *     counts_dev     optional i32[n_trees][counts_ld], counts_ld >= num_actions: the row of n_a (the training target of an AlphaZero-style
+ *              learner), written for finished trees too; columns past num_actions are not written.
+ *              move_dev i32[n_trees].  QG_ERR_INVALID for an unknown mode, a null move_dev, a misaligned array or counts_ld <
+ *              num_actions with counts_dev given; the forest's limits and error codes are those above.  One launch, one wave per tree. */
 typedef struct qg_mcts_forest {
     int32_t *parent;
     float *reward;
@@ -534,6 +553,9 @@ int qg_mcts_select(const qg_mcts_forest *forest, float c_puct, const uint8_t *fi
 int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int32_t *src_dev, const int32_t *dst_dev, const int32_t *act_dev,
                    const int32_t *leaf_dev, const float *logp_dev, uint64_t ld, const float *values_dev, const float *reward_dev,
                    const uint8_t *done_dev, void *stream);
+typedef enum { QG_MCTS_MOST_VISITED = 0, QG_MCTS_SAMPLE = 1 } qg_mcts_decide_mode;
+int qg_mcts_decide(const qg_mcts_forest *forest, int mode, uint64_t seed, uint64_t counter, const uint8_t *finished_dev,
+                   int32_t *move_dev, int32_t *counts_dev, uint64_t counts_ld, void *stream);
 /* Twists, batched: the symmetries of the coupling map as views of the observation (Env::twists, clifford.rs:370-372; symmetry.rs:205-295).
  * For CliffordEnv, LinearFunctionEnv and PermutationEnv twist t is a pair: obs_perms[t] over the flat dense observation (rows * cols entries)
  * and act_perms[t] over the actions.  THE DEFINITION, proved on the oracle env for every kind, twist and action (tests/test_twist_views.py):

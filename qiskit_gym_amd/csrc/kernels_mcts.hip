@@ -1,10 +1,15 @@
 // kernels_mcts.hip -- the tree of a PUCT search (MCTS) over a policy's priors and values: qg_mcts_select (one descent per tree: which node to
-// expand, by which action) and qg_mcts_backup (link the new node, carry its value to the root; in mode QG_MCTS_ROOT: start a tree).  The rules
-// are stated in include/qgym.h; tests/mctsmodel.py restates them in numpy and the kernels agree with it bit for bit.
+// expand, by which action), qg_mcts_backup (link the new node, carry its value to the root; in mode QG_MCTS_ROOT: start a tree) and
+// qg_mcts_decide (the root's visit counts and the move they give: the most visited action, or one drawn in proportion to the counts).  The rules
+// are stated in include/qgym.h; tests/mctsmodel.py and tests/mctssample_model.py restate them in numpy and the kernels agree with them bit for bit.
 //
 // The forest is a struct of plain arrays (qg_mcts_forest): per (tree, node) parent, reward, value, visits, wsum, terminal; per (tree, node,
 // action) child and prior; per tree n_nodes.  One WAVE per tree in both kernels, several trees per workgroup; a wave owns its tree for the
 // whole launch: plain vector loads and stores, no atomics, no barrier between waves.
+//
+// qg_mcts_decide.  The same lanes over the root's actions.  The draw needs the sums n_0 + ... + n_a in ACTION order: the slices k are consecutive
+// blocks of 64 actions, so that is an inclusive scan over the lanes per slice (six __shfl_up steps) plus the totals of the slices before it, all
+// in integers -- the result does not depend on the launch geometry.  No LDS: a root has few children, each count is one load behind the child row.
 //
 // qg_mcts_select.  The lanes cover the actions of the node the descent stands on (action lane + 64 k, k < 4).  A level's score needs the
 // node's child and prior rows and, per expanded edge, the child's visits and wsum: the second would be a dependent memory trip behind the
@@ -226,6 +231,122 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_kernel(const Back
     if (y == 0) f.visits[base] += 1;
 }
 
+struct DecideArgs {
+    qg_mcts_forest f;
+    const uint8_t *finished;  // or nullptr
+    int32_t *move;
+    int32_t *counts;  // or nullptr
+    uint64_t counts_ld, seed, counter;
+    int32_t mode;
+};
+
+__device__ inline uint64_t mcts_shfl64(uint64_t v, int src) {
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64), lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// inclusive prefix sum over the 64 lanes, in lane order: six shifted additions
+__device__ inline uint64_t mcts_wave_scan(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), off, 64), lo = (uint32_t)__shfl_up((int)(uint32_t)v, off, 64);
+        if (lane >= (uint32_t)off) v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
+// The decision after a decision's simulations: the root's visit counts, and the move they give -- the most visited action, or one drawn in
+// proportion to the counts.  The lanes cover the root's actions as in the selection; the counts are one dependent trip behind the child row
+// (the root's children are few, so no LDS copy of the tree pays here).  Nothing is written into the forest.
+__global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_decide_kernel(const DecideArgs a) {
+    const qg_mcts_forest &f = a.f;
+    const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
+    const uint64_t m = (uint64_t)blockIdx.x * MCTS_WAVES + wave;
+    if (m >= f.n_trees) return;  // (the whole wave)
+    const uint32_t cap = f.cap, A = f.num_actions;
+    const uint64_t base = m * cap;
+    const bool fin = a.finished && a.finished[m] != 0;
+    if (fin && !a.counts) {  // no gate, and nobody asks for the row
+        if (lane == 0) a.move[m] = (int32_t)A;
+        return;
+    }
+
+    const uint32_t n = (uint32_t)f.n_nodes[m];
+    bool bad = n < 1 || n > cap;
+    int32_t c[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t ac = lane + QG_WAVE * k;
+        c[k] = (!bad && ac < A) ? f.child[base * A + ac] : -1;
+    }
+    uint32_t na[4];   // n_a
+    bool grown[4];    // the edge has a child
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        na[k] = 0;
+        grown[k] = c[k] >= 0;
+        if (!grown[k]) continue;
+        if (c[k] == 0 || (uint32_t)c[k] >= n) {  // no child of this tree's root
+            bad = true;
+            continue;
+        }
+        const int32_t v = f.visits[base + (uint32_t)c[k]];
+        if (v < 0) bad = true;
+        else na[k] = (uint32_t)v;
+    }
+    if (__ballot(bad)) {  // the tree's work ends here: no move, a row of zeros
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            na[k] = 0;
+            grown[k] = false;
+        }
+    }
+    if (a.counts) {
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t ac = lane + QG_WAVE * k;
+            if (ac < A) a.counts[m * a.counts_ld + ac] = (int32_t)na[k];
+        }
+    }
+    if (fin) {
+        if (lane == 0) a.move[m] = (int32_t)A;
+        return;
+    }
+
+    uint32_t move = A;
+    uint64_t total = 0;
+    if (a.mode == QG_MCTS_SAMPLE) {
+        uint64_t incl[4];  // the sums up to and including the lane's action, in action order: slice k holds actions 64 k .. 64 k + 63
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            incl[k] = total;
+            if (QG_WAVE * k >= A) continue;  // (the whole wave)
+            incl[k] += mcts_wave_scan((uint64_t)na[k], lane);
+            total = mcts_shfl64(incl[k], QG_WAVE - 1);
+        }
+        if (total != 0) {
+            const uint64_t r = __umul64hi(rng_draw(a.seed ^ 0x6D637473ull, m, a.counter), total);  // r < total
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                // the lowest action whose sum exceeds r: the one action with incl - n_a <= r < incl
+                const uint64_t hit = __ballot(incl[k] > r && incl[k] - na[k] <= r);
+                if (hit) move = QG_WAVE * k + (uint32_t)__builtin_ctzll(hit);
+            }
+        }
+    }
+    if (total == 0) {  // the most visited of the expanded edges, the lowest action among equals
+        uint64_t key = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint64_t kk = ((uint64_t)na[k] << 32) | (uint64_t)(0xFFFFFFFFu - (lane + QG_WAVE * k));
+            if (grown[k] && kk > key) key = kk;
+        }
+        const uint64_t top = mcts_wave_max(key);
+        if (top != 0) move = 0xFFFFFFFFu - (uint32_t)top;
+    }
+    if (lane == 0) a.move[m] = (int32_t)move;
+}
+
 static int mcts_check_forest(const qg_mcts_forest *f, const char *who) {
     if (!f) return set_error(QG_ERR_INVALID, "null argument");
     if (!f->parent || !f->reward || !f->value || !f->visits || !f->wsum || !f->terminal || !f->child || !f->prior || !f->n_nodes)
@@ -297,6 +418,29 @@ extern "C" int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int3
     a.mode = mode;
     const dim3 grid((unsigned)((forest->n_trees + MCTS_WAVES - 1) / MCTS_WAVES)), block(64u * MCTS_WAVES);
     hipLaunchKernelGGL(mcts_backup_kernel, grid, block, 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}
+
+extern "C" int qg_mcts_decide(const qg_mcts_forest *forest, int mode, uint64_t seed, uint64_t counter, const uint8_t *finished_dev, int32_t *move_dev,
+                              int32_t *counts_dev, uint64_t counts_ld, void *stream) {
+    if (const int rc = mcts_check_forest(forest, "mcts_decide")) return rc;
+    if (mode != QG_MCTS_MOST_VISITED && mode != QG_MCTS_SAMPLE) return set_error(QG_ERR_INVALID, "mode must be 0 (most visited) or 1 (sample)");
+    if (!move_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (((uintptr_t)move_dev % 4) || ((uintptr_t)counts_dev % 4)) return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (counts_dev && counts_ld < forest->num_actions) return set_error(QG_ERR_INVALID, "bad shape: counts_ld >= num_actions");
+    if (forest->n_trees == 0) return QG_OK;
+    DecideArgs a;
+    a.f = *forest;
+    a.finished = finished_dev;
+    a.move = move_dev;
+    a.counts = counts_dev;
+    a.counts_ld = counts_ld;
+    a.seed = seed;
+    a.counter = counter;
+    a.mode = mode;
+    const dim3 grid((unsigned)((forest->n_trees + MCTS_WAVES - 1) / MCTS_WAVES)), block(64u * MCTS_WAVES);
+    hipLaunchKernelGGL(mcts_decide_kernel, grid, block, 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return QG_OK;
 }

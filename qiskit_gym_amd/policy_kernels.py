@@ -253,6 +253,34 @@ def mcts_backup(forest: MctsForest, logp: torch.Tensor, values: torch.Tensor, re
     return forest
 
 
+def mcts_decide(forest: MctsForest, sample: bool = False, seed: int = 0, counter: int = 0, finished: Optional[torch.Tensor] = None,
+                move: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decision after a decision's simulations (`qg_mcts_decide`), one launch; the forest is only read.  Per tree the visit counts of
+    the root's actions, n_a = visits of the child under action a, 0 where there is none, and the move they give: sample=False the action of
+    the most visits among the expanded ones, the lowest among equals; sample=True the lowest a with n_0 + ... + n_a > r, where
+    r = mulhi64(rng_draw(seed ^ 0x6D637473, tree, counter), sum of the counts) -- an action is drawn in proportion to its visits, in
+    integers, the same for the same (seed, counter, tree); without any visit the answer of sample=False.  A where the root has no child.
+    finished: optional uint8 / bool [M], trees whose real env is final: their move is A.  counts: optional int32 [M, >= A] with unit
+    column stride, gets the rows of n_a (finished trees too; columns past A are left alone).  Returns move, int32 [M]; a preallocated one
+    may be passed."""
+    if not isinstance(forest, MctsForest):
+        raise TypeError("mcts_decide: forest must come from mcts_forest")
+    M, A, dev, i32 = forest.M, forest.A, forest.parent.device, torch.int32
+    if finished is not None and finished.dtype == torch.bool:
+        finished = finished.view(torch.uint8)
+    if move is None:
+        move = torch.empty(M, dtype=i32, device=dev)
+    _mcts_vectors("mcts_decide", forest, (("finished", finished, torch.uint8), ("move", move, i32)))
+    if counts is not None and (counts.dtype != i32 or counts.dim() != 2 or counts.shape[0] != M or counts.shape[1] < A or counts.device != dev or (
+            counts.stride(1) != 1 and counts.shape[1] > 1) or (M > 1 and counts.stride(0) < A)):
+        raise ValueError("mcts_decide: counts must be int32 [M, >= A] with unit column stride on the forest's device")
+    ld = 0 if counts is None else counts.stride(0) if M > 1 else counts.shape[1]
+    _lib.check(_lib.load().qg_mcts_decide(forest._c, _lib.MCTS_SAMPLE if sample else _lib.MCTS_MOST_VISITED, int(seed) & (2 ** 64 - 1), int(counter) & (2 ** 64 - 1),
+                                          finished.data_ptr() if finished is not None else None, move.data_ptr(),
+                                          counts.data_ptr() if counts is not None else None, ld, _stream_ptr()))
+    return move
+
+
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,
         gae_lambda: float, advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None):
     """GAE(lambda) over a [T, B] rollout; `dones[t]` = the episode ended with step t.  Returns (advantages, returns)."""

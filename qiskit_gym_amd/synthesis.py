@@ -20,7 +20,9 @@ target's search once no beam of it can beat its winner (`collector.beam_advance`
 
 `solve(..., deterministic=True, num_mcts_searches=N)` is the reference's third way to search: a PUCT tree search per target, N simulations
 per decision, the trees in plain device arrays (`collector.mcts_forest`), selection and backup on two kernels (`collector.mcts_select`,
-`collector.mcts_backup`), the expansion on the batched clone and one forward pass for all targets; see `solve`.
+`collector.mcts_backup`), the expansion on the batched clone and one forward pass for all targets; see `solve`.  `mcts_sampled=True` is the
+reference's default shape of that call: `num_searches` tree-search episodes per target, every move drawn from the root's visit counts on the
+device (`collector.mcts_decide`), the best successful episode kept.
 
 `solve(..., fast=True)` takes the policy off the tensor library: the first layer reads the bit-packed state (`collector.embed` /
 `embed_words`), the rest is one kernel that either draws (`mid_head_sample`: the sampled searches) or, for the greedy and the beam search,
@@ -50,7 +52,7 @@ import torch
 from . import _lib
 from .envs.gyms import ROTATION_MARKER
 from .policy_kernels import (MCTS_MAX_FOREST_BYTES, BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
-                             mcts_backup, mcts_forest, mcts_select, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
+                             mcts_backup, mcts_decide, mcts_forest, mcts_select, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
 from .vec import VecEnv
 
 
@@ -218,7 +220,7 @@ class BatchedSynthesis:
         PauliGym search, replayed with the solution log on) or "beam" (the two batches of targets * width envs that take turns as source and
         destination of the per-step copy, and the winners, all three with the same constructor arguments: the rule of `copy_envs`; no layout
         choice depends on the batch size) or "mcts" (the pool of targets * (N + 1) node envs, the leaf batch and the real batch of one env per
-        target, again all with the same constructor arguments).  One batch shape at a time per kind: the handles own device memory."""
+        target, again all with the same constructor arguments) or "mcts-sampled" (the same three for targets * searches trees).  One batch shape at a time per kind: the handles own device memory."""
         key = (*batches, perms)  # add_perms: twists() only, the env steps alike
         held = self._held.get(kind)
         if held is not None and held.key != key:
@@ -386,16 +388,23 @@ class BatchedSynthesis:
             self.last_stats.update(bound=bound, bounded=int(bounded.sum()))
         return out
 
-    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool):
+    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool, searches: Optional[int] = None):
         """The search of `solve(num_mcts_searches=N)` on the handles of `held`: the leaf batch, which is all the forward object reads, the pool
-        (node j of target m is env m * (N + 1) + j) and the real envs.  Per decision one forward pass on the roots and N simulations of `mcts_select`,
-        clone + step, one forward pass, clone back, `mcts_backup`; the rules are stated in include/qgym.h and tests/mctsmodel.py."""
+        (node j of tree m is env m * (N + 1) + j) and the real envs.  Per decision one forward pass on the roots and N simulations of `mcts_select`,
+        clone + step, one forward pass, clone back, `mcts_backup`; the rules are stated in include/qgym.h and tests/mctsmodel.py.
+        `searches` None: one tree per target, the move is the root's most visited action.  `searches` = S (`mcts_sampled`): S trees per
+        target, tree and real env m * S + s is search s of target m; the move is drawn from the root's visit counts (`mcts_decide`, counter
+        t) and a target's answer is that of its successful search of the greatest return (tests/mctssample_model.py)."""
         leaf, pool, real = held.vecs
-        M, A, dev = real.batch, real.num_actions(), real.device
+        S = 1 if searches is None else searches
+        M, A, dev = real.batch, real.num_actions(), real.device  # M: trees, `S` per target
         T, cap = int(real._cfg.max_depth), N + 1
         forest = mcts_forest(M, N, A, dev)
         fwd = self._forward(held, 1, None, kernels, rows=True)
-        self._load(real, states, 1)
+        self._load(real, states, S)
+        if searches is not None:
+            ret = torch.zeros(M, dtype=torch.float32, device=dev)
+            drawn = torch.empty(M, dtype=torch.int32, device=dev)
         ids = torch.arange(M, dtype=torch.int32, device=dev)
         roots = ids * cap
         finished = real.success.bool().to(torch.uint8)  # a target that is already solved needs no gates
@@ -416,34 +425,49 @@ class BatchedSynthesis:
                 rows, values = fwd.logp_values(leaf)
                 pool.copy_envs(leaf, ids, dst)
                 mcts_backup(forest, rows, values, leaf.reward, leaf.done, src, dst, act, lf)
-            # the decision: the root's expanded action of the most visits, the lowest among equals; A where the root has no child
-            child = forest.child[:, 0, :].to(torch.int64)
-            visits = torch.gather(forest.visits.to(torch.int64), 1, child.clamp(min=0))
-            best = torch.where(child >= 0, visits * A + keys, -1).max(dim=1).values  # a key per (visits, action): no two alike
-            move = torch.where((best >= 0) & (finished == 0), A - 1 - best % A, parked).to(torch.int32)
+            if searches is None:
+                # the decision: the root's expanded action of the most visits, the lowest among equals; A where the root has no child
+                child = forest.child[:, 0, :].to(torch.int64)
+                visits = torch.gather(forest.visits.to(torch.int64), 1, child.clamp(min=0))
+                best = torch.where(child >= 0, visits * A + keys, -1).max(dim=1).values  # a key per (visits, action): no two alike
+                move = torch.where((best >= 0) & (finished == 0), A - 1 - best % A, parked).to(torch.int32)
+            else:  # drawn in proportion to the visits; A for a finished tree
+                move = mcts_decide(forest, sample=True, seed=self.seed, counter=t, finished=finished, move=drawn)
             live = finished == 0
             nodes += (forest.n_nodes * live).sum()
             decisions += live.sum()
             real.step(move)
+            if searches is not None:
+                ret += torch.where(live, real.reward, torch.zeros_like(ret))
             finished |= real.done.bool().to(torch.uint8)
             steps = t + 1
             if t % 8 == 7 and bool(finished.all()):
                 break
         real.sync()
         sols, lens = real.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
-        ok = real.success.bool().cpu().numpy()
+        ok = real.success.bool()
+        stats = {"mcts": N}
+        if searches is None:
+            mine = range(M)
+            ok = ok.cpu().numpy()
+        else:  # per target the successful search of the greatest return, the lowest s among equals; its env's own log is the answer
+            won = ok.view(-1, S)
+            mine = (torch.arange(M // S, device=dev) * S + _winner(won, ret.view(-1, S))[1]).tolist()
+            stats.update(searches=S, searches_solved=int(won.sum()) / M)
+            ok = won.any(dim=1).cpu().numpy()
         # a finished env was handed A from then on, which the log of some env kinds records: such entries are no gates and no markers
-        out = [[int(x) for x in sols[m, : lens[m]] if x < A or x >= ROTATION_MARKER] if ok[m] else None for m in range(M)]
+        out = [[int(x) for x in sols[e, : lens[e]] if x < A or x >= ROTATION_MARKER] if ok[m] else None for m, e in enumerate(mine)]
         gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
-        self.last_stats = {"mcts": N, "targets": M, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0,
-                           "nodes": float(nodes) / max(int(decisions), 1), "kernels": fwd.kernels}
+        stats.update({"targets": M // S, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0,
+                      "nodes": float(nodes) / max(int(decisions), 1), "kernels": fwd.kernels})
+        self.last_stats = stats
         return out
 
     @torch.no_grad()
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
               beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None,
               twist_kernels: bool = False, bound: Optional[str] = None, num_mcts_searches: int = 0, C: float = 2 ** 0.5,
-              max_expand_depth: int = 1) -> List[Optional[List[int]]]:
+              max_expand_depth: int = 1, mcts_sampled: bool = False) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         The rules of the sampled and the greedy search -- env m * S + s is search s of target m, the draw of step t is the race of
         `sample_actions(logits, seed, t)`, a finished env gets no gate and adds no reward, the loop ends at the first step t with
@@ -527,15 +551,34 @@ class BatchedSynthesis:
         the policy-layer kernels (`mid_head_logp`: rows and values), None / False on the torch forward.  `last_stats`: "mcts" (N),
         "targets", "steps" (decisions), "solved", "mean_gates", "nodes" (mean nodes per tree and decision) and "kernels".  ValueError:
         N < 0; C <= 0; max_expand_depth != 1 (not built: what twisterl means by it cannot be read from the reference);
-        deterministic=False (sampling a move from the visit counts is not built); together with beam_width, merge_duplicates, bound,
+        deterministic=False (unless `mcts_sampled`, below); together with beam_width, merge_duplicates, bound,
         twists or twist_kernels; a forest -- targets * (N + 1) * (21 + 8 * num_actions) bytes -- of more than 1 GiB
         (`policy_kernels.MCTS_MAX_FOREST_BYTES`; the pool of targets * (N + 1) envs comes on top); N + 1 > 8 192 or more than 256
-        actions is the library's QGymError."""
+        actions is the library's QGymError.
+
+        mcts_sampled=True, with num_mcts_searches=N >= 1 and deterministic=False (default False: every code path, handle key and `last_stats`
+        as without the argument, the ValueError for a tree search with deterministic=False included -- which is why this mode is opted
+        into by a keyword of its own): the reference's default shape of the call, S = max(1, num_searches) independent tree-search
+        episodes per target.  Tree and real env m * S + s is search s of target m, the layout of the sampled search; the root and the N
+        simulations of a decision are those of the tree search above, on targets * S trees in the same launches.  After them the move of
+        decision t is drawn from the root's visit counts on the device (`collector.mcts_decide`): r = mulhi64(rng_draw(seed ^ 0x6D637473,
+        tree, t), sum of the counts), the lowest action whose running sum of counts exceeds r -- integers, so the same seed gives the same
+        episodes.  A search's return is the f32 sum, in step order, of the rewards of the steps it was live for; a target's answer is the
+        solution log of its successful search of the greatest return, the lowest s among equals (None without one; PauliGym: rotation
+        markers included, no replay).  The rules are restated in tests/mctssample_model.py.  `last_stats`: "mcts", "searches" (S),
+        "targets", "steps", "solved", "searches_solved" (successful searches / all), "mean_gates", "nodes", "kernels".  The handles are
+        of a kind of their own ("mcts-sampled").  ValueError: without num_mcts_searches >= 1; with deterministic=True; with beam_width,
+        merge_duplicates, bound, twists or twist_kernels; and the tree search's own, the forest limit now on targets * S trees."""
         M = len(states)
+        S = max(1, int(num_searches)) if mcts_sampled else 1
         self._check_options(M == 0, fast, beam_width, merge_duplicates, twists, twist_kernels, bound)
-        N = self._check_mcts(M, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth)
+        N = self._check_mcts(M * S, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
+                             mcts_sampled)
         if M == 0:
             return []
+        if N and mcts_sampled:
+            B = M * S
+            return self._mcts_search(states, self._handles("mcts-sampled", (B, B * (N + 1), B)), N, float(C), fast is True, S)
         if N:
             return self._mcts_search(states, self._handles("mcts", (M, M * (N + 1), M)), N, float(C), fast is True)  # kernels: on request only
         views = None if twists is None else self._views(int(twists))
@@ -576,27 +619,32 @@ class BatchedSynthesis:
                 raise ValueError("bound: a PauliGym step adds pauli_layer_reward per released rotation (pauli.rs:634), and a target may hold rotations "
                                  "beyond the observed columns: the reward still to come has no bound the search can see")
 
-    def _check_mcts(self, targets: int, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth) -> int:
-        """`num_mcts_searches` as an int, after the ValueErrors of `solve`'s tree search; 0: no tree search, and `C` and `max_expand_depth`
-        mean nothing."""
+    def _check_mcts(self, trees: int, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
+                    mcts_sampled) -> int:
+        """`num_mcts_searches` as an int, after the ValueErrors of `solve`'s tree search on `trees` trees; 0: no tree search, and `C` and
+        `max_expand_depth` mean nothing."""
         N = int(num_mcts_searches)
         if N < 0:
             raise ValueError("num_mcts_searches must be at least 0")
+        if mcts_sampled and N == 0:
+            raise ValueError("mcts_sampled=True needs num_mcts_searches >= 1: it draws the moves of a tree search")
         if N == 0:
             return 0
         if not float(C) > 0.0:
             raise ValueError("C must be positive")
         if int(max_expand_depth) != 1:
             raise ValueError("max_expand_depth: only 1 is built (one new node per simulation)")
-        if not deterministic:
-            raise ValueError("num_mcts_searches needs deterministic=True: sampling a move from the visit counts is not built")
+        if mcts_sampled and deterministic:
+            raise ValueError("mcts_sampled=True draws its moves: it cannot be combined with deterministic=True")
+        if not mcts_sampled and not deterministic:
+            raise ValueError("num_mcts_searches needs deterministic=True, or mcts_sampled=True to draw the moves from the visit counts")
         mixed = [name for name, on in (("beam_width", beam_width is not None), ("merge_duplicates", merge_duplicates), ("bound", bound is not None),
                                        ("twists", twists is not None), ("twist_kernels", twist_kernels)) if on]
         if mixed:
             raise ValueError(f"num_mcts_searches cannot be combined with {', '.join(mixed)}")
-        nbytes = int(_lib.load().qg_mcts_forest_bytes(targets, min(N + 1, 2 ** 32 - 1), len(self.env.config["gateset"])))
+        nbytes = int(_lib.load().qg_mcts_forest_bytes(trees, min(N + 1, 2 ** 32 - 1), len(self.env.config["gateset"])))
         if nbytes > MCTS_MAX_FOREST_BYTES:
-            raise ValueError(f"num_mcts_searches={N}: the forest of {targets} targets takes {nbytes} bytes, more than the limit of {MCTS_MAX_FOREST_BYTES}")
+            raise ValueError(f"num_mcts_searches={N}: the forest of {trees} trees takes {nbytes} bytes, more than the limit of {MCTS_MAX_FOREST_BYTES}")
         return N
 
     def _sampled_search(self, states, deterministic: bool, num_searches: int, fast: Optional[bool], views: Optional[List[int]], twist_kernels: bool):
@@ -665,11 +713,11 @@ class BatchedSynthesis:
 
     def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
               twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False, bound: Optional[str] = None,
-              num_mcts_searches: int = 0, C: float = 2 ** 0.5, max_expand_depth: int = 1):
+              num_mcts_searches: int = 0, C: float = 2 ** 0.5, max_expand_depth: int = 1, mcts_sampled: bool = False):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
         sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, fast=fast, beam_width=beam_width,
                           merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels, bound=bound,
-                          num_mcts_searches=num_mcts_searches, C=C, max_expand_depth=max_expand_depth)
+                          num_mcts_searches=num_mcts_searches, C=C, max_expand_depth=max_expand_depth, mcts_sampled=mcts_sampled)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):
