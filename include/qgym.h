@@ -35,7 +35,7 @@ extern "C" {
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
  *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance, qg_mcts_forest_bytes,
- *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide (additions only) */
+ *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide, qg_mcts_rebase (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -474,14 +474,14 @@ int qg_beam_advance(uint64_t n_groups, uint32_t width, const int32_t *parent_dev
                     const uint8_t *success_dev, const uint8_t *done_dev, uint8_t *live_dev, float *best_dev, uint8_t *found_dev,
                     float *ret_out_dev, int32_t *win_src_dev, uint8_t *group_live_dev, int32_t *bounded_dev, int32_t skip, float bonus, int mode,
                     void *stream);
-/* The tree of a PUCT search (MCTS): one tree per target, rebuilt for every decision, in plain arrays the caller owns -- the kernels know no
+/* The tree of a PUCT search (MCTS): one tree per target, rebuilt for every decision unless the caller rebases it (qg_mcts_rebase), in plain arrays the caller owns -- the kernels know no
  * env and no policy.  A forest of n_trees trees of at most cap nodes over num_actions actions is a struct of device arrays:
  *   per (tree m, node j), index m*cap + j:  parent i32 (-1 for node 0) | reward f32, the reward of the step into the node | value f32, the
  *       value head at the node, 0 for a terminal node | visits i32 | wsum f32 | terminal u8, the env's `done`
  *   per (tree, node, action), index (m*cap + j)*num_actions + a:  child i32 (-1 = not expanded) | prior f32
  *   per tree:  n_nodes i32
  * Node 0 is the root.  A node's env is expected in a pool of n_trees*cap envs at index m*cap + j ("pool index"); for a search of N
- * simulations per decision cap = N + 1.  qg_mcts_forest_bytes is what the arrays take together.
+ * simulations per decision cap = N + 1, more where trees are carried from decision to decision.  qg_mcts_forest_bytes is what the arrays take together.
  * The rules (tests/mctsmodel.py restates them in numpy; results agree bit for bit):
  *   root       qg_mcts_backup in mode QG_MCTS_ROOT, per tree from logp_dev[m*ld + a] and values_dev[m]: prior[0][a] = expf(logp), child[0][a]
  *              = -1, terminal[0] = done_dev[m] != 0 (0 where done_dev is NULL), value[0] = values[m] (0 if terminal), visits[0] = 1,
@@ -532,7 +532,33 @@ int qg_beam_advance(uint64_t n_groups, uint32_t width, const int32_t *parent_dev
  *     counts_dev     optional i32[n_trees][counts_ld], counts_ld >= num_actions: the row of n_a (the training target of an AlphaZero-style
  *              learner), written for finished trees too; columns past num_actions are not written.
  *              move_dev i32[n_trees].  QG_ERR_INVALID for an unknown mode, a null move_dev, a misaligned array or counts_ld <
- *              num_actions with counts_dev given; the forest's limits and error codes are those above.  One launch, one wave per tree. */
+ *              num_actions with counts_dev given; the forest's limits and error codes are those above.  One launch, one wave per tree.
+ *   rebase     qg_mcts_rebase, between two decisions: the subtree below the chosen move becomes the tree, in place, so the next decision
+ *              starts from the simulations already spent there (an env's step must be deterministic for that to be valid search work).
+ *              tests/mctsreuse_model.py restates it in numpy; results agree bit for bit.  move_dev i32[n_trees] (qg_mcts_decide's);
+ *              finished_dev optional u8[n_trees]; env_src_dev i32[n_trees*cap], written in full: the src_idx of the qg_vec_copy_envs call
+ *              that moves the node envs into a second pool (new pool index <- old pool index; none = n_trees*cap, which that call skips).
+ *              Per tree m, with n = n_nodes[m], a = move_dev[m]:
+ *     finished     finished_dev[m] != 0: the forest is untouched, env_src[m*cap + j] = none for every j < cap.
+ *     nothing to carry   n outside [1, cap], a outside [0, num_actions) or c = child[0][a] outside (0, n): the forest is untouched,
+ *              env_src[m*cap + j] = m*cap + j for j < n (for j < cap where n > cap, for no j where n < 1), none for every other j.
+ *     kept     Otherwise node c is kept, and a node j, c < j < n, iff the chain j -> parent[j] -> ... reaches c exactly, every link
+ *              strictly below the one before it and >= 0; a chain that breaks, or passes below c, keeps nothing.  No node <= c but c.
+ *     renumbering   The new index j' of a kept node is the number of kept nodes below j: the order stays, c becomes 0.
+ *     fields   reward, value, visits, wsum, terminal and the prior row move unchanged to j'; parent[j'] is the new index of the old
+ *              parent; a child entry c2 becomes its new index where 0 <= c2 < n and c2 is kept, else -1.  The new root gets parent = -1,
+ *              reward = 0, wsum = 0 and keeps everything else -- its visits are, by the backup rule, 1 + the simulations below it: a
+ *              root's count.
+ *     sizes    n_nodes[m] = the number of kept nodes; env_src[m*cap + j'] = m*cap + j for every kept node, none for j' >= n_nodes.
+ *              Array entries at node indices >= the new n_nodes mean nothing.
+ *              The rules are total: any forest content gives a defined result, every index read from the forest is range-checked before
+ *              it is used and every loop is bounded by cap.  The parents and the table of new indices live in LDS (8 bytes per node, the
+ *              launch sizing of qg_mcts_select); the renumbering is a ballot and a popcount per slice of 64 nodes; nodes move in
+ *              ascending order, every load of a trip before its first store, which is what makes the compaction safe in place (j' <= j).
+ *              A full tree has a defined meaning in qg_mcts_select: the simulation that wants to expand gets leaf = -1 and does not
+ *              count.  Limits and error codes are those of qg_mcts_select; a null or misaligned move_dev or env_src_dev is
+ *              QG_ERR_INVALID.  One launch, one wave per tree, plain vector loads and stores, no host reads, no synchronisation,
+ *              capturable. */
 typedef struct qg_mcts_forest {
     int32_t *parent;
     float *reward;
@@ -556,6 +582,7 @@ int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int32_t *src_de
 typedef enum { QG_MCTS_MOST_VISITED = 0, QG_MCTS_SAMPLE = 1 } qg_mcts_decide_mode;
 int qg_mcts_decide(const qg_mcts_forest *forest, int mode, uint64_t seed, uint64_t counter, const uint8_t *finished_dev,
                    int32_t *move_dev, int32_t *counts_dev, uint64_t counts_ld, void *stream);
+int qg_mcts_rebase(const qg_mcts_forest *forest, const int32_t *move_dev, const uint8_t *finished_dev, int32_t *env_src_dev, void *stream);
 /* Twists, batched: the symmetries of the coupling map as views of the observation (Env::twists, clifford.rs:370-372; symmetry.rs:205-295).
  * For CliffordEnv, LinearFunctionEnv and PermutationEnv twist t is a pair: obs_perms[t] over the flat dense observation (rows * cols entries)
  * and act_perms[t] over the actions.  THE DEFINITION, proved on the oracle env for every kind, twist and action (tests/test_twist_views.py):

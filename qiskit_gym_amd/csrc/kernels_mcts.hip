@@ -1,10 +1,11 @@
 // kernels_mcts.hip -- the tree of a PUCT search (MCTS) over a policy's priors and values: qg_mcts_select (one descent per tree: which node to
 // expand, by which action), qg_mcts_backup (link the new node, carry its value to the root; in mode QG_MCTS_ROOT: start a tree) and
-// qg_mcts_decide (the root's visit counts and the move they give: the most visited action, or one drawn in proportion to the counts).  The rules
-// are stated in include/qgym.h; tests/mctsmodel.py and tests/mctssample_model.py restate them in numpy and the kernels agree with them bit for bit.
+// qg_mcts_decide (the root's visit counts and the move they give: the most visited action, or one drawn in proportion to the counts) and
+// qg_mcts_rebase (between two decisions: the chosen move's subtree becomes the tree, in place).  The rules are stated in include/qgym.h;
+// tests/mctsmodel.py, tests/mctssample_model.py and tests/mctsreuse_model.py restate them in numpy and the kernels agree with them bit for bit.
 //
 // The forest is a struct of plain arrays (qg_mcts_forest): per (tree, node) parent, reward, value, visits, wsum, terminal; per (tree, node,
-// action) child and prior; per tree n_nodes.  One WAVE per tree in both kernels, several trees per workgroup; a wave owns its tree for the
+// action) child and prior; per tree n_nodes.  One WAVE per tree in every kernel, several trees per workgroup; a wave owns its tree for the
 // whole launch: plain vector loads and stores, no atomics, no barrier between waves.
 //
 // qg_mcts_decide.  The same lanes over the root's actions.  The draw needs the sums n_0 + ... + n_a in ACTION order: the slices k are consecutive
@@ -347,6 +348,140 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_decide_kernel(const Deci
     if (lane == 0) a.move[m] = (int32_t)move;
 }
 
+struct RebaseArgs {
+    qg_mcts_forest f;
+    const int32_t *move;
+    const uint8_t *finished;  // or nullptr
+    int32_t *env_src;
+    uint32_t waves;
+};
+
+// The step between two decisions: the chosen move's subtree becomes the tree, in place.  Four passes per tree, all on its one wave:
+//   1  the tree's parents into LDS (one trip);
+//   2  per slice of 64 nodes, ascending: is the lane's node below c?  It walks its parents in LDS until it leaves the slice -- there the
+//      answer is already in the table -- so at most 64 steps of a strictly falling index; the new index is the kept nodes so far plus the
+//      kept lanes below this one (a ballot and a popcount);
+//   3  the per-node fields, one node per lane, a slice per trip, and the LDS copy of the parents gives way to the list of the kept nodes;
+//   4  the child and prior rows, ROWS kept nodes per trip (16 rows of up to 64 actions ... 4 rows of up to 256), the child entries renumbered
+//      through the table.
+// In place: a kept node's new index is below its old one and the order is kept, so with ascending nodes, and every load of a trip issued
+// before its first store, a store never lands on a node still to be read.
+template <uint32_t K>  // slices of 64 actions
+__global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_rebase_kernel(const RebaseArgs a) {
+    constexpr uint32_t ROWS = 16 / K;
+    extern __shared__ int32_t mcts_rebase_lds[];  // [waves][2][cap]: parent, later the kept nodes in order | new index, -1: not kept
+    const qg_mcts_forest &f = a.f;
+    const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
+    const uint64_t m = (uint64_t)blockIdx.x * a.waves + wave;
+    if (m >= f.n_trees) return;  // (the whole wave)
+    const uint32_t cap = f.cap, A = f.num_actions;
+    const uint64_t base = m * cap;
+    const int32_t none = (int32_t)(f.n_trees * cap);
+    int32_t *par = mcts_rebase_lds + (size_t)wave * 2 * cap, *idx = par + cap;
+    int32_t *es = a.env_src + base;
+
+    if (a.finished && a.finished[m] != 0) {  // the tree is left alone and copies nothing
+        for (uint32_t j = lane; j < cap; j += QG_WAVE) es[j] = none;
+        return;
+    }
+    const int32_t n_raw = f.n_nodes[m], mv = a.move[m];
+    int32_t c = -1;
+    if (n_raw >= 1 && (uint32_t)n_raw <= cap && mv >= 0 && (uint32_t)mv < A) c = f.child[base * A + (uint32_t)mv];
+    if (!(c > 0 && c < n_raw)) {  // nothing to carry: every node keeps its env
+        const uint32_t lim = n_raw < 1 ? 0u : (uint32_t)n_raw > cap ? cap : (uint32_t)n_raw;
+        for (uint32_t j = lane; j < cap; j += QG_WAVE) es[j] = j < lim ? (int32_t)(base + j) : none;
+        return;
+    }
+    const uint32_t n = (uint32_t)n_raw;
+
+    for (uint32_t j = lane; j < n; j += QG_WAVE) par[j] = f.parent[base + j];
+    __builtin_amdgcn_wave_barrier();  // the wave reads what its other lanes wrote: LDS keeps a wave's accesses in order
+
+    uint32_t kept = 0;
+    for (uint32_t s = 0; s < n; s += QG_WAVE) {
+        const uint32_t j = s + lane;
+        bool keep = j == (uint32_t)c;
+        if (j > (uint32_t)c && j < n) {
+            uint32_t y = j;
+            for (uint32_t step = 0; step < QG_WAVE; ++step) {
+                const int32_t p = par[y];
+                if (p < c || (uint32_t)p >= y) break;  // the chain breaks, or passes below c
+                if (p == c) {
+                    keep = true;
+                    break;
+                }
+                if ((uint32_t)p < s) {  // an earlier slice: settled
+                    keep = idx[p] >= 0;
+                    break;
+                }
+                y = (uint32_t)p;
+            }
+        }
+        const uint64_t mask = __ballot(keep);
+        if (j < n) idx[j] = keep ? (int32_t)(kept + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))) : -1;
+        kept += (uint32_t)__popcll(mask);
+        __builtin_amdgcn_wave_barrier();
+    }
+
+    for (uint32_t s = 0; s < n; s += QG_WAVE) {
+        const uint32_t j = s + lane;
+        const int32_t to = j < n ? idx[j] : -1;
+        if (to >= 0) {
+            const int32_t up = par[j];  // kept: c <= up < j, or j is c
+            int32_t pa = to == 0 ? -1 : idx[up];
+            float rw = f.reward[base + j], ws = f.wsum[base + j];
+            const float va = f.value[base + j];
+            const int32_t vi = f.visits[base + j];
+            const uint8_t te = f.terminal[base + j];
+            if (to == 0) rw = ws = 0.0f;  // the new root
+            f.parent[base + to] = pa;
+            f.reward[base + to] = rw;
+            f.value[base + to] = va;
+            f.visits[base + to] = vi;
+            f.wsum[base + to] = ws;
+            f.terminal[base + to] = te;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (to >= 0) par[to] = (int32_t)j;  // to <= j, and nobody reads a parent at or below this slice again
+    }
+    __builtin_amdgcn_wave_barrier();
+
+    for (uint32_t j0 = 0; j0 < kept; j0 += ROWS) {
+        int32_t ch[ROWS][K];
+        float pr[ROWS][K];
+#pragma unroll
+        for (uint32_t r = 0; r < ROWS; ++r) {
+            const bool row = j0 + r < kept;
+            const uint64_t from = (base + (uint32_t)(row ? par[j0 + r] : 0)) * A;
+#pragma unroll
+            for (uint32_t k = 0; k < K; ++k) {
+                const uint32_t ac = lane + QG_WAVE * k;
+                ch[r][k] = row && ac < A ? f.child[from + ac] : -1;
+                pr[r][k] = row && ac < A ? f.prior[from + ac] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < ROWS; ++r) {
+#pragma unroll
+            for (uint32_t k = 0; k < K; ++k) ch[r][k] = ch[r][k] >= 0 && (uint32_t)ch[r][k] < n ? idx[ch[r][k]] : -1;
+        }
+#pragma unroll
+        for (uint32_t r = 0; r < ROWS; ++r) {
+            const uint64_t to = (base + j0 + r) * A;
+#pragma unroll
+            for (uint32_t k = 0; k < K; ++k) {
+                const uint32_t ac = lane + QG_WAVE * k;
+                if (j0 + r < kept && ac < A) {
+                    f.child[to + ac] = ch[r][k];
+                    f.prior[to + ac] = pr[r][k];
+                }
+            }
+        }
+    }
+    for (uint32_t j = lane; j < cap; j += QG_WAVE) es[j] = j < kept ? (int32_t)(base + (uint32_t)par[j]) : none;
+    if (lane == 0) f.n_nodes[m] = (int32_t)kept;
+}
+
 static int mcts_check_forest(const qg_mcts_forest *f, const char *who) {
     if (!f) return set_error(QG_ERR_INVALID, "null argument");
     if (!f->parent || !f->reward || !f->value || !f->visits || !f->wsum || !f->terminal || !f->child || !f->prior || !f->n_nodes)
@@ -441,6 +576,30 @@ extern "C" int qg_mcts_decide(const qg_mcts_forest *forest, int mode, uint64_t s
     a.mode = mode;
     const dim3 grid((unsigned)((forest->n_trees + MCTS_WAVES - 1) / MCTS_WAVES)), block(64u * MCTS_WAVES);
     hipLaunchKernelGGL(mcts_decide_kernel, grid, block, 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}
+
+extern "C" int qg_mcts_rebase(const qg_mcts_forest *forest, const int32_t *move_dev, const uint8_t *finished_dev, int32_t *env_src_dev, void *stream) {
+    if (const int rc = mcts_check_forest(forest, "mcts_rebase")) return rc;
+    if (!move_dev || !env_src_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (((uintptr_t)move_dev % 4) || ((uintptr_t)env_src_dev % 4)) return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (forest->n_trees == 0) return QG_OK;
+    RebaseArgs a;
+    a.f = *forest;
+    a.move = move_dev;
+    a.finished = finished_dev;
+    a.env_src = env_src_dev;
+    const uint32_t fit = 65536u / (forest->cap * 2u * (uint32_t)sizeof(int32_t));  // trees whose two LDS tables fit one workgroup: >= 1 by MCTS_MAX_CAP
+    a.waves = fit < MCTS_WAVES ? fit : MCTS_WAVES;
+    const dim3 grid((unsigned)((forest->n_trees + a.waves - 1) / a.waves)), block(64u * a.waves);
+    const size_t lds = (size_t)a.waves * forest->cap * 2 * sizeof(int32_t);
+    switch ((forest->num_actions + QG_WAVE - 1) / QG_WAVE) {
+        case 1: hipLaunchKernelGGL(mcts_rebase_kernel<1>, grid, block, lds, (hipStream_t)stream, a); break;
+        case 2: hipLaunchKernelGGL(mcts_rebase_kernel<2>, grid, block, lds, (hipStream_t)stream, a); break;
+        case 3: hipLaunchKernelGGL(mcts_rebase_kernel<3>, grid, block, lds, (hipStream_t)stream, a); break;
+        default: hipLaunchKernelGGL(mcts_rebase_kernel<4>, grid, block, lds, (hipStream_t)stream, a); break;
+    }
     HIP_TRY(hipGetLastError());
     return QG_OK;
 }

@@ -165,13 +165,15 @@ MCTS_MAX_FOREST_BYTES = 1 << 30  # what `mcts_forest` allocates at most unless t
 class MctsForest:
     """The trees of a PUCT search as a struct of arrays (`qg_mcts_forest`), one tree per target, torch tensors on one device:
     `parent` int32, `reward` f32, `value` f32, `visits` int32, `wsum` f32, `terminal` uint8, all [M, cap]; `child` int32 (-1 = not expanded)
-    and `prior` f32, [M, cap, A]; `n_nodes` int32 [M].  `cap` = N + 1 nodes for N simulations; node 0 is the root; node j of tree m goes
+    and `prior` f32, [M, cap, A]; `n_nodes` int32 [M].  `cap` = N + 1 nodes for N simulations unless told otherwise (trees that
+    `mcts_rebase` carries from decision to decision want more); node 0 is the root; node j of tree m goes
     with env m * cap + j of a pool handle.  Only the nodes below `n_nodes[m]` mean anything.  `mcts_backup(root=True)` starts every tree."""
     FIELDS = ("parent", "reward", "value", "visits", "wsum", "terminal", "child", "prior", "n_nodes")
 
-    def __init__(self, M: int, N: int, A: int, device):
-        self.M, self.N, self.A, self.cap, self.device = M, N, A, N + 1, torch.device(device)
-        i32, f32, cap = torch.int32, torch.float32, N + 1
+    def __init__(self, M: int, N: int, A: int, device, cap: Optional[int] = None):
+        cap = N + 1 if cap is None else cap
+        self.M, self.N, self.A, self.cap, self.device = M, N, A, cap, torch.device(device)
+        i32, f32 = torch.int32, torch.float32
         for name, shape, dt in (("parent", (M, cap), i32), ("reward", (M, cap), f32), ("value", (M, cap), f32), ("visits", (M, cap), i32), ("wsum", (M, cap), f32),
                                 ("terminal", (M, cap), torch.uint8), ("child", (M, cap, A), i32), ("prior", (M, cap, A), f32), ("n_nodes", (M,), i32)):
             setattr(self, name, torch.zeros(shape, dtype=dt, device=self.device))
@@ -183,16 +185,26 @@ class MctsForest:
         return self.M * self.cap
 
 
-def mcts_forest(M: int, N: int, A: int, device=None, max_bytes: int = MCTS_MAX_FOREST_BYTES) -> MctsForest:
+MCTS_MAX_CAP = 8192  # the kernels' limit on a tree's nodes
+
+
+def mcts_forest(M: int, N: int, A: int, device=None, max_bytes: int = MCTS_MAX_FOREST_BYTES, cap: Optional[int] = None) -> MctsForest:
     """An empty forest for `mcts_select` / `mcts_backup`: M trees of N + 1 nodes over A actions (`qg_mcts_forest_bytes` says what it takes:
-    (N + 1) * (21 + 8 A) + 4 bytes per tree).  ValueError for M < 1, N < 1, A < 1 or a forest of more than `max_bytes`."""
+    (N + 1) * (21 + 8 A) + 4 bytes per tree).  cap: the nodes a tree has room for, N + 1 <= cap <= 8192, where trees are carried from
+    decision to decision (`mcts_rebase`); None: N + 1.  ValueError for M < 1, N < 1, A < 1, a cap outside its range or a forest of more
+    than `max_bytes`."""
     M, N, A = int(M), int(N), int(A)
     if M < 1 or N < 1 or A < 1:
         raise ValueError("mcts_forest: M >= 1, N >= 1 and A >= 1")
-    nbytes = int(_lib.load().qg_mcts_forest_bytes(M, N + 1, A))
+    if cap is not None:
+        cap = int(cap)
+        if not N + 1 <= cap <= MCTS_MAX_CAP:
+            raise ValueError(f"mcts_forest: cap must satisfy N + 1 = {N + 1} <= cap <= {MCTS_MAX_CAP}")
+    nodes = N + 1 if cap is None else cap
+    nbytes = int(_lib.load().qg_mcts_forest_bytes(M, nodes, A))
     if nbytes > int(max_bytes):
-        raise ValueError(f"mcts_forest: {M} trees of {N + 1} nodes over {A} actions take {nbytes} bytes, more than the limit of {int(max_bytes)}")
-    return MctsForest(M, N, A, "cuda" if device is None else device)
+        raise ValueError(f"mcts_forest: {M} trees of {nodes} nodes over {A} actions take {nbytes} bytes, more than the limit of {int(max_bytes)}")
+    return MctsForest(M, N, A, "cuda" if device is None else device, cap)
 
 
 def _mcts_vectors(name: str, forest: MctsForest, items):
@@ -279,6 +291,30 @@ def mcts_decide(forest: MctsForest, sample: bool = False, seed: int = 0, counter
                                           finished.data_ptr() if finished is not None else None, move.data_ptr(),
                                           counts.data_ptr() if counts is not None else None, ld, _stream_ptr()))
     return move
+
+
+def mcts_rebase(forest: MctsForest, move: torch.Tensor, finished: Optional[torch.Tensor] = None, env_src: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The step between two decisions (`qg_mcts_rebase`), one launch, in place on `forest`: per tree the subtree below the root's child by
+    action `move` (int32 [M], `mcts_decide`'s) becomes the tree -- the kept nodes renumbered in their order, the child the new root -- so
+    the next decision's simulations go on where this one's went.  finished: optional uint8 / bool [M], trees whose real env is final: left
+    alone.  Returns env_src, int32 [M * cap] (a preallocated one may be passed): for every new pool index the old pool index of the
+    node's env, `forest.skip` where there is none -- the `src_idx` of `other_pool.copy_envs(pool, env_src)`.  A tree with nothing to carry
+    (no such child, a move of A) stays as it is and its env_src is the identity on its nodes."""
+    if not isinstance(forest, MctsForest):
+        raise TypeError("mcts_rebase: forest must come from mcts_forest")
+    dev, i32 = forest.parent.device, torch.int32
+    if finished is not None and finished.dtype == torch.bool:
+        finished = finished.view(torch.uint8)
+    if env_src is None:
+        env_src = torch.empty(forest.M * forest.cap, dtype=i32, device=dev)
+    _mcts_vectors("mcts_rebase", forest, (("finished", finished, torch.uint8), ("move", move, i32)))
+    if move is None:
+        raise ValueError("mcts_rebase: move is required")
+    if env_src.dtype != i32 or env_src.dim() != 1 or env_src.numel() != forest.M * forest.cap or not env_src.is_contiguous() or env_src.device != dev:
+        raise ValueError(f"mcts_rebase: env_src must be a contiguous [{forest.M * forest.cap}] int32 tensor on the forest's device")
+    _lib.check(_lib.load().qg_mcts_rebase(forest._c, move.data_ptr(), finished.data_ptr() if finished is not None else None, env_src.data_ptr(),
+                                          _stream_ptr()))
+    return env_src
 
 
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,

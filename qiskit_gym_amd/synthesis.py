@@ -51,8 +51,8 @@ import torch
 
 from . import _lib
 from .envs.gyms import ROTATION_MARKER
-from .policy_kernels import (MCTS_MAX_FOREST_BYTES, BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
-                             mcts_backup, mcts_decide, mcts_forest, mcts_select, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
+from .policy_kernels import (MCTS_MAX_CAP, MCTS_MAX_FOREST_BYTES, BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
+                             mcts_backup, mcts_decide, mcts_forest, mcts_rebase, mcts_select, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
 from .vec import VecEnv
 
 
@@ -220,7 +220,9 @@ class BatchedSynthesis:
         PauliGym search, replayed with the solution log on) or "beam" (the two batches of targets * width envs that take turns as source and
         destination of the per-step copy, and the winners, all three with the same constructor arguments: the rule of `copy_envs`; no layout
         choice depends on the batch size) or "mcts" (the pool of targets * (N + 1) node envs, the leaf batch and the real batch of one env per
-        target, again all with the same constructor arguments) or "mcts-sampled" (the same three for targets * searches trees).  One batch shape at a time per kind: the handles own device memory."""
+        target, again all with the same constructor arguments) or "mcts-sampled" (the same three for targets * searches trees) or "mcts-reuse" /
+        "mcts-sampled-reuse" (`reuse_tree`: the leaf batch, TWO pools of trees * cap node envs that take turns as source and destination of
+        the copy between two decisions, and the real batch).  One batch shape at a time per kind: the handles own device memory."""
         key = (*batches, perms)  # add_perms: twists() only, the env steps alike
         held = self._held.get(kind)
         if held is not None and held.key != key:
@@ -388,22 +390,40 @@ class BatchedSynthesis:
             self.last_stats.update(bound=bound, bounded=int(bounded.sum()))
         return out
 
-    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool, searches: Optional[int] = None):
+    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool, searches: Optional[int] = None, cap: Optional[int] = None):
         """The search of `solve(num_mcts_searches=N)` on the handles of `held`: the leaf batch, which is all the forward object reads, the pool
         (node j of tree m is env m * (N + 1) + j) and the real envs.  Per decision one forward pass on the roots and N simulations of `mcts_select`,
         clone + step, one forward pass, clone back, `mcts_backup`; the rules are stated in include/qgym.h and tests/mctsmodel.py.
         `searches` None: one tree per target, the move is the root's most visited action.  `searches` = S (`mcts_sampled`): S trees per
         target, tree and real env m * S + s is search s of target m; the move is drawn from the root's visit counts (`mcts_decide`, counter
-        t) and a target's answer is that of its successful search of the greatest return (tests/mctssample_model.py)."""
-        leaf, pool, real = held.vecs
+        t) and a target's answer is that of its successful search of the greatest return (tests/mctssample_model.py).
+        `cap` (`reuse_tree`): the trees have room for cap nodes and `held` has a second pool.  Decision 0 runs as ever; after every decision
+        `mcts_rebase` makes the chosen move's subtree the tree and its `env_src` moves the kept nodes' envs into the other pool (`copy_envs`
+        allows no index on both sides within one handle), the pools swap, and the next decision makes its N simulations on what was
+        carried: no copy of the real envs, no root forward pass, no root backup (tests/mctsreuse_model.py)."""
+        reuse = cap is not None
+        if reuse:
+            leaf, pool, other, real = held.vecs
+        else:
+            leaf, pool, real = held.vecs
         S = 1 if searches is None else searches
         M, A, dev = real.batch, real.num_actions(), real.device  # M: trees, `S` per target
-        T, cap = int(real._cfg.max_depth), N + 1
-        forest = mcts_forest(M, N, A, dev)
+        T = int(real._cfg.max_depth)
+        if reuse:
+            forest = mcts_forest(M, N, A, dev, cap=cap)
+            env_src = torch.empty(M * cap, dtype=torch.int32, device=dev)
+            # the stats, without a launch per simulation: every simulation's leaves, and per decision the live trees and their carried sizes
+            leaves = torch.empty((N, M), dtype=torch.int32, device=dev)
+            sizes, lives = torch.zeros((T, M), dtype=torch.int32, device=dev), torch.zeros((T, M), dtype=torch.bool, device=dev)
+            refused = torch.zeros((), dtype=torch.int64, device=dev)
+        else:
+            cap = N + 1
+            forest = mcts_forest(M, N, A, dev)
         fwd = self._forward(held, 1, None, kernels, rows=True)
         self._load(real, states, S)
         if searches is not None:
             ret = torch.zeros(M, dtype=torch.float32, device=dev)
+        if searches is not None or reuse:
             drawn = torch.empty(M, dtype=torch.int32, device=dev)
         ids = torch.arange(M, dtype=torch.int32, device=dev)
         roots = ids * cap
@@ -414,18 +434,23 @@ class BatchedSynthesis:
         nodes, decisions = torch.zeros((), dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
         steps = 0
         for t in range(T):
-            leaf.copy_envs(real, ids)
-            rows, values = fwd.logp_values(leaf)
-            pool.copy_envs(leaf, ids, roots)
-            mcts_backup(forest, rows, values, done=finished, root=True)
-            for _ in range(N):
-                src, dst, act, lf = mcts_select(forest, C, finished, *picked)
+            if t == 0 or not reuse:
+                leaf.copy_envs(real, ids)
+                rows, values = fwd.logp_values(leaf)
+                pool.copy_envs(leaf, ids, roots)
+                mcts_backup(forest, rows, values, done=finished, root=True)
+            for s in range(N):
+                src, dst, act, lf = mcts_select(forest, C, finished, *picked[:3], leaves[s] if reuse else picked[3])
                 leaf.copy_envs(pool, src)
                 leaf.step(act)  # A where nothing is expanded: no gate, and `dst` names no env of the pool
                 rows, values = fwd.logp_values(leaf)
                 pool.copy_envs(leaf, ids, dst)
                 mcts_backup(forest, rows, values, leaf.reward, leaf.done, src, dst, act, lf)
-            if searches is None:
+            if reuse:  # a full tree: the simulation that wants to expand does not count
+                refused += ((leaves < 0) & (finished == 0)).sum()
+            if searches is None and reuse:  # the same decision on its kernel: one launch
+                move = mcts_decide(forest, finished=finished, move=drawn)
+            elif searches is None:
                 # the decision: the root's expanded action of the most visits, the lowest among equals; A where the root has no child
                 child = forest.child[:, 0, :].to(torch.int64)
                 visits = torch.gather(forest.visits.to(torch.int64), 1, child.clamp(min=0))
@@ -440,6 +465,12 @@ class BatchedSynthesis:
             if searches is not None:
                 ret += torch.where(live, real.reward, torch.zeros_like(ret))
             finished |= real.done.bool().to(torch.uint8)
+            if reuse:  # a tree whose real env just ended is left alone and copies nothing
+                mcts_rebase(forest, move, finished, env_src)
+                other.copy_envs(pool, env_src)
+                pool, other = other, pool
+                torch.eq(finished, 0, out=lives[t])
+                torch.mul(forest.n_nodes, lives[t], out=sizes[t])
             steps = t + 1
             if t % 8 == 7 and bool(finished.all()):
                 break
@@ -460,6 +491,8 @@ class BatchedSynthesis:
         gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
         stats.update({"targets": M // S, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0,
                       "nodes": float(nodes) / max(int(decisions), 1), "kernels": fwd.kernels})
+        if reuse:
+            stats.update(reuse=True, capacity=cap, carried=float(sizes.sum()) / max(int(lives.sum()), 1), refused=int(refused))
         self.last_stats = stats
         return out
 
@@ -467,7 +500,8 @@ class BatchedSynthesis:
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
               beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None,
               twist_kernels: bool = False, bound: Optional[str] = None, num_mcts_searches: int = 0, C: float = 2 ** 0.5,
-              max_expand_depth: int = 1, mcts_sampled: bool = False) -> List[Optional[List[int]]]:
+              max_expand_depth: int = 1, mcts_sampled: bool = False, reuse_tree: bool = False,
+              mcts_nodes: Optional[int] = None) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         The rules of the sampled and the greedy search -- env m * S + s is search s of target m, the draw of step t is the race of
         `sample_actions(logits, seed, t)`, a finished env gets no gate and adds no reward, the loop ends at the first step t with
@@ -568,14 +602,33 @@ class BatchedSynthesis:
         markers included, no replay).  The rules are restated in tests/mctssample_model.py.  `last_stats`: "mcts", "searches" (S),
         "targets", "steps", "solved", "searches_solved" (successful searches / all), "mean_gates", "nodes", "kernels".  The handles are
         of a kind of their own ("mcts-sampled").  ValueError: without num_mcts_searches >= 1; with deterministic=True; with beam_width,
-        merge_duplicates, bound, twists or twist_kernels; and the tree search's own, the forest limit now on targets * S trees."""
+        merge_duplicates, bound, twists or twist_kernels; and the tree search's own, the forest limit now on targets * S trees.
+
+        reuse_tree=True, with num_mcts_searches=N >= 1, deterministic or `mcts_sampled` (default False: not one launch, handle or
+        `last_stats` entry changes): the chosen move's subtree is kept between decisions.  The search handles step deterministically, so
+        the child under the move IS the next root, and its priors, values, children and stepped envs are valid search work.  The trees
+        have room for cap = `mcts_nodes` nodes, by default min(2 N + 1, 8192).  Decision 0 runs as above; after every decision
+        `collector.mcts_rebase` compacts every live tree to that subtree on the device (the new root keeps its visits, 1 + the simulations
+        below it) and the kept nodes' envs move into a second pool; decisions t >= 1 make their N simulations on the carried tree, without
+        the copy of the real envs, the root's forward pass and the root backup; the deterministic search's decision is `collector.mcts_decide`'s
+        most visited action, one launch.  A tree that is full makes no further nodes: a simulation
+        that wants to expand does not count (`collector.mcts_select`: leaf = -1).  The rules are in include/qgym.h and restated in
+        tests/mctsreuse_model.py.  `last_stats` gains "reuse" (True), "capacity" (cap), "carried" (mean nodes right after the rebase, over
+        live trees and decisions t >= 1) and "refused" ((live tree, simulation) pairs that did not count); "nodes" is the mean size at
+        the decision, carried nodes included.  The handles are of a kind of their own ("mcts-reuse", "mcts-sampled-reuse"): the leaf
+        batch, two pools of trees * cap envs, the real batch.  ValueError: reuse_tree without num_mcts_searches >= 1; mcts_nodes without
+        reuse_tree; mcts_nodes outside [N + 1, 8192]; the forest limit counts cap nodes per tree."""
         M = len(states)
         S = max(1, int(num_searches)) if mcts_sampled else 1
         self._check_options(M == 0, fast, beam_width, merge_duplicates, twists, twist_kernels, bound)
         N = self._check_mcts(M * S, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
-                             mcts_sampled)
+                             mcts_sampled, reuse_tree, mcts_nodes)
         if M == 0:
             return []
+        if N and reuse_tree:
+            B, cap = M * S, int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)
+            held = self._handles("mcts-sampled-reuse" if mcts_sampled else "mcts-reuse", (B, B * cap, B * cap, B))
+            return self._mcts_search(states, held, N, float(C), fast is True, S if mcts_sampled else None, cap)
         if N and mcts_sampled:
             B = M * S
             return self._mcts_search(states, self._handles("mcts-sampled", (B, B * (N + 1), B)), N, float(C), fast is True, S)
@@ -620,7 +673,7 @@ class BatchedSynthesis:
                                  "beyond the observed columns: the reward still to come has no bound the search can see")
 
     def _check_mcts(self, trees: int, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
-                    mcts_sampled) -> int:
+                    mcts_sampled, reuse_tree=False, mcts_nodes=None) -> int:
         """`num_mcts_searches` as an int, after the ValueErrors of `solve`'s tree search on `trees` trees; 0: no tree search, and `C` and
         `max_expand_depth` mean nothing."""
         N = int(num_mcts_searches)
@@ -628,6 +681,10 @@ class BatchedSynthesis:
             raise ValueError("num_mcts_searches must be at least 0")
         if mcts_sampled and N == 0:
             raise ValueError("mcts_sampled=True needs num_mcts_searches >= 1: it draws the moves of a tree search")
+        if reuse_tree and N == 0:
+            raise ValueError("reuse_tree=True needs num_mcts_searches >= 1: it keeps the subtree of a tree search's move")
+        if mcts_nodes is not None and not reuse_tree:
+            raise ValueError("mcts_nodes needs reuse_tree=True: without it a tree holds the N + 1 nodes of one decision")
         if N == 0:
             return 0
         if not float(C) > 0.0:
@@ -642,7 +699,12 @@ class BatchedSynthesis:
                                        ("twists", twists is not None), ("twist_kernels", twist_kernels)) if on]
         if mixed:
             raise ValueError(f"num_mcts_searches cannot be combined with {', '.join(mixed)}")
-        nbytes = int(_lib.load().qg_mcts_forest_bytes(trees, min(N + 1, 2 ** 32 - 1), len(self.env.config["gateset"])))
+        nodes = N + 1
+        if reuse_tree:
+            nodes = int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)
+            if not N + 1 <= nodes <= MCTS_MAX_CAP:
+                raise ValueError(f"mcts_nodes must satisfy num_mcts_searches + 1 = {N + 1} <= mcts_nodes <= {MCTS_MAX_CAP}, got {nodes}")
+        nbytes = int(_lib.load().qg_mcts_forest_bytes(trees, min(nodes, 2 ** 32 - 1), len(self.env.config["gateset"])))
         if nbytes > MCTS_MAX_FOREST_BYTES:
             raise ValueError(f"num_mcts_searches={N}: the forest of {trees} trees takes {nbytes} bytes, more than the limit of {MCTS_MAX_FOREST_BYTES}")
         return N
@@ -713,11 +775,13 @@ class BatchedSynthesis:
 
     def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
               twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False, bound: Optional[str] = None,
-              num_mcts_searches: int = 0, C: float = 2 ** 0.5, max_expand_depth: int = 1, mcts_sampled: bool = False):
+              num_mcts_searches: int = 0, C: float = 2 ** 0.5, max_expand_depth: int = 1, mcts_sampled: bool = False, reuse_tree: bool = False,
+              mcts_nodes: Optional[int] = None):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
         sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, fast=fast, beam_width=beam_width,
                           merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels, bound=bound,
-                          num_mcts_searches=num_mcts_searches, C=C, max_expand_depth=max_expand_depth, mcts_sampled=mcts_sampled)
+                          num_mcts_searches=num_mcts_searches, C=C, max_expand_depth=max_expand_depth, mcts_sampled=mcts_sampled,
+                          reuse_tree=reuse_tree, mcts_nodes=mcts_nodes)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):
