@@ -35,7 +35,7 @@ extern "C" {
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
  *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance, qg_mcts_forest_bytes,
- *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide, qg_mcts_rebase (additions only) */
+ *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide, qg_mcts_rebase, qg_search_plan_query (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -864,6 +864,20 @@ typedef enum {
     QG_PLAN_COPY_ENVS = 9        /* qg_vec_copy_envs: "copy_envs_kernel [rows x w ...]", the state regions of a tile it walks */
 } qg_plan_op;
 int qg_plan_query(const qg_config *cfg, uint64_t batch, uint32_t num_actions, int op, uint64_t arg, int nonsymplectic, char *name_out, size_t cap);
+
+/* The launch geometry of the search kernels, from the same functions their launchers call (csrc/qgym_plan.hpp); needs no GPU.  No result
+ * depends on it -- the kernels give the same answer whatever way the work is dealt to waves -- so a test pins which shapes reach which
+ * bracket (tests/test_search_dispatch.py).  Returns the number asked for, or a negative status: QG_ERR_INVALID for an unknown op or a zero
+ * size, QG_ERR_UNSUPPORTED beyond the kernel's limits (cap > 8192, num_actions > 256, width > 64, width * num_actions > 14 336; qg_beam_merge's
+ * limit on an env's bytes is not checked here: the word size is no argument). */
+typedef enum {
+    QG_SEARCH_PLAN_MCTS_TREES = 0,   /* a = cap: trees (waves) per workgroup of qg_mcts_select and qg_mcts_rebase, min(4, 65536 / (8 cap)) */
+    QG_SEARCH_PLAN_REBASE_SLICES = 1, /* a = num_actions: K = ceil(num_actions / 64) of qg_mcts_rebase's row pass */
+    QG_SEARCH_PLAN_REBASE_ROWS = 2,  /* a = num_actions: the kept nodes' rows it moves per trip, 16 / K */
+    QG_SEARCH_PLAN_BEAM_SELECT_WAVES = 3, /* a = width, b = num_actions: 1, 2, 4 or 8 for width * num_actions <= 1024, <= 2048, <= 6144, above */
+    QG_SEARCH_PLAN_BEAM_MERGE_WAVES = 4   /* a = width, b = words_per_env, c = seen_cap (0: no history): 1 where a * b <= 512 and c <= 512, else 4 */
+} qg_search_plan_op;
+int64_t qg_search_plan_query(int op, uint64_t a, uint64_t b, uint64_t c);
 
 /* ------------------------------------------------------------------------------------------
  * Scalar environment: the `Env` trait method for method (clifford.rs:285-382): a batch of one on the same kernels.  A call that changes the

@@ -32,9 +32,10 @@
 
 namespace qg {
 
-constexpr uint32_t MCTS_WAVES = 4;          // trees per workgroup (fewer where a tree's LDS copy is large)
-constexpr uint32_t MCTS_MAX_ACTIONS = 256;  // four actions per lane
-constexpr uint32_t MCTS_MAX_CAP = 8192;     // 8 bytes of LDS per node, one tree per workgroup at the limit
+// the launch geometry -- trees per workgroup, the rebase's slices of 64 actions -- and the limits: qgym_plan.hpp
+using plan::MCTS_MAX_ACTIONS;
+using plan::MCTS_MAX_CAP;
+using plan::MCTS_WAVES;
 
 // larger score <=> larger word; a NaN has no word (0); every other score's word is >= 0x007FFFFF
 __device__ inline uint32_t mcts_order(float score) {
@@ -368,7 +369,7 @@ struct RebaseArgs {
 // before its first store, a store never lands on a node still to be read.
 template <uint32_t K>  // slices of 64 actions
 __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_rebase_kernel(const RebaseArgs a) {
-    constexpr uint32_t ROWS = 16 / K;
+    constexpr uint32_t ROWS = plan::mcts_rebase_rows(K);
     extern __shared__ int32_t mcts_rebase_lds[];  // [waves][2][cap]: parent, later the kept nodes in order | new index, -1: not kept
     const qg_mcts_forest &f = a.f;
     const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
@@ -519,8 +520,8 @@ extern "C" int qg_mcts_select(const qg_mcts_forest *forest, float c_puct, const 
     a.act = act_dev;
     a.leaf = leaf_dev;
     a.C = c_puct;
-    const uint32_t fit = 65536u / (forest->cap * (uint32_t)sizeof(uint2));  // trees whose LDS copies fit one workgroup: >= 1 by MCTS_MAX_CAP
-    a.waves = fit < MCTS_WAVES ? fit : MCTS_WAVES;
+    static_assert(sizeof(uint2) == plan::MCTS_LDS_NODE_BYTES, "a node's LDS copy");
+    a.waves = plan::mcts_trees_per_workgroup(forest->cap);  // trees whose LDS copies fit one workgroup
     const dim3 grid((unsigned)((forest->n_trees + a.waves - 1) / a.waves)), block(64u * a.waves);
     hipLaunchKernelGGL(mcts_select_kernel, grid, block, (size_t)a.waves * forest->cap * sizeof(uint2), (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
@@ -590,11 +591,11 @@ extern "C" int qg_mcts_rebase(const qg_mcts_forest *forest, const int32_t *move_
     a.move = move_dev;
     a.finished = finished_dev;
     a.env_src = env_src_dev;
-    const uint32_t fit = 65536u / (forest->cap * 2u * (uint32_t)sizeof(int32_t));  // trees whose two LDS tables fit one workgroup: >= 1 by MCTS_MAX_CAP
-    a.waves = fit < MCTS_WAVES ? fit : MCTS_WAVES;
+    static_assert(2 * sizeof(int32_t) == plan::MCTS_LDS_NODE_BYTES, "a node's two table entries");
+    a.waves = plan::mcts_trees_per_workgroup(forest->cap);  // trees whose two LDS tables fit one workgroup
     const dim3 grid((unsigned)((forest->n_trees + a.waves - 1) / a.waves)), block(64u * a.waves);
     const size_t lds = (size_t)a.waves * forest->cap * 2 * sizeof(int32_t);
-    switch ((forest->num_actions + QG_WAVE - 1) / QG_WAVE) {
+    switch (plan::mcts_rebase_slices(forest->num_actions)) {
         case 1: hipLaunchKernelGGL(mcts_rebase_kernel<1>, grid, block, lds, (hipStream_t)stream, a); break;
         case 2: hipLaunchKernelGGL(mcts_rebase_kernel<2>, grid, block, lds, (hipStream_t)stream, a); break;
         case 3: hipLaunchKernelGGL(mcts_rebase_kernel<3>, grid, block, lds, (hipStream_t)stream, a); break;

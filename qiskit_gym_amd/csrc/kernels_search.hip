@@ -24,9 +24,9 @@
 
 namespace qg {
 
-constexpr uint32_t BEAM_MAX_WIDTH = 64;      // one lane of a wave per output slot
-constexpr uint32_t BEAM_MAX_CAND = 14336;    // width * num_actions: 56 KiB of order words (64 beams x 224 actions)
-constexpr uint32_t BEAM_MAX_WAVES = 8;
+using plan::BEAM_MAX_CAND;
+using plan::BEAM_MAX_WIDTH;
+using plan::BEAM_MAX_WAVES;  // the waves of a launch: qgym_plan.hpp beam_select_waves
 
 struct BeamArgs {
     const void *logp;
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(64 * BEAM_MAX_WAVES) void beam_select_kernel(const 
 //      remaining slot with its key has the larger (order word, lower slot)); survivors take consecutive places of the history by a ballot.
 // One workgroup owns a group's history and counters for the whole launch: plain vector loads and stores, no atomics.
 constexpr uint32_t MERGE_MAX_ENV_BYTES = 2048;
-constexpr uint32_t MERGE_WAVES = 4;
+using plan::MERGE_WAVES;  // the waves of a launch: qgym_plan.hpp beam_merge_waves
 
 struct MergeArgs {
     const void *words;
@@ -380,8 +380,7 @@ extern "C" int qg_beam_select(const void *logp_dev, int logp_dtype, uint64_t ld,
     a.W = width;
     a.n = width * num_actions;
     a.act64 = action_dtype == QG_ACT_I64;
-    // about 16 candidates per lane before another wave joins (each of the W rounds rescans one lane's share); the result does not depend on it
-    const uint32_t waves = a.n <= 1024u ? 1u : a.n <= 2048u ? 2u : a.n <= 6144u ? 4u : BEAM_MAX_WAVES;
+    const uint32_t waves = plan::beam_select_waves(a.n);  // the result does not depend on it
     const dim3 grid((unsigned)n_groups), block(64u * waves);
     const size_t lds = (size_t)waves * width * sizeof(uint64_t) + (size_t)a.n * sizeof(uint32_t);  // <= 4 KiB + 56 KiB
     hipStream_t s = (hipStream_t)stream;
@@ -421,8 +420,7 @@ extern "C" int qg_beam_merge(const void *words_dev, int word_bytes, uint32_t wor
     a.cap = seen_dev ? seen_cap : 0;
     a.W = width;
     a.n = words_per_env;
-    // one wave while a group's words and its history are a few hundred each; the result does not depend on it
-    const uint32_t waves = (uint64_t)width * words_per_env <= 512u && a.cap <= 512u ? 1u : MERGE_WAVES;
+    const uint32_t waves = plan::beam_merge_waves(width, words_per_env, a.cap);  // the result does not depend on it
     const dim3 grid((unsigned)n_groups), block(64u * waves);
     const size_t lds = ((size_t)words_per_env + width) * sizeof(uint64_t) + (size_t)width * 2 * sizeof(uint32_t);  // <= 16 KiB + 1 KiB
     hipStream_t s = (hipStream_t)stream;

@@ -1271,6 +1271,31 @@ int qg_plan_query(const qg_config *cfg, uint64_t batch, uint32_t num_actions, in
     return QG_OK;
 }
 
+int64_t qg_search_plan_query(int op, uint64_t a, uint64_t b, uint64_t c) {
+    switch (op) {
+    case QG_SEARCH_PLAN_MCTS_TREES:
+        if (a < 2) return set_error(QG_ERR_INVALID, "search_plan: cap >= 2");
+        if (a > plan::MCTS_MAX_CAP) return set_error(QG_ERR_UNSUPPORTED, "search_plan: cap <= %u supported", plan::MCTS_MAX_CAP);
+        return plan::mcts_trees_per_workgroup((uint32_t)a);
+    case QG_SEARCH_PLAN_REBASE_SLICES:
+    case QG_SEARCH_PLAN_REBASE_ROWS:
+        if (a == 0) return set_error(QG_ERR_INVALID, "search_plan: num_actions >= 1");
+        if (a > plan::MCTS_MAX_ACTIONS) return set_error(QG_ERR_UNSUPPORTED, "search_plan: num_actions <= %u supported", plan::MCTS_MAX_ACTIONS);
+        return op == QG_SEARCH_PLAN_REBASE_SLICES ? plan::mcts_rebase_slices((uint32_t)a) : plan::mcts_rebase_rows(plan::mcts_rebase_slices((uint32_t)a));
+    case QG_SEARCH_PLAN_BEAM_SELECT_WAVES:
+        if (a == 0 || b == 0) return set_error(QG_ERR_INVALID, "search_plan: width and num_actions must be positive");
+        if (a > plan::BEAM_MAX_WIDTH || b > plan::BEAM_MAX_CAND || a * b > plan::BEAM_MAX_CAND)
+            return set_error(QG_ERR_UNSUPPORTED, "search_plan: width <= %u and width * num_actions <= %u supported", plan::BEAM_MAX_WIDTH, plan::BEAM_MAX_CAND);
+        return plan::beam_select_waves((uint32_t)(a * b));
+    case QG_SEARCH_PLAN_BEAM_MERGE_WAVES:
+        if (a == 0 || b == 0) return set_error(QG_ERR_INVALID, "search_plan: width and words_per_env must be positive");
+        if (a > plan::BEAM_MAX_WIDTH || b > 0xFFFFFFFFull || c > 0xFFFFFFFFull)
+            return set_error(QG_ERR_UNSUPPORTED, "search_plan: width <= %u, words_per_env and seen_cap < 2^32 supported", plan::BEAM_MAX_WIDTH);
+        return plan::beam_merge_waves((uint32_t)a, (uint32_t)b, c);
+    default: return set_error(QG_ERR_INVALID, "unknown search plan op %d", op);
+    }
+}
+
 int qg_vec_copy_envs(qg_vec *dst, const qg_vec *src, const uint32_t *src_idx_dev, const uint32_t *dst_idx_dev, uint64_t n, void *stream) {
     if (!dst || !src || (n && !src_idx_dev)) return set_error(QG_ERR_INVALID, "null argument");
     if (!same_ctor(dst, src)) return set_error(QG_ERR_INVALID, "copy_envs: source and destination need the same constructor arguments and device");

@@ -412,5 +412,33 @@ inline bool dense_rides_in_step(const HandlePlan &p) {  // env.step() on a handl
     return dense_in_kernel(p, step_kernel_of(p, 1, false, false, false, 1, false));
 }
 
+// ---- search kernels: launch geometry (kernels_mcts.hip, kernels_search.hip) -----------------------------------------------------------
+// None of these changes a result: every kernel deals its work to lanes and waves so that the answer is the same whatever the deal.  They are
+// written here so that qg_search_plan_query answers them without a GPU and tests/test_search_dispatch.py pins every bracket the GPU tests
+// are meant to reach.
+constexpr uint32_t SEARCH_LDS_BYTES = 65536;   // what one workgroup may ask for
+constexpr uint32_t MCTS_WAVES = 4;             // trees per workgroup (fewer where a tree's LDS tables are large)
+constexpr uint32_t MCTS_MAX_ACTIONS = 256;     // four actions per lane
+constexpr uint32_t MCTS_MAX_CAP = 8192;        // 8 bytes of LDS per node, one tree per workgroup at the limit
+constexpr uint32_t MCTS_LDS_NODE_BYTES = 8;    // select: (visits, wsum); rebase: (parent, new index)
+// trees (waves) per workgroup of qg_mcts_select and qg_mcts_rebase: those whose LDS tables fit one workgroup; >= 1 by MCTS_MAX_CAP
+constexpr uint32_t mcts_trees_per_workgroup(uint32_t cap) {
+    return SEARCH_LDS_BYTES / (cap * MCTS_LDS_NODE_BYTES) < MCTS_WAVES ? SEARCH_LDS_BYTES / (cap * MCTS_LDS_NODE_BYTES) : MCTS_WAVES;
+}
+// slices of 64 actions of qg_mcts_rebase's row pass (mcts_rebase_kernel<K>, 16 / K rows per trip), 1 .. 4 by MCTS_MAX_ACTIONS
+constexpr uint32_t mcts_rebase_slices(uint32_t num_actions) { return (num_actions + 63u) / 64u; }
+constexpr uint32_t mcts_rebase_rows(uint32_t slices) { return 16u / slices; }
+// waves of qg_beam_select's one workgroup per group, from n = width * num_actions: about 16 candidates per lane before another wave joins
+// (each of the W rounds rescans one lane's share)
+constexpr uint32_t BEAM_MAX_WIDTH = 64;      // one lane of a wave per output slot
+constexpr uint32_t BEAM_MAX_CAND = 14336;    // width * num_actions: 56 KiB of order words (64 beams x 224 actions)
+constexpr uint32_t BEAM_MAX_WAVES = 8;
+constexpr uint32_t beam_select_waves(uint32_t n) { return n <= 1024u ? 1u : n <= 2048u ? 2u : n <= 6144u ? 4u : BEAM_MAX_WAVES; }
+// waves of qg_beam_merge's one workgroup per group: one while a group's words and its history are a few hundred each
+constexpr uint32_t MERGE_WAVES = 4;
+constexpr uint32_t beam_merge_waves(uint32_t width, uint32_t words_per_env, uint64_t seen_cap) {
+    return (uint64_t)width * words_per_env <= 512u && seen_cap <= 512u ? 1u : MERGE_WAVES;
+}
+
 }  // namespace plan
 }  // namespace qg

@@ -63,8 +63,8 @@ def select(f: Forest, C: float, finished: Optional[np.ndarray] = None):
     return src, dst, act, leaf
 
 
-def kept_nodes(f: Forest, m: int, c: int) -> List[int]:
-    """The nodes of tree m that hang below c, c first, ascending."""
+def kept_nodes_by_walk(f: Forest, m: int, c: int) -> List[int]:
+    """The nodes of tree m that hang below c, c first, ascending: the rule as it is stated, every node's chain walked to its end."""
     n = int(f.n_nodes[m])
     out = [c]
     for j in range(c + 1, n):
@@ -78,6 +78,20 @@ def kept_nodes(f: Forest, m: int, c: int) -> List[int]:
                 break
             y = p
     return out
+
+
+def kept_nodes(f: Forest, m: int, c: int) -> List[int]:
+    """`kept_nodes_by_walk` without the walks.  The chain of j goes on at p = parent[j] where c < p < j, and from there it is the chain of
+    p, a node settled before j: j is kept iff p is c, or c < p < j and p is kept.  A chain of thousands of nodes costs one step per node
+    here and a walk of its whole length per node there; tests/test_mctsreuse_model.py holds the two together."""
+    n = int(f.n_nodes[m])
+    parent = f.parent[m, :n].tolist()
+    kept = [False] * n
+    kept[c] = True
+    for j in range(c + 1, n):
+        p = parent[j]
+        kept[j] = c <= p < j and kept[p]  # (p == c: kept[c]; below c, at or above j, negative: the chain breaks)
+    return [j for j in range(c, n) if kept[j]]
 
 
 def carried_child(f: Forest, m: int, a: int) -> Optional[int]:

@@ -63,6 +63,11 @@ CASES = [  # W, A, ld, groups, dtype
     (1, 3, 5, 1, "f32"), (1, 170, 176, 2500, "bf16"), (2, 3, 4, 4097, "bf16"), (2, 222, 224, 300, "f32"), (16, 3, 8, 3000, "f32"),
     (16, 170, 176, 3000, "f32"), (16, 170, 172, 64, "bf16"), (16, 222, 223, 1, "f16"), (64, 3, 4, 2000, "bf16"), (64, 170, 171, 40, "f32"),
     (64, 222, 224, 130, "f32"), (64, 222, 232, 1, "bf16"),
+    # both sides of every break of the number of waves (1, 2, 4, 8 for W * A <= 1024, <= 2048, <= 6144, above: tests/test_search_dispatch.py
+    # pins which is which); 2050 and 6148 are the smallest products above their breaks that a width <= 64 and <= 256 actions give; 14336 is
+    # the most a group holds
+    (16, 64, 68, 40, "f32"), (25, 41, 44, 40, "bf16"), (16, 100, 104, 40, "f32"), (16, 100, 104, 40, "bf16"), (16, 100, 104, 40, "f16"),
+    (64, 32, 36, 40, "bf16"), (10, 205, 208, 40, "f32"), (32, 192, 196, 40, "f16"), (29, 212, 216, 40, "f32"), (64, 224, 228, 40, "bf16"),
 ]
 
 

@@ -49,6 +49,7 @@ def to_dev(words, cum, live):
 CASES = [  # W, words_per_env, word_bytes, groups, seen_cap (None: 3 * W, never full)
     (1, 1, 8, 3, None), (8, 6, 4, 5, None), (16, 9, 1, 4, None), (33, 32, 4, 70, None), (64, 64, 8, 2, None), (64, 256, 1, 2, None),
     (8, 6, 4, 5, 3),  # a pool of 4 rows per group and room for 3 keys: the history saturates
+    (8, 64, 4, 5, None), (9, 57, 4, 5, None),  # 512 and 513 words per group: the last shape of one wave, the first of four (test_search_dispatch.py)
 ]
 
 
@@ -95,6 +96,47 @@ def test_kernel_against_the_model_bit_for_bit(W, n, wb, groups, cap):
     live_out = beam_merge(*to_dev(words, cum, live), W)
     torch.cuda.synchronize()
     np.testing.assert_array_equal(live_out.cpu().numpy(), merge(words, cum, live, W)[0], err_msg="no history")
+
+
+@pytest.mark.parametrize("cap", [512, 513])
+def test_a_long_history_with_small_words(cap):
+    """W 8, 6 words per env -- a group's 48 words would go to one wave -- with room for 512 keys (one wave: the last capacity that takes it)
+    and for 513 (four waves, because of the history alone).  100 calls of mostly new rows: the history grows past 512 keys where there is
+    room, so the threads' shares of it are dozens of keys each and a revisited key lies anywhere in it, and saturates at 512 where not."""
+    from qiskit_gym_amd.collector import beam_merge, beam_seen
+
+    W, n, groups, calls = 8, 6, 3, 100
+    B = groups * W
+    rng = np.random.default_rng(cap)
+    seen_m, total = [[] for _ in range(groups)], np.zeros((groups, 2), dtype=np.uint32)
+    seen = beam_seen(groups, cap, "cuda")
+    dropped = torch.zeros((groups, 2), dtype=torch.int32, device="cuda")
+    keys = torch.empty(B, dtype=torch.int64, device="cuda")
+    rows = rng.integers(0, 1 << 32, size=(calls, B, n), dtype=np.uint64).astype(np.uint32)
+    rows[:, :, 0] = np.arange(calls * B, dtype=np.uint32).reshape(calls, B)  # no two rows alike, whatever the draw
+    revisits = late = 0
+    for c in range(calls):
+        words = rows[c].copy()
+        for slot in np.nonzero(rng.random(B) < 0.12)[0]:  # a row its group has met: in an earlier call, anywhere in the history, or in this one
+            back = int(rng.integers(0, c + 1))
+            words[slot] = rows[back, slot // W * W + int(rng.integers(0, W))] if back < c else words[slot // W * W]
+        cum = rng.choice(CUMS, size=B, p=[0.2, 0.15, 0.2, 0.2, 0.15, 0.05, 0.05])
+        live = (rng.random(B) < 0.9).astype(np.uint8)
+        held = [len(h) for h in seen_m]
+        live_want, keys_want, d = merge(words, cum, live, W, seen_m, cap)
+        total += d
+        revisits += int(d[:, 0].sum())
+        late += int(d[:, 0].sum()) if min(held) > 448 else 0  # revisits found in a history of hundreds of keys
+        live_out = beam_merge(*to_dev(words, cum, live), W, seen, cap, keys=keys, dropped=dropped)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(keys.cpu().numpy().view(np.uint64), keys_want, err_msg=f"keys, call {c}")
+        np.testing.assert_array_equal(live_out.cpu().numpy(), live_want, err_msg=f"live_out, call {c}")
+        np.testing.assert_array_equal(dropped.cpu().numpy().view(np.uint32), total, err_msg=f"dropped, call {c}")
+    got = seen.cpu().numpy().view(np.uint64).reshape(groups, cap + 1)
+    for g in range(groups):  # the history itself: the number of keys held, then the keys in the order they came
+        assert got[g, 0] == len(seen_m[g]) and got[g, 1 : 1 + len(seen_m[g])].tolist() == seen_m[g], g
+    assert revisits >= 20 and late >= 1 and total[:, 1].sum() >= 1
+    assert [len(h) for h in seen_m] == [cap] * groups if cap == 512 else min(len(h) for h in seen_m) > 512
 
 
 def test_the_launch_replayed_from_a_graph_with_the_memset_inside():

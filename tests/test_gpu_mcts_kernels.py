@@ -8,15 +8,10 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from mctsdevice import C, Data, Device, bits  # noqa: E402
 from mctsmodel import FIELDS, Forest, backup, check_invariants, root, select  # noqa: E402
 
-C = 2 ** 0.5
 EXP_ULPS = 4
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({1: np.uint8, 4: np.uint32}[x.dtype.itemsize])
 
 
 def expect_forest(dev, model, label):
@@ -31,71 +26,6 @@ def expect_priors(got, logp, label):
     """Rows of `prior` against exp(logp) in f32."""
     want = np.exp(logp.astype(np.float32))
     assert (np.abs(got.astype(np.float64) - want) <= EXP_ULPS * np.spacing(want)).all(), label
-
-
-class Data:
-    """The test's stand-in for envs and policy: per call rows of log-probabilities [M, ld] (the columns past A hold a value that would
-    win every comparison, and turn every prior into +inf, if it were read), values, rewards and terminal flags."""
-
-    def __init__(self, M, A, ld, seed, quantised):
-        self.M, self.A, self.ld, self.quantised, self.rng = M, A, ld, quantised, np.random.default_rng(seed)
-
-    def rows(self):
-        rng, M, A = self.rng, self.M, self.A
-        logp = np.full((M, self.ld), 3.0e38, dtype=np.float32)
-        if self.quantised:  # few distinct priors, some of them 0: equal scores are frequent
-            with np.errstate(divide="ignore"):  # a prior of 0: log-probability -inf, a masked action
-                logp[:, :A] = np.log(rng.integers(0, 4, size=(M, A)).astype(np.float32) / np.float32(4.0 * A)).astype(np.float32)
-            values = (rng.integers(-2, 5, size=M) / 4.0).astype(np.float32)
-            reward = (rng.integers(-2, 5, size=M) / 4.0).astype(np.float32)
-        else:
-            logp[:, :A] = np.log(rng.dirichlet(np.ones(A), size=M)).astype(np.float32)
-            values = rng.standard_normal(M).astype(np.float32)
-            reward = (rng.random(M) * 1.5 - 0.5).astype(np.float32)
-        done = (rng.random(M) < 0.15).astype(np.uint8)
-        done[0] = 0  # tree 0 never meets a terminal node: it fills its N + 1 nodes exactly
-        return logp, values, reward, done
-
-
-class Device:
-    """The forest on the device with static operand buffers, so that a select / backup pair can be captured once and replayed."""
-
-    def __init__(self, M, N, A, ld):
-        from qiskit_gym_amd.collector import mcts_forest
-
-        self.forest = mcts_forest(M, N, A, "cuda")
-        self.logp = torch.empty((M, ld), dtype=torch.float32, device="cuda")
-        self.values, self.reward = (torch.empty(M, dtype=torch.float32, device="cuda") for _ in range(2))
-        self.done, self.finished = (torch.zeros(M, dtype=torch.uint8, device="cuda") for _ in range(2))
-        self.picked = tuple(torch.full((M,), -7, dtype=torch.int32, device="cuda") for _ in range(4))
-        self.graph = None
-
-    def load(self, logp, values, reward=None, done=None):
-        for t, a in ((self.logp, logp), (self.values, values), (self.reward, reward), (self.done, done)):
-            if a is not None:
-                t.copy_(torch.as_tensor(a))
-
-    def root(self, with_done):
-        from qiskit_gym_amd.collector import mcts_backup
-
-        mcts_backup(self.forest, self.logp, self.values, done=self.done if with_done else None, root=True)
-
-    def pair(self):
-        from qiskit_gym_amd.collector import mcts_backup, mcts_select
-
-        out = mcts_select(self.forest, C, self.finished, *self.picked)
-        assert all(o is p for o, p in zip(out, self.picked))
-        mcts_backup(self.forest, self.logp, self.values, self.reward, self.done, *self.picked)
-
-    def simulate(self, captured):
-        if not captured:
-            return self.pair()
-        if self.graph is None:
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.pair()
-        self.graph.replay()
 
 
 def drive(M, N, A, ld, seed, quantised=True, captured=False):

@@ -1,5 +1,5 @@
 """`collector.mcts_rebase` against the CPU model of tests/mctsreuse_model.py, bit for bit, on forests the test drives itself with the
-`Device` / `Data` scheme of tests/test_gpu_mcts_kernels.py: decisions of driven simulations, a rebase on device and model, further
+`Device` / `Data` scheme of tests/mctsdevice.py: decisions of driven simulations, a rebase on device and model, further
 simulations on the rebased trees and a second rebase -- so `mcts_select`, `mcts_backup` and `mcts_decide` are shown to accept rebased
 trees -- then the corner cases and hand-broken forests of tests/test_mctsreuse_model.py, a captured rebase + `copy_envs` pair, the
 argument checks and `mcts_forest(cap=...)`.  A rebased tree is compared on the nodes below its new n_nodes (the entries past them mean
@@ -12,123 +12,10 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-from mctsmodel import FIELDS, Forest, backup, check_invariants, root  # noqa: E402
-from mctsreuse_model import carried_child, rebase, select  # noqa: E402
-from mctssample_model import decide_most, decide_sampled  # noqa: E402
-from test_gpu_mcts_kernels import C, Data, Device, bits  # noqa: E402
+from mctsdevice import Data, Device, drive, rebase_both, simulate, upload  # noqa: E402
+from mctsmodel import FIELDS  # noqa: E402
+from mctssample_model import decide_most  # noqa: E402
 from test_mctsreuse_model import chain_forest, corner_forests, interleaving, random_forest  # noqa: E402
-
-NODE_FIELDS = ("parent", "reward", "value", "visits", "wsum", "terminal", "child", "prior")
-
-
-def expect_rebased(dev, model, touched, label):
-    """Device forest against the model's: tree m on its nodes below n_nodes where `touched[m]`, in full elsewhere."""
-    torch.cuda.synchronize()
-    np.testing.assert_array_equal(dev.n_nodes.cpu().numpy(), model.n_nodes, err_msg=f"{label}: n_nodes")
-    for name in NODE_FIELDS:
-        got, want = getattr(dev, name).cpu().numpy(), getattr(model, name)
-        assert got.dtype == want.dtype and got.shape == want.shape, (label, name)
-        for m in range(model.M):
-            k = int(model.n_nodes[m]) if touched[m] else model.cap
-            assert bits(got[m, :k]).tobytes() == bits(want[m, :k]).tobytes(), f"{label}: {name} of tree {m}"
-
-
-def upload(model):
-    from qiskit_gym_amd.collector import mcts_forest
-
-    dev = mcts_forest(model.M, 1, model.A, "cuda", cap=model.cap)
-    for name in FIELDS:
-        getattr(dev, name).copy_(torch.as_tensor(getattr(model, name)))
-    return dev
-
-
-def rebase_both(dev, model, move, finished, label):
-    """One rebase on the device forest and on the model; compares and returns env_src."""
-    from qiskit_gym_amd.collector import mcts_rebase
-
-    touched = [not (finished is not None and finished[m]) and carried_child(model, m, int(move[m])) is not None for m in range(model.M)]
-    env_src = torch.full((model.M * model.cap,), -7, dtype=torch.int32, device="cuda")
-    out = mcts_rebase(dev, torch.as_tensor(np.asarray(move, dtype=np.int32)).cuda(),
-                      None if finished is None else torch.as_tensor(np.asarray(finished, dtype=np.uint8)).cuda(), env_src)
-    assert out is env_src
-    want = rebase(model, move, finished)
-    expect_rebased(dev, model, touched, label)
-    np.testing.assert_array_equal(env_src.cpu().numpy(), want, err_msg=f"{label}: env_src")
-    # what the model left past n_nodes is not what the device left there: from here on the model holds the device's
-    for name in NODE_FIELDS:
-        setattr(model, name, getattr(dev, name).cpu().numpy().copy())
-    return want, touched
-
-
-def simulate(dev, data, model, finished, sims, label):
-    """`sims` select / backup pairs on device and model, compared after each; returns the refused simulations."""
-    M, A = model.M, model.A
-    refused = 0
-    for s in range(sims):
-        logp, values, reward, done = data.rows()
-        dev.load(logp, values, reward, done)
-        dev.pair()
-        torch.cuda.synchronize()
-        want = select(model, C, finished)
-        for name, g, w in zip(("src", "dst", "act", "leaf"), (p.cpu().numpy() for p in dev.picked), want):
-            np.testing.assert_array_equal(g, w, err_msg=f"{label} simulation {s}: {name}")
-        src, dst, act, leaf = want
-        new_prior, dev_prior = np.zeros((M, A), dtype=np.float32), dev.forest.prior.cpu().numpy()
-        for m in np.nonzero(act < A)[0]:
-            new_prior[m] = dev_prior[m, leaf[m]]
-        backup(model, src, dst, act, leaf, new_prior, values, reward, done)
-        expect_rebased(dev.forest, model, [True] * M, f"{label} simulation {s}")
-        refused += int(((leaf < 0) & (finished == 0)).sum())
-    return refused
-
-
-def drive(M, cap, A, rounds, quantised=False):
-    """`rounds`: the simulations before each rebase.  Returns what was seen."""
-    from qiskit_gym_amd.collector import mcts_decide
-
-    ld = (A + 3) // 4 * 4 + 4
-    data, dev, model = Data(M, A, ld, 77 + M + cap + A, quantised), Device(M, cap - 1, A, ld), Forest(M, cap - 1, A)
-    finished = np.zeros(M, dtype=np.uint8)
-    if M > 2:
-        finished[2] = 1
-    dev.finished.copy_(torch.as_tensor(finished))
-    logp, values, _, _ = data.rows()
-    dev.load(logp, values, done=np.zeros(M, dtype=np.uint8))
-    dev.root(True)
-    torch.cuda.synchronize()
-    root(model, dev.forest.prior.cpu().numpy()[:, 0, :], values, np.zeros(M, dtype=np.uint8))
-    seen = {"kept": 0, "dropped": 0, "refused": 0, "untouched": 0}
-    for r, sims in enumerate(rounds):
-        seen["refused"] += simulate(dev, data, model, finished, sims, f"round {r}")
-        sizes = model.n_nodes.copy()
-        if r % 2 == 0:  # the most visited action; else one drawn from the counts
-            move = decide_most(model, finished)
-            got = mcts_decide(dev.forest, finished=dev.finished).cpu().numpy()
-        else:
-            move = decide_sampled(model, 9, r, finished)
-            got = mcts_decide(dev.forest, sample=True, seed=9, counter=r, finished=dev.finished).cpu().numpy()
-        np.testing.assert_array_equal(got, move, err_msg=f"round {r}: the decision on a rebased tree")
-        if M > 3 and r == 0:
-            move[3] = A  # a live tree with no move: nothing to carry
-        env_src, touched = rebase_both(dev.forest, model, move, finished, f"round {r}")
-        check_invariants(_trees(model, touched))
-        for m in np.nonzero(touched)[0]:
-            kept = env_src[m * cap : m * cap + model.n_nodes[m]] - m * cap
-            seen["kept"] += len(kept)
-            seen["dropped"] += int(sizes[m]) - len(kept)
-        seen["untouched"] += M - int(np.sum(touched))
-        if r == 0 and M > 4:  # the real envs move on: one more tree ends before the second rebase
-            finished[M - 1] = 1
-            dev.finished.copy_(torch.as_tensor(finished))
-    return seen
-
-
-def _trees(f, rows):
-    rows = np.nonzero(rows)[0]
-    g = Forest(len(rows), f.cap - 1, f.A)
-    for name in FIELDS:
-        setattr(g, name, getattr(f, name)[rows].copy())
-    return g
 
 
 @pytest.mark.parametrize("M,cap,A,rounds", [(1, 2, 1, (1, 1, 1)), (5, 7, 3, (4, 4, 8)), (3, 130, 5, (100, 70, 40)), (2, 300, 256, (200, 150)),

@@ -22,9 +22,39 @@ from test_gpu_synthesis import replay  # noqa: E402
 from test_mctsreuse_model import PINNED, PINNED_STATS  # noqa: E402
 
 NODE_FIELDS = tuple(name for name in FIELDS if name != "n_nodes")
+
+
+def clifford7_case():
+    """CliffordGym on the line of 7 qubits: 71 actions, so the rebase moves its rows in two slices of 64 actions, 8 rows per trip (every
+    other case here has fewer than 64: one slice).  No trained policy of that size ships: a seeded random one.  The recorded
+    log-probabilities are the model's input, so any policy serves; it finds few answers, so the identity comes twice."""
+    import qiskit_gym_amd.envs as envs
+    from oracle import OracleEnv
+    from qiskit_gym_amd.collector import BasicPolicy
+    from util import line_gateset
+
+    n = 7
+    gs = line_gateset("clifford", n)
+    assert len(gs) == 71
+    gym = envs.CliffordGym(n, gs, max_depth=6)
+    torch.manual_seed(7)
+    policy = BasicPolicy(4 * n * n, len(gs))
+    rng = np.random.default_rng(7)
+    states = []
+    for k in range(5):
+        d = 1 + k % 3
+        env = OracleEnv("clifford", n, gs, add_inverts=0, add_perms=0, track_solution=0, difficulty=d, max_depth=6)
+        env.reset_with(rng.integers(0, len(gs), size=d))
+        states.append(env.get_state().tolist())
+    solved = OracleEnv("clifford", n, gs, add_inverts=0, add_perms=0).get_state().tolist()
+    return gym, policy, states + [solved, solved], None
+
+
 # (case, S or None: deterministic, N, fast, mcts_nodes)
 CALLS = ([(case, None, 4, None, None) for case in CASES] + [(case, 3, 4, None, None) for case in CASES]
          + [("clifford-3q", None, 16, True, None), ("clifford-3q", 2, 16, True, None), ("pinned", None, PINNED["N"], None, PINNED["N"] + 1)])
+CASES = dict(CASES, **{"clifford-7q": clifford7_case})
+CALLS += [("clifford-7q", None, 16, None, None), ("clifford-7q", 3, 16, None, None)]
 STATS = {"mcts", "targets", "steps", "solved", "mean_gates", "nodes", "kernels", "reuse", "capacity", "carried", "refused"}
 
 

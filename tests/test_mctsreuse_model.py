@@ -331,6 +331,25 @@ def test_corner_cases_by_hand():
     assert rebase(g, move).reshape(g.M, g.cap)[3].tolist()[:4] == [3 * g.cap + j for j in (1, 3, 5, 6)] and g.n_nodes[3] == 4
 
 
+def test_the_kept_nodes_without_the_walks_are_those_of_the_walks():
+    """`rebase` settles a node by its parent's answer; the rule walks every chain.  The same nodes on the corner cases (broken links, chains
+    that pass below c), on random trees under every child of the root, on chains, and on parents drawn without any rule."""
+    from mctsreuse_model import kept_nodes, kept_nodes_by_walk
+
+    compared = 0
+    corners, move, _, _ = corner_forests()
+    wild = random_forest(3, 200, 4, 180, 5)
+    wild.parent[:, 1:] = np.random.default_rng(6).integers(-3, 200, size=(3, 199))
+    for f, moves in ((corners, [int(a) for a in move]), (random_forest(3, 300, 7, 280, 2), None), (chain_forest(2, 70, 70), None), (wild, None)):
+        for m in range(f.M):
+            for a in range(f.A) if moves is None else [moves[m]]:
+                c = carried_child(f, m, a)
+                if c is not None:
+                    assert kept_nodes(f, m, c) == kept_nodes_by_walk(f, m, c), (m, a)
+                    compared += 1
+    assert compared > 20
+
+
 def chain_forest(M, cap, n):
     """A = 1: every tree is a chain of n nodes."""
     f = Forest(M, cap - 1, 1)
