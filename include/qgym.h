@@ -35,7 +35,8 @@ extern "C" {
  * 3: + qg_vec_track_dense, qg_comm_p2p_reset, qg_plan_query, qg_vec_reset_done_step, qg_env_pool_clear, qg_vec_copy_envs, qg_beam_select,
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
  *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance, qg_mcts_forest_bytes,
- *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide, qg_mcts_rebase, qg_search_plan_query (additions only) */
+ *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide, qg_mcts_rebase, qg_search_plan_query, qg_mcts_select_many,
+ *      qg_mcts_backup_many (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -558,7 +559,42 @@ int qg_beam_advance(uint64_t n_groups, uint32_t width, const int32_t *parent_dev
  *              A full tree has a defined meaning in qg_mcts_select: the simulation that wants to expand gets leaf = -1 and does not
  *              count.  Limits and error codes are those of qg_mcts_select; a null or misaligned move_dev or env_src_dev is
  *              QG_ERR_INVALID.  One launch, one wave per tree, plain vector loads and stores, no host reads, no synchronisation,
- *              capturable. */
+ *              capturable.
+ *   several leaves per launch   qg_mcts_select_many and qg_mcts_backup_many: k descents per tree in one launch each, so a decision of N
+ *              simulations takes ceil(N / k) rounds of launches on a leaf batch k times as large.  tests/mctsmany_model.py restates both in
+ *              numpy; results agree bit for bit.  stride >= k is the row length of the per-descent arrays: entry m*stride + i of src, dst,
+ *              act, leaf (i32[n_trees*stride]), of values, reward, done and row m*stride + i of logp belong to descent i of tree m.
+ *     qg_mcts_select_many   Per tree, n0 = n_nodes at entry.  The call keeps an OVERLAY, a copy of the tree's (visits, wsum) that starts as
+ *              the forest's, and makes descents i = 0 .. k-1 in that order.  Each is qg_mcts_select's descent -- the scores, the order of
+ *              the f32 operations, the ties, the terminal rule and the range checks (children against n0) -- with three differences:
+ *                overlay        visits and wsum are read from the overlay.
+ *                pending edges  an edge (x, a) that an earlier descent of this call chose for expansion is no candidate, exactly like an
+ *                               action whose score is a NaN: two descents of one call never expand the same edge and no descent enters a
+ *                               node that does not exist yet.  With no candidate left at x the existing rule applies: leaf = x, act =
+ *                               num_actions, nothing is expanded, the simulation counts.
+ *                numbering      the e-th descent of the call that expands (e = 0, 1, ...) names node j = n0 + e; j >= cap refuses the
+ *                               descent as a full tree does: leaf = -1, act = num_actions, dst = n_trees*cap, src the node it stood on,
+ *                               and its edge is not pending.
+ *              After descent i every node y it stood on, the root through the node it ended on -- also when it was refused for a full
+ *              tree -- gets overlay visits[y] += 1, and every such y != 0 overlay wsum[y] = wsum[y] - virtual_loss, one f32 subtraction.
+ *              (A descent stands on no node twice, so the kernel applies this as the descent leaves each node, its scores taken.)
+ *              A failed range check ends the tree's work for the call: that descent gets leaf = -1 with src the node it stood on, and
+ *              every later descent of the tree is not made.  A descent that is not made -- after a failed check, i in [k, stride), every
+ *              entry of a tree with finished_dev[m] != 0 or n0 outside [1, cap] -- is written as src = m*cap, dst = n_trees*cap, act =
+ *              num_actions, leaf = -1, so every call writes all four arrays in full.  Nothing is written into the forest.
+ *     qg_mcts_backup_many   Per tree, for i = 0 .. k-1 in that order, the QG_MCTS_BACKUP rule of qg_mcts_backup with every check it has,
+ *              on entry m*stride + i.  n_nodes grows as the expansions are linked, so the i-th expanding entry must name the then-current
+ *              n_nodes, which qg_mcts_select_many's numbering does.  An entry that fails a check is skipped and later entries go on (an
+ *              expansion that was skipped makes the next one's j = n_nodes check fail by itself); n_nodes outside [1, cap] at entry
+ *              skips the tree.
+ *              With k = stride = 1 both calls give exactly what qg_mcts_select and qg_mcts_backup give, for any forest content and any
+ *              virtual_loss; after a select / backup pair the forest's visits of every node that existed at entry equal the overlay's
+ *              (in a tree none of whose descents was refused: a refused descent leaves virtual visits and no real ones).
+ *              Limits: 1 <= k <= stride <= 64 (the pending edges live in the lanes of the tree's wave, the overlay is qg_mcts_select's
+ *              LDS copy), virtual_loss finite and >= 0, n_trees*stride < 2^31 - 1: QG_ERR_INVALID beyond; the forest's own limits and
+ *              error codes as above.  One launch each, one wave per tree, plain vector loads and stores, no atomics, no host reads,
+ *              capturable.  In the backup a location that a later entry reads after an earlier one stored it has one lane that does
+ *              both (child[x][a]: lane a % 64; the per-node fields and the walk: lane 0). */
 typedef struct qg_mcts_forest {
     int32_t *parent;
     float *reward;
@@ -583,6 +619,11 @@ typedef enum { QG_MCTS_MOST_VISITED = 0, QG_MCTS_SAMPLE = 1 } qg_mcts_decide_mod
 int qg_mcts_decide(const qg_mcts_forest *forest, int mode, uint64_t seed, uint64_t counter, const uint8_t *finished_dev,
                    int32_t *move_dev, int32_t *counts_dev, uint64_t counts_ld, void *stream);
 int qg_mcts_rebase(const qg_mcts_forest *forest, const int32_t *move_dev, const uint8_t *finished_dev, int32_t *env_src_dev, void *stream);
+int qg_mcts_select_many(const qg_mcts_forest *forest, float c_puct, float virtual_loss, uint32_t k, uint32_t stride, const uint8_t *finished_dev,
+                        int32_t *src_dev, int32_t *dst_dev, int32_t *act_dev, int32_t *leaf_dev, void *stream);
+int qg_mcts_backup_many(const qg_mcts_forest *forest, uint32_t k, uint32_t stride, const int32_t *src_dev, const int32_t *dst_dev,
+                        const int32_t *act_dev, const int32_t *leaf_dev, const float *logp_dev, uint64_t ld, const float *values_dev,
+                        const float *reward_dev, const uint8_t *done_dev, void *stream);
 /* Twists, batched: the symmetries of the coupling map as views of the observation (Env::twists, clifford.rs:370-372; symmetry.rs:205-295).
  * For CliffordEnv, LinearFunctionEnv and PermutationEnv twist t is a pair: obs_perms[t] over the flat dense observation (rows * cols entries)
  * and act_perms[t] over the actions.  THE DEFINITION, proved on the oracle env for every kind, twist and action (tests/test_twist_views.py):

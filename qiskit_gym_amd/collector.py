@@ -39,7 +39,7 @@ import torch.nn as nn
 
 from . import _lib
 from .policy_kernels import (_DT, BasicPolicy, FirstLayer, PolicyOperands, _linear_relu, _logp_outputs, _twist_operands, beam_advance, beam_merge, beam_seen, beam_select,  # noqa: F401
-                             embed, embed_words, expand_packed, first_layer, gae, head_logp, head_sample, mcts_backup, mcts_decide, mcts_forest, mcts_rebase, mcts_select, mid_head_logp,
+                             embed, embed_words, expand_packed, first_layer, gae, head_logp, head_sample, mcts_backup, mcts_backup_many, mcts_decide, mcts_forest, mcts_rebase, mcts_select, mcts_select_many, mid_head_logp,
                              mid_head_sample, mid_head_sample_step, pack_embed_words, pack_embedding, pack_first, pack_head, pack_mid, run_first_layer, sample_actions,
                              twist_expand_packed, twist_pack_words, untwist_actions)
 from .vec import VecEnv, _stream_ptr

@@ -4,6 +4,9 @@
 // qg_mcts_rebase (between two decisions: the chosen move's subtree becomes the tree, in place).  The rules are stated in include/qgym.h;
 // tests/mctsmodel.py, tests/mctssample_model.py and tests/mctsreuse_model.py restate them in numpy and the kernels agree with them bit for bit.
 //
+// qg_mcts_select_many and qg_mcts_backup_many are the first two for k descents per tree and launch (virtual visits between the descents);
+// tests/mctsmany_model.py restates them.
+//
 // The forest is a struct of plain arrays (qg_mcts_forest): per (tree, node) parent, reward, value, visits, wsum, terminal; per (tree, node,
 // action) child and prior; per tree n_nodes.  One WAVE per tree in every kernel, several trees per workgroup; a wave owns its tree for the
 // whole launch: plain vector loads and stores, no atomics, no barrier between waves.
@@ -231,6 +234,217 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_kernel(const Back
         y = (uint32_t)up;
     }
     if (y == 0) f.visits[base] += 1;
+}
+
+struct SelectManyArgs {
+    qg_mcts_forest f;
+    const uint8_t *finished;  // or nullptr
+    int32_t *src, *dst, *act, *leaf;
+    float C, vloss;
+    uint32_t waves, k, stride;
+};
+
+// k descents per tree in one launch, one after another on the tree's statistics (qg_mcts_select_many).  The LDS copy of (visits, wsum) that
+// mcts_select_kernel makes is the overlay: as a descent leaves a node, lane 0 adds the virtual visit there (and takes virtual_loss from its
+// wsum, the root's excepted) -- LDS keeps a wave's accesses in order, so the next read of any lane sees it.  The edges chosen for expansion
+// so far live in registers, pair e in lane e (stride <= 64): at a node that some pair names, the pairs are read lane by lane and the lane
+// that holds the action drops it from its candidates.  The four outputs of descent i are kept in lane i and stored once, at the end, so a
+// call writes entries 0 .. stride - 1 of every array.  Nothing is written into the forest.
+__global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_select_many_kernel(const SelectManyArgs a) {
+    extern __shared__ uint2 mcts_lds[];  // [waves][cap]: (visits, bits of wsum) of the wave's tree, with this call's virtual visits
+    const qg_mcts_forest &f = a.f;
+    const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
+    const uint64_t m = (uint64_t)blockIdx.x * a.waves + wave;
+    if (m >= f.n_trees) return;  // (the whole wave)
+    const uint32_t cap = f.cap, A = f.num_actions;
+    const uint64_t base = m * cap;
+    const int32_t none = (int32_t)(f.n_trees * cap);
+    uint2 *st = mcts_lds + (size_t)wave * cap;
+
+    // lane i: the outputs of descent i -- a refused one until it is made
+    int32_t o_src = (int32_t)base, o_dst = none, o_act = (int32_t)A, o_leaf = -1;
+    int32_t pend_x = -1;    // lane e: the e-th edge chosen for expansion, (node, action)
+    uint32_t pend_a = 0;
+    uint32_t grown = 0;     // edges chosen so far
+    const uint32_t n = (uint32_t)f.n_nodes[m];
+    bool run = !(a.finished && a.finished[m] != 0) && n >= 1 && n <= cap;
+    if (run) {
+        for (uint32_t j = lane; j < n; j += QG_WAVE) st[j] = make_uint2((uint32_t)f.visits[base + j], __float_as_uint(f.wsum[base + j]));
+        __builtin_amdgcn_wave_barrier();
+    }
+    for (uint32_t i = 0; i < a.k && run; ++i) {
+        uint32_t x = 0;
+        int32_t leaf = -1, act = (int32_t)A, dst = none;
+        for (uint32_t level = 0; level < cap; ++level) {
+            const uint64_t row = (base + x) * A;
+            const bool term = f.terminal[base + x] != 0;
+            const float vx = f.value[base + x];
+            int32_t c[4];
+            float p[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t ac = lane + QG_WAVE * k;
+                c[k] = ac < A ? f.child[row + ac] : -1;
+                p[k] = ac < A ? f.prior[row + ac] : 0.0f;
+            }
+            const uint2 sx = st[x];  // x < n
+            __builtin_amdgcn_wave_barrier();  // every lane has read the node's pair before lane 0 changes it
+            // the descent stands on x once, and everything it reads of x it has read: the virtual visit
+            const uint2 after = make_uint2(sx.x + 1u, x != 0 ? __float_as_uint(__uint_as_float(sx.y) - a.vloss) : sx.y);
+            if (term) {  // the descent ends on a terminal node: nothing is expanded
+                if (lane == 0) st[x] = after;
+                leaf = (int32_t)x;
+                break;
+            }
+            // the edges of x that an earlier descent of this call chose: no candidates
+            uint32_t taken = 0;
+            for (uint64_t hit = __ballot(pend_x == (int32_t)x); hit; hit &= hit - 1) {  // at most 64 pairs
+                const uint32_t pa = (uint32_t)__shfl((int)pend_a, (int)__builtin_ctzll(hit), 64);
+                if ((pa & (QG_WAVE - 1)) == lane) taken |= 1u << (pa >> 6);
+            }
+            const float sq = __builtin_sqrtf((float)(int32_t)sx.x);
+            uint64_t key = 0;
+            bool bad = false;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t ac = lane + QG_WAVE * k;
+                if (ac >= A || ((taken >> k) & 1u)) continue;
+                float q = vx;
+                int32_t na = 0;
+                if (c[k] >= 0) {
+                    if ((uint32_t)c[k] >= n || (uint32_t)c[k] <= x) {  // no node of this tree, or no step down
+                        bad = true;
+                        continue;
+                    }
+                    const uint2 s = st[c[k]];
+                    na = (int32_t)s.x;
+                    q = __uint_as_float(s.y) / (float)na;
+                }
+                const float u = ((a.C * p[k]) * sq) / (float)(1 + na);
+                const uint32_t o = mcts_order(q + u);
+                const uint64_t kk = ((uint64_t)o << 32) | (uint64_t)(0xFFFFFFFFu - ac);
+                if (o && kk > key) key = kk;
+            }
+            if (__ballot(bad)) {  // leaf stays -1, and the tree's work ends here: no later descent is made
+                run = false;
+                break;
+            }
+            __builtin_amdgcn_wave_barrier();  // the children's pairs are read
+            if (lane == 0) st[x] = after;
+            const uint64_t top = mcts_wave_max(key);
+            if (top == 0) {  // no candidate left: nothing to expand
+                leaf = (int32_t)x;
+                break;
+            }
+            const uint32_t best = 0xFFFFFFFFu - (uint32_t)top, k = best >> 6;
+            const int32_t mine = k == 0 ? c[0] : k == 1 ? c[1] : k == 2 ? c[2] : c[3];
+            const int32_t next = __shfl(mine, (int)(best & (QG_WAVE - 1)), 64);
+            if (next < 0) {  // an unexpanded edge: the new node is n_nodes + the edges chosen before, if the tree has room
+                if (n + grown < cap) {  // (grown <= 64: no overflow)
+                    leaf = (int32_t)(n + grown);
+                    dst = (int32_t)(base + n + grown);
+                    act = (int32_t)best;
+                    if (lane == grown) {
+                        pend_x = (int32_t)x;
+                        pend_a = best;
+                    }
+                    grown += 1;
+                }
+                break;
+            }
+            x = (uint32_t)next;  // x < next < n: at most cap - 1 steps down
+        }
+        __builtin_amdgcn_wave_barrier();  // lane 0's virtual visits before the next descent's reads
+        if (lane == i) {
+            o_src = (int32_t)(base + x);
+            o_dst = dst;
+            o_act = act;
+            o_leaf = leaf;
+        }
+    }
+    if (lane < a.stride) {
+        const uint64_t at = m * a.stride + lane;
+        a.src[at] = o_src;
+        a.dst[at] = o_dst;
+        a.act[at] = o_act;
+        a.leaf[at] = o_leaf;
+    }
+}
+
+struct BackupManyArgs {
+    qg_mcts_forest f;
+    const int32_t *src, *dst, *act, *leaf;
+    const float *logp, *values, *reward;
+    const uint8_t *done;
+    uint64_t ld;
+    uint32_t k, stride;
+};
+
+// mcts_backup_kernel's QG_MCTS_BACKUP body k times per tree, entry m * stride + i in turn, n_nodes in a register (qg_mcts_backup_many).
+// A later entry reads what an earlier one of the same launch stored, so every such location has ONE lane that stores and loads it, and what
+// that lane reads is handed to the others by a lane read: child[x][a] belongs to lane a % 64 (the row of a new node and the link into it),
+// every per-node field and the walk to lane 0.  A lane's own stores are in program order before its loads.
+__global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_many_kernel(const BackupManyArgs a) {
+    const qg_mcts_forest &f = a.f;
+    const uint32_t lane = threadIdx.x & (QG_WAVE - 1), wave = threadIdx.x >> 6;
+    const uint64_t m = (uint64_t)blockIdx.x * MCTS_WAVES + wave;
+    if (m >= f.n_trees) return;  // (the whole wave)
+    const uint32_t cap = f.cap, A = f.num_actions;
+    const uint64_t base = m * cap;
+    const uint32_t n0 = (uint32_t)f.n_nodes[m];
+    if (n0 < 1 || n0 > cap) return;  // no simulation that counts
+    uint32_t n = n0;
+    for (uint32_t i = 0; i < a.k; ++i) {
+        const uint64_t e = m * a.stride + i;
+        const int32_t leaf = a.leaf[e];
+        if (leaf < 0) continue;
+        const uint32_t ac = (uint32_t)a.act[e];
+        const bool expand = ac < A;
+        float g = 0.0f;  // the leaf's value: lane 0's
+        if (expand) {
+            const int64_t x = (int64_t)a.src[e] - (int64_t)base, j = (int64_t)a.dst[e] - (int64_t)base;
+            // the new node is n_nodes, below cap, the child of a node of this tree by an edge that has none
+            if (x < 0 || x >= (int64_t)n || j != (int64_t)n || j >= (int64_t)cap || leaf != (int32_t)j) continue;
+            const uint32_t owner = ac & (QG_WAVE - 1);
+            int32_t *edge = f.child + (base + (uint64_t)x) * A + ac;
+            const int32_t had = __shfl(lane == owner ? *edge : 0, (int)owner, 64);
+            if (had != -1) continue;
+            const bool term = a.done[e] != 0;
+            g = term ? 0.0f : a.values[e];
+            mcts_open_node(f, base + (uint64_t)j, a.logp + e * a.ld, lane);
+            if (lane == owner) *edge = (int32_t)j;
+            if (lane == 0) {
+                f.parent[base + j] = (int32_t)x;
+                f.reward[base + j] = a.reward[e];
+                f.value[base + j] = g;
+                f.visits[base + j] = 0;
+                f.wsum[base + j] = 0.0f;
+                f.terminal[base + j] = term ? 1 : 0;
+            }
+            n += 1;
+        } else if ((uint32_t)leaf >= n) {
+            continue;
+        }
+        if (lane == 0) {
+            if (!expand) g = f.value[base + (uint32_t)leaf];
+            // the walk, on the lane that stored every field it loads: one trip per level, every address is y's
+            uint32_t y = (uint32_t)leaf;
+            bool whole = true;
+            for (uint32_t step = 0; step < cap && y != 0; ++step) {
+                const int32_t up = f.parent[base + y];
+                g = f.reward[base + y] + g;
+                f.visits[base + y] += 1;
+                f.wsum[base + y] += g;
+                if (up < 0 || (uint32_t)up >= y) {  // no step up: the root is not counted
+                    whole = false;
+                    break;
+                }
+                y = (uint32_t)up;
+            }
+            if (whole && y == 0) f.visits[base] += 1;
+        }
+    }
+    if (lane == 0 && n != n0) f.n_nodes[m] = (int32_t)n;
 }
 
 struct DecideArgs {
@@ -554,6 +768,70 @@ extern "C" int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int3
     a.mode = mode;
     const dim3 grid((unsigned)((forest->n_trees + MCTS_WAVES - 1) / MCTS_WAVES)), block(64u * MCTS_WAVES);
     hipLaunchKernelGGL(mcts_backup_kernel, grid, block, 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}
+
+static int mcts_check_many(const qg_mcts_forest *f, uint32_t k, uint32_t stride, const char *who) {
+    if (k < 1 || k > stride || stride > plan::MCTS_MAX_LEAVES)
+        return set_error(QG_ERR_INVALID, "%s: 1 <= k <= stride <= %u (a descent per lane of the tree's wave)", who, plan::MCTS_MAX_LEAVES);
+    if (f->n_trees * stride >= 0x7FFFFFFFull) return set_error(QG_ERR_INVALID, "%s: n_trees * stride must stay below 2^31 - 1", who);
+    return QG_OK;
+}
+
+extern "C" int qg_mcts_select_many(const qg_mcts_forest *forest, float c_puct, float virtual_loss, uint32_t k, uint32_t stride, const uint8_t *finished_dev,
+                                   int32_t *src_dev, int32_t *dst_dev, int32_t *act_dev, int32_t *leaf_dev, void *stream) {
+    if (const int rc = mcts_check_forest(forest, "mcts_select_many")) return rc;
+    if (const int rc = mcts_check_many(forest, k, stride, "mcts_select_many")) return rc;
+    if (!(virtual_loss >= 0.0f) || virtual_loss > 3.402823466e+38f) return set_error(QG_ERR_INVALID, "mcts_select_many: virtual_loss must be finite and >= 0");
+    if (!src_dev || !dst_dev || !act_dev || !leaf_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4))
+        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (forest->n_trees == 0) return QG_OK;
+    SelectManyArgs a;
+    a.f = *forest;
+    a.finished = finished_dev;
+    a.src = src_dev;
+    a.dst = dst_dev;
+    a.act = act_dev;
+    a.leaf = leaf_dev;
+    a.C = c_puct;
+    a.vloss = virtual_loss;
+    a.k = k;
+    a.stride = stride;
+    a.waves = plan::mcts_trees_per_workgroup(forest->cap);  // the overlay is qg_mcts_select's LDS copy: the same trees per workgroup
+    const dim3 grid((unsigned)((forest->n_trees + a.waves - 1) / a.waves)), block(64u * a.waves);
+    hipLaunchKernelGGL(mcts_select_many_kernel, grid, block, (size_t)a.waves * forest->cap * sizeof(uint2), (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return QG_OK;
+}
+
+extern "C" int qg_mcts_backup_many(const qg_mcts_forest *forest, uint32_t k, uint32_t stride, const int32_t *src_dev, const int32_t *dst_dev,
+                                   const int32_t *act_dev, const int32_t *leaf_dev, const float *logp_dev, uint64_t ld, const float *values_dev,
+                                   const float *reward_dev, const uint8_t *done_dev, void *stream) {
+    if (const int rc = mcts_check_forest(forest, "mcts_backup_many")) return rc;
+    if (const int rc = mcts_check_many(forest, k, stride, "mcts_backup_many")) return rc;
+    if (!logp_dev || !values_dev || !src_dev || !dst_dev || !act_dev || !leaf_dev || !reward_dev || !done_dev) return set_error(QG_ERR_INVALID, "null argument");
+    if (ld < forest->num_actions) return set_error(QG_ERR_INVALID, "bad shape: ld >= num_actions");
+    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4) || ((uintptr_t)logp_dev % 4) ||
+        ((uintptr_t)values_dev % 4) || ((uintptr_t)reward_dev % 4))
+        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (forest->n_trees == 0) return QG_OK;
+    BackupManyArgs a;
+    a.f = *forest;
+    a.src = src_dev;
+    a.dst = dst_dev;
+    a.act = act_dev;
+    a.leaf = leaf_dev;
+    a.logp = logp_dev;
+    a.values = values_dev;
+    a.reward = reward_dev;
+    a.done = done_dev;
+    a.ld = ld;
+    a.k = k;
+    a.stride = stride;
+    const dim3 grid((unsigned)((forest->n_trees + MCTS_WAVES - 1) / MCTS_WAVES)), block(64u * MCTS_WAVES);
+    hipLaunchKernelGGL(mcts_backup_many_kernel, grid, block, 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return QG_OK;
 }

@@ -421,6 +421,7 @@ constexpr uint32_t MCTS_WAVES = 4;             // trees per workgroup (fewer whe
 constexpr uint32_t MCTS_MAX_ACTIONS = 256;     // four actions per lane
 constexpr uint32_t MCTS_MAX_CAP = 8192;        // 8 bytes of LDS per node, one tree per workgroup at the limit
 constexpr uint32_t MCTS_LDS_NODE_BYTES = 8;    // select: (visits, wsum); rebase: (parent, new index)
+constexpr uint32_t MCTS_MAX_LEAVES = 64;       // descents per tree and launch of qg_mcts_select_many: lane e keeps the e-th pending edge
 // trees (waves) per workgroup of qg_mcts_select and qg_mcts_rebase: those whose LDS tables fit one workgroup; >= 1 by MCTS_MAX_CAP
 constexpr uint32_t mcts_trees_per_workgroup(uint32_t cap) {
     return SEARCH_LDS_BYTES / (cap * MCTS_LDS_NODE_BYTES) < MCTS_WAVES ? SEARCH_LDS_BYTES / (cap * MCTS_LDS_NODE_BYTES) : MCTS_WAVES;

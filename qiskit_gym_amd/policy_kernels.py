@@ -265,6 +265,78 @@ def mcts_backup(forest: MctsForest, logp: torch.Tensor, values: torch.Tensor, re
     return forest
 
 
+MCTS_MAX_LEAVES = 64  # descents per tree and launch: one lane of the tree's wave per pending edge
+
+
+def _mcts_many_shape(name: str, forest: MctsForest, K, k):
+    """(K, k) as ints after the checks both many-descent wrappers share: 1 <= k <= K <= 64, M * K within 32-bit indices."""
+    if not isinstance(forest, MctsForest):
+        raise TypeError(f"{name}: forest must come from mcts_forest")
+    K = int(K)
+    k = K if k is None else int(k)
+    if not 1 <= k <= K <= MCTS_MAX_LEAVES:
+        raise ValueError(f"{name}: 1 <= k <= K <= {MCTS_MAX_LEAVES}, got k={k}, K={K}")
+    if forest.M * K >= 2 ** 31 - 1:
+        raise ValueError(f"{name}: {forest.M} trees of {K} descents are too many for 32-bit indices")
+    return K, k
+
+
+def _mcts_many_vectors(name: str, forest: MctsForest, K: int, items):
+    """`_mcts_vectors` for the per-descent arrays: contiguous [M * K]."""
+    for nm, t, dt in items:
+        if t is not None and (t.dtype != dt or t.dim() != 1 or t.numel() != forest.M * K or not t.is_contiguous() or t.device != forest.parent.device):
+            raise ValueError(f"{name}: {nm} must be a contiguous [{forest.M * K}] {dt} tensor on the forest's device")
+
+
+def mcts_select_many(forest: MctsForest, C: float, K: int, k: Optional[int] = None, virtual_loss: float = 0.0, finished: Optional[torch.Tensor] = None,
+                     src: Optional[torch.Tensor] = None, dst: Optional[torch.Tensor] = None, act: Optional[torch.Tensor] = None,
+                     leaf: Optional[torch.Tensor] = None):
+    """k PUCT descents per tree in one launch (`qg_mcts_select_many`), made one after another on a copy of the tree's visits and wsum: each
+    is `mcts_select`'s descent, leaves a virtual visit on every node of its path (and takes `virtual_loss` from the wsum of every node but
+    the root), so the next one goes elsewhere; an edge an earlier descent of the call chose for expansion is no candidate, and the e-th
+    expansion names node n_nodes + e (refused, leaf = -1, where the tree is full).  K is the row length of the outputs, 1 <= k <= K <= 64,
+    k=None: K.  Returns int32 [M * K] each, entry m * K + i for descent i of tree m: (src, dst, act, leaf) as `mcts_select` gives them;
+    entries i >= k and those of `finished` trees are refused descents.  The forest is only read.  Preallocated outputs may be passed."""
+    K, k = _mcts_many_shape("mcts_select_many", forest, K, k)
+    if not float(C) > 0.0:
+        raise ValueError("mcts_select_many: C must be positive")
+    vl = float(virtual_loss)
+    if not (vl >= 0.0 and vl < float("inf")):
+        raise ValueError("mcts_select_many: virtual_loss must be finite and at least 0")
+    dev, i32 = forest.parent.device, torch.int32
+    if finished is not None and finished.dtype == torch.bool:
+        finished = finished.view(torch.uint8)
+    src, dst, act, leaf = (torch.empty(forest.M * K, dtype=i32, device=dev) if t is None else t for t in (src, dst, act, leaf))
+    _mcts_vectors("mcts_select_many", forest, (("finished", finished, torch.uint8),))
+    _mcts_many_vectors("mcts_select_many", forest, K, (("src", src, i32), ("dst", dst, i32), ("act", act, i32), ("leaf", leaf, i32)))
+    _lib.check(_lib.load().qg_mcts_select_many(forest._c, float(C), vl, k, K, finished.data_ptr() if finished is not None else None, src.data_ptr(),
+                                               dst.data_ptr(), act.data_ptr(), leaf.data_ptr(), _stream_ptr()))
+    return src, dst, act, leaf
+
+
+def mcts_backup_many(forest: MctsForest, K: int, logp: torch.Tensor, values: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
+                     src: torch.Tensor, dst: torch.Tensor, act: torch.Tensor, leaf: torch.Tensor, k: Optional[int] = None) -> MctsForest:
+    """The other half of a round (`qg_mcts_backup_many`), in place on `forest`: per tree `mcts_backup`'s rule for entries m * K + i,
+    i = 0 .. k - 1 in that order -- link the new node where act < A, carry the leaf's value to the root -- with n_nodes growing as the
+    nodes are linked.  logp: f32 [M * K, >= A] with unit column stride; values, reward f32 [M * K]; done uint8 / bool [M * K]; src, dst,
+    act, leaf `mcts_select_many`'s outputs.  Entries with leaf < 0, and those that fail a check, are skipped."""
+    K, k = _mcts_many_shape("mcts_backup_many", forest, K, k)
+    R, A, dev, i32, f32 = forest.M * K, forest.A, forest.parent.device, torch.int32, torch.float32
+    if logp is None or logp.dtype != f32 or logp.dim() != 2 or logp.shape[0] != R or logp.shape[1] < A or logp.device != dev or (
+            logp.stride(1) != 1 and logp.shape[1] > 1) or (R > 1 and logp.stride(0) < A):
+        raise ValueError("mcts_backup_many: logp must be f32 [M * K, >= A] with unit column stride on the forest's device")
+    if done is not None and done.dtype == torch.bool:
+        done = done.view(torch.uint8)
+    if any(t is None for t in (values, reward, done, src, dst, act, leaf)):
+        raise ValueError("mcts_backup_many: values, reward, done, src, dst, act and leaf are required")
+    _mcts_many_vectors("mcts_backup_many", forest, K, (("values", values, f32), ("reward", reward, f32), ("done", done, torch.uint8), ("src", src, i32),
+                                                       ("dst", dst, i32), ("act", act, i32), ("leaf", leaf, i32)))
+    _lib.check(_lib.load().qg_mcts_backup_many(forest._c, k, K, src.data_ptr(), dst.data_ptr(), act.data_ptr(), leaf.data_ptr(), logp.data_ptr(),
+                                               logp.stride(0) if R > 1 else logp.shape[1], values.data_ptr(), reward.data_ptr(), done.data_ptr(),
+                                               _stream_ptr()))
+    return forest
+
+
 def mcts_decide(forest: MctsForest, sample: bool = False, seed: int = 0, counter: int = 0, finished: Optional[torch.Tensor] = None,
                 move: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The decision after a decision's simulations (`qg_mcts_decide`), one launch; the forest is only read.  Per tree the visit counts of

@@ -51,8 +51,8 @@ import torch
 
 from . import _lib
 from .envs.gyms import ROTATION_MARKER
-from .policy_kernels import (MCTS_MAX_CAP, MCTS_MAX_FOREST_BYTES, BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
-                             mcts_backup, mcts_decide, mcts_forest, mcts_rebase, mcts_select, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
+from .policy_kernels import (MCTS_MAX_CAP, MCTS_MAX_FOREST_BYTES, MCTS_MAX_LEAVES, BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
+                             mcts_backup, mcts_backup_many, mcts_decide, mcts_forest, mcts_rebase, mcts_select, mcts_select_many, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
 from .vec import VecEnv
 
 
@@ -222,7 +222,8 @@ class BatchedSynthesis:
         choice depends on the batch size) or "mcts" (the pool of targets * (N + 1) node envs, the leaf batch and the real batch of one env per
         target, again all with the same constructor arguments) or "mcts-sampled" (the same three for targets * searches trees) or "mcts-reuse" /
         "mcts-sampled-reuse" (`reuse_tree`: the leaf batch, TWO pools of trees * cap node envs that take turns as source and destination of
-        the copy between two decisions, and the real batch).  One batch shape at a time per kind: the handles own device memory."""
+        the copy between two decisions, and the real batch); each of the four again with "-many" appended (`mcts_leaves=K`: the
+        same handles with a leaf batch of trees * K envs).  One batch shape at a time per kind: the handles own device memory."""
         key = (*batches, perms)  # add_perms: twists() only, the env steps alike
         held = self._held.get(kind)
         if held is not None and held.key != key:
@@ -390,7 +391,8 @@ class BatchedSynthesis:
             self.last_stats.update(bound=bound, bounded=int(bounded.sum()))
         return out
 
-    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool, searches: Optional[int] = None, cap: Optional[int] = None):
+    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool, searches: Optional[int] = None, cap: Optional[int] = None,
+                     K: int = 1, vloss: float = 0.0):
         """The search of `solve(num_mcts_searches=N)` on the handles of `held`: the leaf batch, which is all the forward object reads, the pool
         (node j of tree m is env m * (N + 1) + j) and the real envs.  Per decision one forward pass on the roots and N simulations of `mcts_select`,
         clone + step, one forward pass, clone back, `mcts_backup`; the rules are stated in include/qgym.h and tests/mctsmodel.py.
@@ -400,7 +402,10 @@ class BatchedSynthesis:
         `cap` (`reuse_tree`): the trees have room for cap nodes and `held` has a second pool.  Decision 0 runs as ever; after every decision
         `mcts_rebase` makes the chosen move's subtree the tree and its `env_src` moves the kept nodes' envs into the other pool (`copy_envs`
         allows no index on both sides within one handle), the pools swap, and the next decision makes its N simulations on what was
-        carried: no copy of the real envs, no root forward pass, no root backup (tests/mctsreuse_model.py)."""
+        carried: no copy of the real envs, no root forward pass, no root backup (tests/mctsreuse_model.py).
+        `K` >= 2 (`mcts_leaves`): the leaf batch has trees * K envs, env m * K + i for descent i of tree m, and a decision makes
+        R = ceil(N / K) rounds of `mcts_select_many` (k_r = min(K, N - r K) descents, virtual visits and `vloss` between them), clone + step,
+        one forward pass on the whole leaf batch, clone back, `mcts_backup_many` (tests/mctsmany_model.py).  K = 1 is the loop as it was."""
         reuse = cap is not None
         if reuse:
             leaf, pool, other, real = held.vecs
@@ -429,7 +434,14 @@ class BatchedSynthesis:
         roots = ids * cap
         finished = real.success.bool().to(torch.uint8)  # a target that is already solved needs no gates
         parked = torch.full((M,), A, dtype=torch.int32, device=dev)  # out of range: no gate (clifford.rs:324)
-        picked = tuple(torch.empty(M, dtype=torch.int32, device=dev) for _ in range(4))  # src, dst, act, leaf of a simulation
+        picked = tuple(torch.empty(M * K, dtype=torch.int32, device=dev) for _ in range(4))  # src, dst, act, leaf of a simulation / a round
+        if K > 1:
+            R = -(-N // K)
+            per_round = [min(K, N - r * K) for r in range(R)]
+            slots = torch.arange(M * K, dtype=torch.int32, device=dev)
+            round_leaves = torch.empty((R, M, K), dtype=torch.int32, device=dev)  # every round's leaves: the stats, without a launch per round
+            made = (torch.arange(K, device=dev)[None, :] < torch.tensor(per_round, device=dev)[:, None])[:, None, :]  # [R, 1, K]: i < k_r
+            idle = torch.zeros((), dtype=torch.int64, device=dev)
         keys = torch.arange(A - 1, -1, -1, dtype=torch.int64, device=dev)  # equal visits: the lowest action has the greatest key
         nodes, decisions = torch.zeros((), dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
         steps = 0
@@ -438,15 +450,24 @@ class BatchedSynthesis:
                 leaf.copy_envs(real, ids)
                 rows, values = fwd.logp_values(leaf)
                 pool.copy_envs(leaf, ids, roots)
-                mcts_backup(forest, rows, values, done=finished, root=True)
-            for s in range(N):
+                mcts_backup(forest, rows[:M], values[:M], done=finished, root=True)  # (the leaf batch has K envs per tree: the roots are the first M)
+            for r in range(R if K > 1 else 0):
+                src, dst, act, lf = mcts_select_many(forest, C, K, per_round[r], vloss, finished, *picked[:3], round_leaves[r].view(-1))
+                leaf.copy_envs(pool, src)  # a descent that is refused or not made names its tree's root and no gate
+                leaf.step(act)
+                rows, values = fwd.logp_values(leaf)
+                pool.copy_envs(leaf, slots, dst)
+                mcts_backup_many(forest, K, rows, values, leaf.reward, leaf.done, src, dst, act, lf, k=per_round[r])
+            if K > 1:  # descents that did not count: a full tree
+                idle += ((round_leaves < 0) & made & (finished == 0)[None, :, None]).sum()
+            for s in range(N if K == 1 else 0):
                 src, dst, act, lf = mcts_select(forest, C, finished, *picked[:3], leaves[s] if reuse else picked[3])
                 leaf.copy_envs(pool, src)
                 leaf.step(act)  # A where nothing is expanded: no gate, and `dst` names no env of the pool
                 rows, values = fwd.logp_values(leaf)
                 pool.copy_envs(leaf, ids, dst)
                 mcts_backup(forest, rows, values, leaf.reward, leaf.done, src, dst, act, lf)
-            if reuse:  # a full tree: the simulation that wants to expand does not count
+            if reuse and K == 1:  # a full tree: the simulation that wants to expand does not count
                 refused += ((leaves < 0) & (finished == 0)).sum()
             if searches is None and reuse:  # the same decision on its kernel: one launch
                 move = mcts_decide(forest, finished=finished, move=drawn)
@@ -492,7 +513,9 @@ class BatchedSynthesis:
         stats.update({"targets": M // S, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0,
                       "nodes": float(nodes) / max(int(decisions), 1), "kernels": fwd.kernels})
         if reuse:
-            stats.update(reuse=True, capacity=cap, carried=float(sizes.sum()) / max(int(lives.sum()), 1), refused=int(refused))
+            stats.update(reuse=True, capacity=cap, carried=float(sizes.sum()) / max(int(lives.sum()), 1), refused=int(refused if K == 1 else idle))
+        if K > 1:
+            stats.update(leaves=K, rounds=R, idle=int(idle))
         self.last_stats = stats
         return out
 
@@ -501,7 +524,7 @@ class BatchedSynthesis:
               beam_width: Optional[int] = None, merge_duplicates: bool = False, twists: Optional[int] = None,
               twist_kernels: bool = False, bound: Optional[str] = None, num_mcts_searches: int = 0, C: float = 2 ** 0.5,
               max_expand_depth: int = 1, mcts_sampled: bool = False, reuse_tree: bool = False,
-              mcts_nodes: Optional[int] = None) -> List[Optional[List[int]]]:
+              mcts_nodes: Optional[int] = None, mcts_leaves: int = 1, virtual_loss: float = 0.0) -> List[Optional[List[int]]]:
         """One entry per target: `Env::solution()` of the best successful search, or None (rl/synthesis.py:121-126).
         The rules of the sampled and the greedy search -- env m * S + s is search s of target m, the draw of step t is the race of
         `sample_actions(logits, seed, t)`, a finished env gets no gate and adds no reward, the loop ends at the first step t with
@@ -617,14 +640,35 @@ class BatchedSynthesis:
         live trees and decisions t >= 1) and "refused" ((live tree, simulation) pairs that did not count); "nodes" is the mean size at
         the decision, carried nodes included.  The handles are of a kind of their own ("mcts-reuse", "mcts-sampled-reuse"): the leaf
         batch, two pools of trees * cap envs, the real batch.  ValueError: reuse_tree without num_mcts_searches >= 1; mcts_nodes without
-        reuse_tree; mcts_nodes outside [N + 1, 8192]; the forest limit counts cap nodes per tree."""
+        reuse_tree; mcts_nodes outside [N + 1, 8192]; the forest limit counts cap nodes per tree.
+
+        mcts_leaves=K >= 2, with num_mcts_searches=N >= K (default 1: not one launch, handle or `last_stats` entry changes): K leaves per
+        tree and round of launches.  A decision makes R = ceil(N / K) rounds instead of N simulations; round r makes k_r = min(K, N - r K)
+        descents per tree in ONE selection launch (`collector.mcts_select_many`), one after another on the tree's statistics: each descent
+        leaves a virtual visit on every node of its path and takes `virtual_loss` (default 0.0) from the wsum of every node but the root,
+        for the rest of the launch only, so the next descent goes elsewhere; an edge already chosen in the round is no candidate.  The
+        k_r leaves are cloned, stepped and evaluated in one forward pass on a leaf batch of trees * K envs (env m * K + i is descent i of
+        tree m) and linked and backed up in one launch (`collector.mcts_backup_many`).  A decision spends at most N simulations, so
+        cap = N + 1 still holds them.  It combines with fast=True, `mcts_sampled` and `reuse_tree`: the decision and the rebase do not care
+        how the tree was grown.  The rules are in include/qgym.h and restated in tests/mctsmany_model.py.  The handles are of kinds of
+        their own (the kind's name + "-many"), so a K = 1 handle set is never reused with another leaf size.  `last_stats` gains "leaves"
+        (K), "rounds" (R) and "idle" ((live tree, descent) pairs that did not count: leaf < 0, a full tree; with `reuse_tree` "refused" is
+        the same number).  ValueError: mcts_leaves < 1 or > 64; mcts_leaves > 1 without num_mcts_searches >= 1; mcts_leaves >
+        num_mcts_searches; virtual_loss negative or not finite; virtual_loss != 0 with mcts_leaves = 1."""
         M = len(states)
         S = max(1, int(num_searches)) if mcts_sampled else 1
         self._check_options(M == 0, fast, beam_width, merge_duplicates, twists, twist_kernels, bound)
         N = self._check_mcts(M * S, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
-                             mcts_sampled, reuse_tree, mcts_nodes)
+                             mcts_sampled, reuse_tree, mcts_nodes, mcts_leaves, virtual_loss)
         if M == 0:
             return []
+        K = int(mcts_leaves)
+        if N and K > 1:  # the same searches in rounds of K leaves: a leaf batch of trees * K envs, handles of kinds of their own
+            B = M * S
+            kind = ("mcts-sampled" if mcts_sampled else "mcts") + ("-reuse" if reuse_tree else "") + "-many"
+            cap = (int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)) if reuse_tree else None
+            held = self._handles(kind, (B * K, B * cap, B * cap, B) if reuse_tree else (B * K, B * (N + 1), B))
+            return self._mcts_search(states, held, N, float(C), fast is True, S if mcts_sampled else None, cap, K, float(virtual_loss))
         if N and reuse_tree:
             B, cap = M * S, int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)
             held = self._handles("mcts-sampled-reuse" if mcts_sampled else "mcts-reuse", (B, B * cap, B * cap, B))
@@ -673,7 +717,7 @@ class BatchedSynthesis:
                                  "beyond the observed columns: the reward still to come has no bound the search can see")
 
     def _check_mcts(self, trees: int, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
-                    mcts_sampled, reuse_tree=False, mcts_nodes=None) -> int:
+                    mcts_sampled, reuse_tree=False, mcts_nodes=None, mcts_leaves=1, virtual_loss=0.0) -> int:
         """`num_mcts_searches` as an int, after the ValueErrors of `solve`'s tree search on `trees` trees; 0: no tree search, and `C` and
         `max_expand_depth` mean nothing."""
         N = int(num_mcts_searches)
@@ -685,6 +729,17 @@ class BatchedSynthesis:
             raise ValueError("reuse_tree=True needs num_mcts_searches >= 1: it keeps the subtree of a tree search's move")
         if mcts_nodes is not None and not reuse_tree:
             raise ValueError("mcts_nodes needs reuse_tree=True: without it a tree holds the N + 1 nodes of one decision")
+        K, vl = int(mcts_leaves), float(virtual_loss)
+        if not 1 <= K <= MCTS_MAX_LEAVES:
+            raise ValueError(f"mcts_leaves must satisfy 1 <= mcts_leaves <= {MCTS_MAX_LEAVES}, got {K}")
+        if not (vl >= 0.0 and vl < float("inf")):
+            raise ValueError("virtual_loss must be finite and at least 0")
+        if K > 1 and N == 0:
+            raise ValueError("mcts_leaves > 1 needs num_mcts_searches >= 1: it is the leaf batch of a tree search")
+        if vl != 0.0 and K == 1:
+            raise ValueError("virtual_loss needs mcts_leaves > 1: one descent per launch leaves no virtual visits behind")
+        if K > N >= 1:
+            raise ValueError(f"mcts_leaves={K} is more than num_mcts_searches={N}: a decision makes at most N descents")
         if N == 0:
             return 0
         if not float(C) > 0.0:
@@ -776,12 +831,12 @@ class BatchedSynthesis:
     def synth(self, inputs, deterministic: bool = False, num_searches: int = 100, beam_width: Optional[int] = None, merge_duplicates: bool = False,
               twists: Optional[int] = None, fast: Optional[bool] = None, twist_kernels: bool = False, bound: Optional[str] = None,
               num_mcts_searches: int = 0, C: float = 2 ** 0.5, max_expand_depth: int = 1, mcts_sampled: bool = False, reuse_tree: bool = False,
-              mcts_nodes: Optional[int] = None):
+              mcts_nodes: Optional[int] = None, mcts_leaves: int = 1, virtual_loss: float = 0.0):
         """`RLSynthesis.synth` over a list of inputs: circuits (needs qiskit) or None where no search succeeded."""
         sols = self.solve([self.env.get_state(x) for x in inputs], deterministic, num_searches, fast=fast, beam_width=beam_width,
                           merge_duplicates=merge_duplicates, twists=twists, twist_kernels=twist_kernels, bound=bound,
                           num_mcts_searches=num_mcts_searches, C=C, max_expand_depth=max_expand_depth, mcts_sampled=mcts_sampled,
-                          reuse_tree=reuse_tree, mcts_nodes=mcts_nodes)
+                          reuse_tree=reuse_tree, mcts_nodes=mcts_nodes, mcts_leaves=mcts_leaves, virtual_loss=virtual_loss)
         return [self.env.build_circuit_from_solution(s, x) if s is not None else None for s, x in zip(sols, inputs)]
 
     def gate_lists(self, solutions):
