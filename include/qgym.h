@@ -36,7 +36,7 @@ extern "C" {
  *      qg_beam_merge, qg_beam_seen_bytes, qg_vec_twists, qg_twist_expand_packed, qg_vec_observe_twisted, qg_untwist_actions,
  *      qg_policy_head_logp, qg_policy_mid_head_logp, qg_twist_pack_words, qg_vec_observe_twisted_words, qg_beam_advance, qg_mcts_forest_bytes,
  *      qg_mcts_select, qg_mcts_backup, qg_mcts_decide, qg_mcts_rebase, qg_search_plan_query, qg_mcts_select_many,
- *      qg_mcts_backup_many (additions only) */
+ *      qg_mcts_backup_many, qg_az_pack_scratch_bytes, qg_az_pack (additions only) */
 #define QG_ABI_VERSION 3
 
 typedef enum {
@@ -624,6 +624,43 @@ int qg_mcts_select_many(const qg_mcts_forest *forest, float c_puct, float virtua
 int qg_mcts_backup_many(const qg_mcts_forest *forest, uint32_t k, uint32_t stride, const int32_t *src_dev, const int32_t *dst_dev,
                         const int32_t *act_dev, const int32_t *leaf_dev, const float *logp_dev, uint64_t ld, const float *values_dev,
                         const float *reward_dev, const uint8_t *done_dev, void *stream);
+/* Self-play samples: qg_az_pack turns the log of a finished batch of sampled tree searches into the dense batch an AlphaZero-style learner
+ * reads (the reference's twisterl.rl.AZ collects the same three things per decision: observation, visit distribution, return).  Episodes end
+ * at different decisions, so a [T][E] log is mostly dead rows; the call compacts the live decisions in a fixed order, normalises the counts
+ * and computes the value target on the way.  Like the search kernels it knows no env and no policy.  tests/azmodel.py restates the rules
+ * in numpy; results agree bit for bit.  T decisions, E episodes, A = num_actions; everything is on the device.
+ *   in    counts_dev i32[T][E][counts_ld], counts_ld >= A, columns past A are never read: the rows qg_mcts_decide wrote;
+ *         reward_dev f32[T][E]: the reward of the real env's step at decision t;  live_dev u8[T][E]: != 0 where episode e made decision t;
+ *         move_dev i32[T][E];  words_dev optional, [T][E][W] words of word_bytes in {1, 4, 8}: the packed observation before the move, as
+ *         qg_vec_observe_packed writes it;  capacity >= 1.
+ *   out   n_dev i32[3]; index_dev i32[capacity]; z_dev f32[capacity]; move_out_dev i32[capacity]; pi_dev f32[capacity][pi_ld], pi_ld >= A;
+ *         words_out_dev [capacity][W] (required with words_dev).  scratch_dev: qg_az_pack_scratch_bytes(T, E) bytes, the caller's, 4-aligned.
+ *   1 rows     total(t,e) = the sum over a < A of counts[t][e][a], in 64-bit integers.  A row is BAD if any count is negative or total >=
+ *              2^24 (f32(total) would not be exact).  It is VALID iff live != 0, it is not bad and total > 0.  The counts of a row that is
+ *              not live are never read.
+ *   2 value    G(T,e) = 0; for t = T-1 .. 0: G(t,e) = reward[t][e] + G(t+1,e) where live[t][e] != 0, else G(t,e) = G(t+1,e).  The sum is
+ *              one f32 addition, round to nearest, contracted with nothing: the undiscounted return to go in the order of the backup's
+ *              G = reward[y] + G, what the value head is taken for inside the tree.  A decision that is live but not valid still
+ *              contributes its reward; live need not be monotone in t.
+ *   3 order    The rank of a valid (t,e) is the number of valid (t',e') with t'*E + e' < t*E + e.  It is written iff rank < capacity.
+ *   4 sample   At its rank: index = t*E + e; z = G(t,e), its own bits; move_out = move[t][e], copied as it stands; pi[a] =
+ *              f32(counts[a]) / f32(total) for a < A, one correctly rounded f32 division each (the plain `/` of qg_mcts_select); the W
+ *              words copied.  Columns [A, pi_ld) and every entry at a rank >= n[0] are not written.
+ *   5 n        n = { min(valid, capacity), valid, the number of live rows that are bad }, written in full by every call.
+ *   6          No randomness; the result does not depend on the launch geometry.  Inputs, outputs and scratch may not alias.
+ * Four launches on `stream` (mark the rows and count per chunk of 256 items; the returns, a lane per episode; one workgroup scans the
+ * per-chunk counts; write), no host reads, no synchronisation, capturable into a hipGraph.  The prefix sum is ballots and popcounts within
+ * a wave, LDS across a workgroup's waves and the scratch array of per-chunk counts between launches: no workgroup waits for another, no
+ * atomics, plain vector loads and stores only.  A row of counts is read by one wave, four actions per lane, once to mark it and, if valid
+ * and of rank < capacity, once more to write pi.
+ * Limits: A <= 256, T*E < 2^31 - 1, W*word_bytes <= 2048: QG_ERR_UNSUPPORTED beyond.  QG_ERR_INVALID for a null required pointer, a zero
+ * size (T, E, A, capacity; W with words_dev), counts_ld < A, pi_ld < A, a word_bytes other than 1, 4, 8, a misaligned 32-bit array (words:
+ * to word_bytes) or words_dev without words_out_dev.  qg_az_pack_scratch_bytes gives 8 bytes per item + 8 per chunk, 0 beyond the limits. */
+size_t qg_az_pack_scratch_bytes(uint64_t T, uint64_t E);
+int qg_az_pack(const int32_t *counts_dev, uint64_t counts_ld, const float *reward_dev, const uint8_t *live_dev, const int32_t *move_dev,
+               const void *words_dev, int word_bytes, uint32_t W, uint64_t T, uint64_t E, uint32_t num_actions, uint64_t capacity,
+               int32_t *n_dev, int32_t *index_dev, float *z_dev, int32_t *move_out_dev, float *pi_dev, uint64_t pi_ld, void *words_out_dev,
+               void *scratch_dev, void *stream);
 /* Twists, batched: the symmetries of the coupling map as views of the observation (Env::twists, clifford.rs:370-372; symmetry.rs:205-295).
  * For CliffordEnv, LinearFunctionEnv and PermutationEnv twist t is a pair: obs_perms[t] over the flat dense observation (rows * cols entries)
  * and act_perms[t] over the actions.  THE DEFINITION, proved on the oracle env for every kind, twist and action (tests/test_twist_views.py):

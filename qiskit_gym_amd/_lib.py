@@ -100,7 +100,7 @@ EXPORTED_SYMBOLS = [
     "qg_vec_solutions",
     "qg_vec_set_kernel_clock",
     "qg_kernel_clock_rate_khz",
-    "qg_vec_observe_dense_as", "qg_expand_packed", "qg_widen_dense", "qg_sample_actions", "qg_beam_select", "qg_beam_seen_bytes", "qg_beam_merge", "qg_beam_advance", "qg_mcts_forest_bytes", "qg_mcts_select", "qg_mcts_backup", "qg_mcts_decide", "qg_mcts_rebase", "qg_mcts_select_many", "qg_mcts_backup_many", "qg_gae",
+    "qg_vec_observe_dense_as", "qg_expand_packed", "qg_widen_dense", "qg_sample_actions", "qg_beam_select", "qg_beam_seen_bytes", "qg_beam_merge", "qg_beam_advance", "qg_mcts_forest_bytes", "qg_mcts_select", "qg_mcts_backup", "qg_mcts_decide", "qg_mcts_rebase", "qg_mcts_select_many", "qg_mcts_backup_many", "qg_az_pack_scratch_bytes", "qg_az_pack", "qg_gae",
     "qg_vec_twists", "qg_twist_expand_packed", "qg_vec_observe_twisted", "qg_untwist_actions", "qg_twist_pack_words", "qg_vec_observe_twisted_words",
     "qg_vec_embed_packed_bytes", "qg_vec_pack_embedding", "qg_vec_embed", "qg_vec_embed_observe",
     "qg_policy_embed_words_packed_bytes", "qg_policy_pack_embed_words", "qg_policy_embed_words",
@@ -194,6 +194,9 @@ def load():
     L.qg_mcts_rebase.argtypes = [C.POINTER(QGMctsForest), vp, vp, vp, vp]
     L.qg_mcts_select_many.argtypes = [C.POINTER(QGMctsForest), C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]
     L.qg_mcts_backup_many.argtypes = [C.POINTER(QGMctsForest), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp]
+    L.qg_az_pack_scratch_bytes.argtypes = [u64, u64]
+    L.qg_az_pack_scratch_bytes.restype = sz
+    L.qg_az_pack.argtypes = [vp, u64, vp, vp, vp, vp, C.c_int, C.c_uint32, u64, u64, C.c_uint32, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp]
     L.qg_widen_dense.argtypes = [vp, u64, vp, C.c_int, vp]
     L.qg_vec_twists.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.qg_vec_twists.restype = i64

@@ -31,14 +31,14 @@ The kernels' wrappers, `BasicPolicy` and the packed operands live in `policy_ker
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Optional, Tuple  # noqa: F401
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .policy_kernels import (_DT, BasicPolicy, FirstLayer, PolicyOperands, _linear_relu, _logp_outputs, _twist_operands, beam_advance, beam_merge, beam_seen, beam_select,  # noqa: F401
+from .policy_kernels import (_DT, AzPack, BasicPolicy, FirstLayer, PolicyOperands, _linear_relu, _logp_outputs, _twist_operands, az_pack, beam_advance, beam_merge, beam_seen, beam_select,  # noqa: F401
                              embed, embed_words, expand_packed, first_layer, gae, head_logp, head_sample, mcts_backup, mcts_backup_many, mcts_decide, mcts_forest, mcts_rebase, mcts_select, mcts_select_many, mid_head_logp,
                              mid_head_sample, mid_head_sample_step, pack_embed_words, pack_embedding, pack_first, pack_head, pack_mid, run_first_layer, sample_actions,
                              twist_expand_packed, twist_pack_words, untwist_actions)
@@ -67,6 +67,31 @@ class Rollout:
         if not self.obs_packed:
             return o.to(dtype)
         return expand_packed(o, self.obs_cols, dtype).flatten(-2)
+
+
+@dataclass
+class SelfPlayBatch:
+    """What `BatchedSynthesis.self_play` returns: the decisions of a batch of self-play episodes (E of them, each a sampled tree search) as
+    the samples an AlphaZero-style learner reads, packed on the device by `az_pack` in (decision, episode) order.  The tensors are views of
+    buffers that the synthesis object's self-play handles own: the next `self_play` call writes them again, so a learner that keeps a
+    batch across calls clones what it keeps."""
+    n: int                  # samples
+    obs: torch.Tensor       # [n, W] bit-packed observation before the move (`VecEnv.observe_packed` words)
+    pi: torch.Tensor        # [n, A] float32: the root's visit counts over their sum
+    z: torch.Tensor         # [n] float32: the undiscounted return from this decision to the episode's end (f32 sums from the end)
+    actions: torch.Tensor   # [n] int32: the move drawn from the counts
+    index: torch.Tensor     # [n] int32: t * E + e, decision t of episode e; strictly ascending
+    returns: torch.Tensor   # [E] float32: the episode's rewards summed forward in f32 by the search (not z at t = 0: it rounds differently)
+    success: torch.Tensor   # [E] bool: the episode ended in success
+    lengths: torch.Tensor   # [E] int32: the decisions the episode was live for
+    stats: dict = field(default_factory=dict)  # the search's `last_stats` plus episodes, episodes_solved, samples, valid, bad
+    obs_cols: int = 0
+
+    def dense_obs(self, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """[n, rows*cols] dense {0,1} observation in `dtype`, re-expanded from the packed rows (`expand_packed`)."""
+        if self.n == 0:
+            return torch.empty((0, self.obs.shape[1] * self.obs_cols), dtype=dtype, device=self.obs.device)
+        return expand_packed(self.obs, self.obs_cols, dtype).flatten(-2)
 
 
 @dataclass(frozen=True)

@@ -11,7 +11,7 @@ snapshot when a parameter's version counter has moved.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -387,6 +387,81 @@ def mcts_rebase(forest: MctsForest, move: torch.Tensor, finished: Optional[torch
     _lib.check(_lib.load().qg_mcts_rebase(forest._c, move.data_ptr(), finished.data_ptr() if finished is not None else None, env_src.data_ptr(),
                                           _stream_ptr()))
     return env_src
+
+
+class AzPack(NamedTuple):
+    """What `az_pack` writes, all on the device: n int32 [3] = (samples written, valid decisions, live rows with bad counts); per sample
+    index int32 [capacity] (t * E + e), z f32 [capacity], move int32 [capacity], pi f32 [capacity, A], words [capacity, W] or None; and the
+    call's scratch (uint8).  Only the first n[0] rows mean anything."""
+    n: torch.Tensor
+    index: torch.Tensor
+    z: torch.Tensor
+    move: torch.Tensor
+    pi: torch.Tensor
+    words: Optional[torch.Tensor]
+    scratch: torch.Tensor
+
+
+_AZ_WORD_DTYPES = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}
+if hasattr(torch, "uint32"):
+    _AZ_WORD_DTYPES.update({torch.uint32: 4, torch.uint64: 8})
+
+
+def az_pack(counts: torch.Tensor, reward: torch.Tensor, live: torch.Tensor, move: torch.Tensor, words: Optional[torch.Tensor] = None,
+            capacity: Optional[int] = None, out: Optional[AzPack] = None) -> AzPack:
+    """A finished self-play log -> a dense batch of training samples (`qg_az_pack`), four launches, no host read.  counts: int32 [T, E, A]
+    with unit column stride (a view of [T, E, >= A] will do: the columns past A are never read), the rows `mcts_decide(counts=)` wrote;
+    reward f32, live uint8 / bool, move int32, all contiguous [T, E]; words: optional contiguous [T, E, W] of 1-, 4- or 8-byte integers,
+    the packed observation before the move.  The valid decisions -- live, no negative count, 0 < sum of the counts < 2^24 -- are compacted in
+    t * E + e order, the first `capacity` of them (None: T * E) written: index, z = the undiscounted return to go in f32 (a live decision
+    that is not valid still contributes its reward), the move, pi = counts / their sum, the words.  out: the `AzPack` of an earlier call
+    of the same shapes, written again; rows at or past n[0] are left as they were.  Inputs and outputs may not alias."""
+    i32, f32 = torch.int32, torch.float32
+    if counts.dtype != i32 or counts.dim() != 3 or min(counts.shape) < 1:
+        raise ValueError("az_pack: counts must be int32 [T, E, A] with T, E, A >= 1")
+    T, E, A = counts.shape
+    dev = counts.device
+    ld = counts.stride(1) if E > 1 else counts.stride(0) if T > 1 else A  # the stride from one (t, e) row to the next
+    if (A > 1 and counts.stride(2) != 1) or ld < A or (T > 1 and E > 1 and counts.stride(0) != E * ld):
+        raise ValueError("az_pack: counts must have unit column stride and rows at one stride >= A over all of [T, E]")
+    if live.dtype == torch.bool:
+        live = live.view(torch.uint8)
+    for nm, t, dt in (("reward", reward, f32), ("live", live, torch.uint8), ("move", move, i32)):
+        if t is None or t.dtype != dt or tuple(t.shape) != (T, E) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"az_pack: {nm} must be a contiguous [{T}, {E}] {dt} tensor on the device of counts")
+    W, wb = 0, 0
+    if words is not None:
+        if words.dtype not in _AZ_WORD_DTYPES or words.dim() != 3 or tuple(words.shape[:2]) != (T, E) or words.shape[2] < 1 or not words.is_contiguous() or words.device != dev:
+            raise ValueError(f"az_pack: words must be a contiguous [{T}, {E}, W >= 1] tensor of 1-, 4- or 8-byte integers on the device of counts")
+        W, wb = words.shape[2], _AZ_WORD_DTYPES[words.dtype]
+    cap = T * E if capacity is None else int(capacity)
+    if cap < 1:
+        raise ValueError("az_pack: capacity must be at least 1")
+    L = _lib.load()
+    need = int(L.qg_az_pack_scratch_bytes(T, E))
+    if need == 0:
+        raise ValueError(f"az_pack: {T} decisions of {E} episodes are too many for 32-bit indices")
+    if out is None:
+        out = AzPack(torch.empty(3, dtype=i32, device=dev), torch.empty(cap, dtype=i32, device=dev), torch.empty(cap, dtype=f32, device=dev),
+                     torch.empty(cap, dtype=i32, device=dev), torch.empty((cap, A), dtype=f32, device=dev),
+                     torch.empty((cap, W), dtype=words.dtype, device=dev) if words is not None else None,
+                     torch.empty(need, dtype=torch.uint8, device=dev))
+    else:
+        shapes = ((out.n, (3,), i32), (out.index, (cap,), i32), (out.z, (cap,), f32), (out.move, (cap,), i32), (out.scratch, None, torch.uint8)) + (
+            ((out.words, (cap, W), words.dtype),) if words is not None else ())
+        for t, shape, dt in shapes:
+            if t is None or t.dtype != dt or t.device != dev or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+                raise ValueError("az_pack: out must be the AzPack of a call of the same shapes, capacity and device")
+        if out.scratch.numel() < need:
+            raise ValueError(f"az_pack: out.scratch holds {out.scratch.numel()} bytes, {need} are needed")
+        # pi may be a view of wider rows: the columns past A are not written
+        if out.pi.dtype != f32 or out.pi.device != dev or tuple(out.pi.shape) != (cap, A) or (A > 1 and out.pi.stride(1) != 1) or (cap > 1 and out.pi.stride(0) < A):
+            raise ValueError(f"az_pack: out.pi must be f32 [{cap}, {A}] with unit column stride on the device of counts")
+    pi_ld = out.pi.stride(0) if cap > 1 else A
+    _lib.check(L.qg_az_pack(counts.data_ptr(), ld, reward.data_ptr(), live.data_ptr(), move.data_ptr(), words.data_ptr() if words is not None else None, wb, W,
+                            T, E, A, cap, out.n.data_ptr(), out.index.data_ptr(), out.z.data_ptr(), out.move.data_ptr(), out.pi.data_ptr(), pi_ld,
+                            out.words.data_ptr() if words is not None else None, out.scratch.data_ptr(), _stream_ptr()))
+    return out
 
 
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, last_values: Optional[torch.Tensor], gamma: float,

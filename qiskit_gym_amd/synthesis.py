@@ -50,8 +50,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from .collector import SelfPlayBatch
 from .envs.gyms import ROTATION_MARKER
-from .policy_kernels import (MCTS_MAX_CAP, MCTS_MAX_FOREST_BYTES, MCTS_MAX_LEAVES, BasicPolicy, FirstLayer, PolicyOperands, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
+from .policy_kernels import (MCTS_MAX_CAP, MCTS_MAX_FOREST_BYTES, MCTS_MAX_LEAVES, AzPack, BasicPolicy, FirstLayer, PolicyOperands, az_pack, beam_advance, beam_merge, beam_seen, beam_select, first_layer,
                              mcts_backup, mcts_backup_many, mcts_decide, mcts_forest, mcts_rebase, mcts_select, mcts_select_many, mid_head_logp, mid_head_sample, run_first_layer, sample_actions)
 from .vec import VecEnv
 
@@ -90,6 +91,53 @@ class _Handles:
     key: tuple
     vecs: Tuple[VecEnv, ...]
     first: Dict[VecEnv, FirstLayer] = field(default_factory=dict)
+    log: Optional["_SelfPlayLog"] = None  # the self-play kinds: the decision log and the packed samples, reused from call to call
+
+
+SELF_PLAY_MAX_LOG_BYTES = 1 << 30  # what `self_play` allocates at most for its log and samples: 1 GiB
+
+
+class _SelfPlayLog:
+    """The recorder of `_mcts_search` for `self_play`: per decision t and episode e the root's visit counts, the live flag, the packed
+    observation before the move, the real step's reward and the move, all on the device, and the `az_pack` outputs they are packed into.
+    `reset` (states=None): (difficulty, seed) for the real envs' own reset instead of loaded targets."""
+
+    def __init__(self, T: int, E: int, A: int, real: VecEnv, capacity: int):
+        dev, i32, f32 = real.device, torch.int32, torch.float32
+        self.shape = (T, E, A, capacity)
+        self.counts = torch.zeros((T, E, A), dtype=i32, device=dev)
+        self.live = torch.zeros((T, E), dtype=torch.bool, device=dev)
+        self.reward = torch.zeros((T, E), dtype=f32, device=dev)
+        self.move = torch.zeros((T, E), dtype=i32, device=dev)
+        self.words = torch.zeros((T, E, real.packed_words_per_env), dtype={1: torch.uint8, 4: i32, 8: torch.int64}[real.packed_word_bytes], device=dev)
+        self.out: Optional[AzPack] = None
+        self.reset: Optional[Tuple[int, int]] = None
+
+    @staticmethod
+    def nbytes(T: int, E: int, A: int, W: int, word_bytes: int, capacity: int) -> int:
+        return T * E * (4 * A + 9 + W * word_bytes + 8) + T * E // 32 + 8 + capacity * (4 * A + 12 + W * word_bytes)
+
+    def before(self, t: int, real: VecEnv, finished: torch.Tensor):
+        real.observe_packed(out=self.words[t])
+        torch.eq(finished, 0, out=self.live[t])
+
+    def after(self, t: int, real: VecEnv, move: torch.Tensor):
+        self.reward[t].copy_(real.reward)
+        self.move[t].copy_(move)
+
+    def pack(self, steps: int) -> AzPack:
+        """One `az_pack` over the `steps` >= 1 decisions made, into the first rows of the outputs (made for `capacity` samples; a log of
+        `steps` decisions holds at most steps * E)."""
+        T, E, A, capacity = self.shape
+        if self.out is None:
+            dev, i32, f32 = self.counts.device, torch.int32, torch.float32
+            self.out = AzPack(torch.zeros(3, dtype=i32, device=dev), torch.zeros(capacity, dtype=i32, device=dev), torch.zeros(capacity, dtype=f32, device=dev),
+                              torch.zeros(capacity, dtype=i32, device=dev), torch.zeros((capacity, A), dtype=f32, device=dev),
+                              torch.zeros((capacity, self.words.shape[2]), dtype=self.words.dtype, device=dev),
+                              torch.empty(int(_lib.load().qg_az_pack_scratch_bytes(T, E)), dtype=torch.uint8, device=dev))
+        o, cap = self.out, min(capacity, steps * E)
+        return az_pack(self.counts[:steps], self.reward[:steps], self.live[:steps], self.move[:steps], self.words[:steps], capacity=cap,
+                       out=AzPack(o.n, o.index[:cap], o.z[:cap], o.move[:cap], o.pi[:cap], o.words[:cap], o.scratch))
 
 
 def _winner(solved: torch.Tensor, ret: torch.Tensor):
@@ -392,7 +440,7 @@ class BatchedSynthesis:
         return out
 
     def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool, searches: Optional[int] = None, cap: Optional[int] = None,
-                     K: int = 1, vloss: float = 0.0):
+                     K: int = 1, vloss: float = 0.0, rec: Optional[_SelfPlayLog] = None):
         """The search of `solve(num_mcts_searches=N)` on the handles of `held`: the leaf batch, which is all the forward object reads, the pool
         (node j of tree m is env m * (N + 1) + j) and the real envs.  Per decision one forward pass on the roots and N simulations of `mcts_select`,
         clone + step, one forward pass, clone back, `mcts_backup`; the rules are stated in include/qgym.h and tests/mctsmodel.py.
@@ -405,7 +453,10 @@ class BatchedSynthesis:
         carried: no copy of the real envs, no root forward pass, no root backup (tests/mctsreuse_model.py).
         `K` >= 2 (`mcts_leaves`): the leaf batch has trees * K envs, env m * K + i for descent i of tree m, and a decision makes
         R = ceil(N / K) rounds of `mcts_select_many` (k_r = min(K, N - r K) descents, virtual visits and `vloss` between them), clone + step,
-        one forward pass on the whole leaf batch, clone back, `mcts_backup_many` (tests/mctsmany_model.py).  K = 1 is the loop as it was."""
+        one forward pass on the whole leaf batch, clone back, `mcts_backup_many` (tests/mctsmany_model.py).  K = 1 is the loop as it was.
+        `rec` (`self_play`, with `searches`): the same loop, logged -- before the real step of decision t the real envs' packed observation and
+        which of them are live, the decision's rows of visit counts (`mcts_decide(counts=)`), after the step its rewards and the moves; with
+        `rec.reset` the real envs are reset on the device instead of loaded from `states`.  Without it not one launch, stat or call differs."""
         reuse = cap is not None
         if reuse:
             leaf, pool, other, real = held.vecs
@@ -425,7 +476,11 @@ class BatchedSynthesis:
             cap = N + 1
             forest = mcts_forest(M, N, A, dev)
         fwd = self._forward(held, 1, None, kernels, rows=True)
-        self._load(real, states, S)
+        if rec is not None and rec.reset is not None:
+            real.difficulty = rec.reset[0]
+            real.reset(rec.reset[1])
+        else:
+            self._load(real, states, S)
         if searches is not None:
             ret = torch.zeros(M, dtype=torch.float32, device=dev)
         if searches is not None or reuse:
@@ -477,12 +532,17 @@ class BatchedSynthesis:
                 visits = torch.gather(forest.visits.to(torch.int64), 1, child.clamp(min=0))
                 best = torch.where(child >= 0, visits * A + keys, -1).max(dim=1).values  # a key per (visits, action): no two alike
                 move = torch.where((best >= 0) & (finished == 0), A - 1 - best % A, parked).to(torch.int32)
+            elif rec is not None:  # the same draw, and the rows of counts it was made from are kept
+                rec.before(t, real, finished)
+                move = mcts_decide(forest, sample=True, seed=self.seed, counter=t, finished=finished, move=drawn, counts=rec.counts[t])
             else:  # drawn in proportion to the visits; A for a finished tree
                 move = mcts_decide(forest, sample=True, seed=self.seed, counter=t, finished=finished, move=drawn)
             live = finished == 0
             nodes += (forest.n_nodes * live).sum()
             decisions += live.sum()
             real.step(move)
+            if rec is not None:
+                rec.after(t, real, move)
             if searches is not None:
                 ret += torch.where(live, real.reward, torch.zeros_like(ret))
             finished |= real.done.bool().to(torch.uint8)
@@ -495,6 +555,8 @@ class BatchedSynthesis:
             steps = t + 1
             if t % 8 == 7 and bool(finished.all()):
                 break
+        if rec is not None:  # the samples, packed behind the loop on its stream; what the search kept per episode
+            rec.packed, rec.steps, rec.returns, rec.success = rec.pack(steps), steps, ret, real.success.bool()
         real.sync()
         sols, lens = real.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
         ok = real.success.bool()
@@ -684,6 +746,81 @@ class BatchedSynthesis:
         W, groups = int(beam_width), M * (1 if views is None else len(views))
         held = self._handles("beam", (groups * W, groups * W, groups), views is not None)
         return self._beam_search(states, held, views, W, bool(twist_kernels) or fast is True, bool(merge_duplicates), bound)  # kernels: on request only
+
+    @torch.no_grad()
+    def self_play(self, states: Optional[Sequence[Sequence[int]]] = None, num_episodes: Optional[int] = None, episodes_per_state: int = 1,
+                  difficulty: Optional[int] = None, reset_seed: int = 0, num_mcts_searches: int = 0, C: float = 2 ** 0.5, reuse_tree: bool = False,
+                  mcts_nodes: Optional[int] = None, mcts_leaves: int = 1, virtual_loss: float = 0.0, fast: Optional[bool] = None,
+                  capacity: Optional[int] = None) -> SelfPlayBatch:
+        """Self-play collection for an AlphaZero-style learner (the reference's `AlphaZeroConfig` -> `twisterl.rl.AZ` collects the same):
+        E episodes, each a sampled tree search of N = `num_mcts_searches` simulations per decision, every decision logged on the device --
+        the packed observation before the move, the root's visit counts, the move drawn from them, the real step's reward -- and the log
+        packed by `collector.az_pack` into dense samples (obs, pi, z, action) in (decision, episode) order: one call behind the loop,
+        then one host read, the number of samples.  No learner is built: `examples/az_linear_function.py` closes the loop in plain torch.
+
+        states given: exactly the episodes of `solve(states, num_searches=episodes_per_state, num_mcts_searches=N, mcts_sampled=True, ...)`
+        under the same seed -- episode m * S + s is search s of target m, the draw of decision t has stream 0x6D637473 and counter t, the
+        loop ends by the same rule, every move is the same.  states=None: `num_episodes` real envs get `difficulty` (None: the gym's own)
+        and `reset(reset_seed)` on the device; no target crosses the host.  `C`, `reuse_tree`, `mcts_nodes`, `mcts_leaves`, `virtual_loss`
+        and `fast` are `solve`'s.  capacity: the samples the batch has room for (None: max_depth * E, every decision); the first
+        `capacity` in order are kept and `stats["valid"]` says how many there were.
+
+        A decision gives a sample where its episode was live and its root had a visited child (a row of counts without a visit, or one
+        `az_pack` calls bad, gives none: `stats["bad"]` counts the latter; neither occurs in a search that made a simulation).  A target
+        that is solved on arrival gives none.  z is the undiscounted return to go, f32 sums from the episode's end (rules: include/qgym.h,
+        restated in tests/azmodel.py).  `stats`: `last_stats` of the search, plus "episodes" (E), "episodes_solved" (share ending in
+        success), "samples", "valid", "bad".  The handles are of kinds of their own ("self-play", with "-reuse" / "-many" as `solve`'s),
+        so a `solve` before and after answers as ever.  The batch's tensors are views of buffers those handles own: the next `self_play`
+        writes them again.  PauliGym: the handles are built without add_perms, so `observe_packed` draws nothing and the logged
+        observation is a function of the state alone (qg_vec_observe_packed never permutes; kernels_pauli_tile.hip).
+
+        ValueError: the tree search's own (`solve`); neither or both of `states` / `num_episodes`; `difficulty` with `states`;
+        num_episodes, episodes_per_state or capacity below 1; a log and samples of more than `SELF_PLAY_MAX_LOG_BYTES`; an env whose
+        packed observation does not exist (a PauliGym of more than 64 observation columns).  All before any handle is built."""
+        if (states is None) == (num_episodes is None):
+            raise ValueError("self_play: give either states or num_episodes (states=None: targets reset on the device)")
+        if states is not None and difficulty is not None:
+            raise ValueError("self_play: difficulty goes with states=None (it is the scramble length of the device-side reset)")
+        S = int(episodes_per_state)
+        if S < 1 or (states is None and S != 1):
+            raise ValueError("self_play: episodes_per_state must be at least 1, and 1 with states=None (every episode has a target of its own)")
+        if states is None and int(num_episodes) < 1:
+            raise ValueError("self_play: num_episodes must be at least 1")
+        if states is not None and len(states) == 0:
+            raise ValueError("self_play: no states")
+        E = int(num_episodes) if states is None else len(states) * S
+        N = self._check_mcts(E, False, None, False, None, False, None, num_mcts_searches, C, 1, True, reuse_tree, mcts_nodes, mcts_leaves, virtual_loss)
+        cfg = self.env.config
+        n, A, T = int(cfg["num_qubits"]), len(cfg["gateset"]), int(cfg["max_depth"])
+        kind = self.env.env_kind
+        cols = 2 * n + max(int(cfg.get("max_rotations", 5)), 1) if kind == "pauli" else 2 * n if kind == "clifford" else n
+        if cols > 64:
+            raise ValueError(f"self_play: the packed observation needs at most 64 observation columns, this env has {cols}")
+        cap_samples = T * E if capacity is None else int(capacity)
+        if cap_samples < 1:
+            raise ValueError("self_play: capacity must be at least 1")
+        rows = 2 * n if kind in ("pauli", "clifford") else n
+        nbytes = _SelfPlayLog.nbytes(T, E, A, rows, 8, cap_samples)  # a row word is 8 bytes at most
+        if nbytes > SELF_PLAY_MAX_LOG_BYTES:
+            raise ValueError(f"self_play: the log of {T} decisions x {E} episodes and {cap_samples} samples takes up to {nbytes} bytes, more than the limit "
+                             f"of {SELF_PLAY_MAX_LOG_BYTES}")
+        K = int(mcts_leaves)
+        tree_cap = (int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)) if reuse_tree else None
+        name = "self-play" + ("-reuse" if reuse_tree else "") + ("-many" if K > 1 else "")
+        held = self._handles(name, (E * K, E * tree_cap, E * tree_cap, E) if reuse_tree else (E * K, E * (N + 1), E))
+        real = held.vecs[-1]
+        if held.log is None or held.log.shape != (T, E, A, cap_samples):
+            held.log = None  # (the old buffers go first)
+            held.log = _SelfPlayLog(T, E, A, real, cap_samples)
+        rec = held.log
+        rec.reset = None if states is not None else (real.difficulty if difficulty is None else int(difficulty), int(reset_seed))
+        self._mcts_search(states, held, N, float(C), fast is True, S, tree_cap, K, float(virtual_loss), rec=rec)
+        packed = rec.packed
+        n_samples, valid, bad = (int(x) for x in packed.n.tolist())  # the one host read of the collection
+        stats = dict(self.last_stats, episodes=E, episodes_solved=float(rec.success.sum()) / E, samples=n_samples, valid=valid, bad=bad)
+        return SelfPlayBatch(n=n_samples, obs=packed.words[:n_samples], pi=packed.pi[:n_samples], z=packed.z[:n_samples], actions=packed.move[:n_samples],
+                             index=packed.index[:n_samples], returns=rec.returns, success=rec.success,
+                             lengths=rec.live[: rec.steps].sum(dim=0, dtype=torch.int32), stats=stats, obs_cols=real.obs_shape_[1])
 
     def _check_options(self, empty: bool, fast, beam_width, merge_duplicates, twists, twist_kernels, bound):
         """ValueError for a combination of `solve`'s options that does not exist; what needs a handle's config (the metrics weights under `bound`)

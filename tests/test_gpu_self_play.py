@@ -1,0 +1,327 @@
+"""`BatchedSynthesis.self_play` against `SelfPlayModel` (tests/azmodel.py): the sampled tree search of tests/mctssample_model.py with every
+decision logged and the log packed into training samples.
+
+As in tests/test_gpu_mcts_sampled.py the model is driven with the device's own rows and values: stand-ins on `synthesis.mcts_select`,
+`synthesis.mcts_backup` and `synthesis.mcts_decide` (written again here, for `self_play`) call the real function and keep what it read and
+wrote, a stand-in on `VecEnv.step` the actions every handle was given.  The model makes the same search on oracle envs; every draw, every
+sample's index, action, pi and z (by bit pattern), the expanded observation against the oracle env's at that decision, the returns, the
+success flags, the lengths and the stats must be the device's.  For `reuse_tree` and `mcts_leaves` the forest is not verified again (their own
+tests do that): the oracle envs replay the decisions from the rows of counts the device's decision wrote."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+from azmodel import F32, SelfPlayModel, pack  # noqa: E402
+from mctsmodel import FIELDS  # noqa: E402
+from mctssample_model import MASK64, STREAM, counts, draw_from  # noqa: E402
+from test_gpu_mcts import CASES, expect_forest, golden_case  # noqa: E402
+from test_gpu_mcts_kernels import bits  # noqa: E402
+from test_gpu_sampled_search import oracle_targets  # noqa: E402
+from util import rng_draw  # noqa: E402
+
+CALLS = [(case, 3, 4, None) for case in CASES] + [("clifford-3q", 3, 16, True)]
+SEARCH_STATS = {"mcts", "searches", "targets", "steps", "solved", "searches_solved", "mean_gates", "nodes", "kernels"}
+OWN_STATS = {"episodes", "episodes_solved", "samples", "valid", "bad"}
+
+
+def call_id(call):
+    case, S, N, fast = call
+    return f"{case}-S={S}-N={N}" + ("-fast" if fast else "")
+
+
+def recorded_self_play(monkeypatch, syn, **kw):
+    """`syn.self_play(**kw)` with the stand-ins in place.  Returns (the batch, the calls in order -- ("root" | "select" | "backup" | "decide" |
+    "move", what the call read and wrote, as numpy copies))."""
+    from qiskit_gym_amd import synthesis
+    from qiskit_gym_amd.vec import VecEnv
+
+    log, steps = [], []
+    real_select, real_backup, real_decide, real_step = synthesis.mcts_select, synthesis.mcts_backup, synthesis.mcts_decide, VecEnv.step
+
+    def cpu(t):
+        return None if t is None else t.cpu().numpy().copy()
+
+    def snapshot(forest):
+        return {name: cpu(getattr(forest, name)) for name in FIELDS}
+
+    def select(forest, C, finished=None, *out):
+        res = real_select(forest, C, finished, *out)
+        log.append(("select", dict(C=C, finished=cpu(finished), picked=[cpu(t) for t in res])))
+        return res
+
+    def backup(forest, logp, values, reward=None, done=None, src=None, dst=None, act=None, leaf=None, root=False):
+        res = real_backup(forest, logp, values, reward, done, src, dst, act, leaf, root)
+        log.append(("root" if root else "backup", dict(logp=cpu(logp), values=cpu(values), reward=cpu(reward), done=cpu(done),
+                                                       picked=[cpu(t) for t in (src, dst, act, leaf)], forest=snapshot(forest))))
+        return res
+
+    def decide(forest, sample=False, seed=0, counter=0, finished=None, move=None, counts=None):
+        assert counts is not None, "self_play asks every decision for its rows of counts"
+        res = real_decide(forest, sample, seed, counter, finished, move, counts)
+        log.append(("decide", dict(sample=sample, seed=seed, counter=counter, finished=cpu(finished), move=cpu(res), counts=cpu(counts))))
+        return res
+
+    def step(self, actions, coins=None):
+        steps.append((self, len(log), cpu(actions).astype(np.int64)))
+        return real_step(self, actions, coins)
+
+    with monkeypatch.context() as m:
+        m.setattr(synthesis, "mcts_select", select)
+        m.setattr(synthesis, "mcts_backup", backup)
+        m.setattr(synthesis, "mcts_decide", decide)
+        m.setattr(VecEnv, "step", step)
+        batch = syn.self_play(**kw)
+    real = [h for k, h in syn._held.items() if k.startswith("self-play")][0].vecs[-1]
+    moves = 0
+    for v, at, actions in steps:
+        if v is real:
+            log.insert(at + moves, ("move", dict(actions=actions)))
+            moves += 1
+    return batch, log
+
+
+def expect_samples(batch, want, observation, label):
+    """The batch's samples against the model's `Packed`, bit for bit, and every expanded observation against the oracle env's."""
+    n = int(want.n[0])
+    assert batch.n == n and batch.stats["samples"] == n and batch.stats["valid"] == int(want.n[1]) and batch.stats["bad"] == int(want.n[2]) == 0, label
+    for name, t in (("obs", batch.obs), ("pi", batch.pi), ("z", batch.z), ("actions", batch.actions), ("index", batch.index)):
+        assert t.shape[0] == n, (label, name)
+    np.testing.assert_array_equal(batch.index.cpu().numpy(), want.index, err_msg=f"{label}: index")
+    np.testing.assert_array_equal(batch.actions.cpu().numpy(), want.move, err_msg=f"{label}: actions")
+    np.testing.assert_array_equal(bits(batch.pi.cpu().numpy()), bits(want.pi), err_msg=f"{label}: pi")
+    np.testing.assert_array_equal(bits(batch.z.cpu().numpy()), bits(want.z), err_msg=f"{label}: z")
+    dense = batch.dense_obs(torch.int8).cpu().numpy()
+    assert dense.shape[0] == n
+    for i, index in enumerate(want.index):
+        np.testing.assert_array_equal(dense[i], observation(index), err_msg=f"{label}: the observation of sample {i} (index {index})")
+
+
+@pytest.mark.parametrize("call", CALLS, ids=call_id)
+def test_self_play_against_the_model_decision_by_decision(monkeypatch, call):
+    from qiskit_gym_amd.synthesis import BatchedSynthesis
+
+    case, S, N, fast = call
+    gym, policy, states, raw = CASES[case]()
+    seed = 1
+    syn = BatchedSynthesis(gym, policy, seed=seed)
+    batch, log = recorded_self_play(monkeypatch, syn, states=states, episodes_per_state=S, num_mcts_searches=N, fast=fast)
+    stats = batch.stats
+    A, T, M = len(gym.config["gateset"]), gym.config["max_depth"], len(states)
+    B = M * S
+    assert set(syn._held) == {"self-play"} and syn._held["self-play"].key == (B, B * (N + 1), B, False)
+    assert set(stats) == SEARCH_STATS | OWN_STATS and stats["kernels"] is bool(fast) and stats["mcts"] == N and stats["episodes"] == B
+    assert {k: stats[k] for k in SEARCH_STATS} == syn.last_stats
+    model = SelfPlayModel(oracle_targets(gym, states, raw), S, N, A, T, seed=seed)
+    f = model.forest
+    events = iter(log)
+    off_top = 0
+    for t in range(stats["steps"]):
+        assert not model.ended, f"the search went on after decision {t}"
+        kind_, rec = next(events)
+        assert kind_ == "root"
+        np.testing.assert_array_equal(rec["done"] != 0, model.finished, err_msg=f"decision {t}: which real envs are final")
+        model.start(rec["forest"]["prior"][:, 0, :], rec["values"])
+        expect_forest(rec["forest"], f, f"decision {t}: root")
+        for s in range(N):
+            label = f"decision {t} simulation {s}"
+            kind_, rec = next(events)
+            assert kind_ == "select"
+            src, dst, act, leaf = model.select()
+            for name, g, w in zip(("src", "dst", "act", "leaf"), rec["picked"], (src, dst, act, leaf)):
+                np.testing.assert_array_equal(g, w, err_msg=f"{label}: {name}")
+            model.expand()
+            kind_, rec = next(events)
+            assert kind_ == "backup"
+            prior = np.zeros((B, A), dtype=np.float32)
+            for m in np.nonzero(act < A)[0]:
+                prior[m] = rec["forest"]["prior"][m, leaf[m]]
+            model.backup(prior, rec["values"])
+            expect_forest(rec["forest"], f, label)
+        kind_, rec = next(events)
+        assert kind_ == "decide" and rec["sample"] is True and rec["seed"] == seed and rec["counter"] == t
+        np.testing.assert_array_equal(rec["finished"] != 0, model.finished, err_msg=f"decision {t}")
+        live = ~model.finished
+        n_a = counts(f)
+        np.testing.assert_array_equal(rec["counts"][:, :A], n_a, err_msg=f"decision {t}: the rows of counts")
+        draw = model.decide()
+        np.testing.assert_array_equal(rec["move"], draw, err_msg=f"decision {t}: the draws")
+        off_top += int((n_a[np.arange(B), np.minimum(draw, A - 1)] < n_a.max(axis=1))[live].sum())
+        kind_, rec = next(events)
+        assert kind_ == "move"
+        np.testing.assert_array_equal(rec["actions"], draw, err_msg=f"decision {t}: the real envs' moves")
+    assert model.ended and next(events, None) is None, f"the search stopped after {stats['steps']} decisions, the model goes on"
+    _, want_stats = model.result()
+    for key in want_stats:
+        assert stats[key] == want_stats[key], key
+    expect_samples(batch, model.samples(), model.observation, call_id(call))
+    ok = np.array([e.success() for e in model.real])
+    lengths = model.lengths()
+    np.testing.assert_array_equal(bits(batch.returns.cpu().numpy()), bits(model.ret), err_msg="the returns")
+    np.testing.assert_array_equal(batch.success.cpu().numpy(), ok)
+    np.testing.assert_array_equal(batch.lengths.cpu().numpy(), lengths)
+    assert batch.success.dtype == torch.bool and batch.lengths.dtype == torch.int32 and batch.actions.dtype == torch.int32
+    assert stats["episodes_solved"] == float(ok.sum()) / B
+    # the test is about something: samples, draws off the most visited action, episodes of different lengths
+    print(f"{call_id(call)}: {stats}; lengths {sorted(set(lengths.tolist()))}, {int((~ok).sum())} episodes without success, {off_top} draws off the top")
+    assert batch.n == int(lengths.sum()) > 0 and off_top > 0
+    index = batch.index.cpu().numpy()
+    if raw is None:  # the identity is solved on arrival: its S episodes give no sample
+        assert ok[-S:].all() and (lengths[-S:] == 0).all() and not np.isin(index % B, np.arange(B - S, B)).any()
+        assert len(set(lengths[lengths > 0].tolist())) >= 2
+    else:  # the untrained PauliGym policy: N = 4 simulations solve next to nothing, the episodes end without success
+        assert (~ok).any() or (lengths == T).any()
+
+
+@pytest.mark.parametrize("extra", [dict(reuse_tree=True), dict(mcts_leaves=2)], ids=["reuse", "leaves=2"])
+def test_carried_trees_and_several_leaves_log_the_same_way(monkeypatch, extra):
+    from qiskit_gym_amd.synthesis import BatchedSynthesis
+
+    gym, policy, states, raw = CASES["clifford-3q"]()
+    S, N, seed = 2, 4, 3
+    A, T, B = len(gym.config["gateset"]), gym.config["max_depth"], len(states) * S
+    syn = BatchedSynthesis(gym, policy, seed=seed)
+    batch, log = recorded_self_play(monkeypatch, syn, states=states, episodes_per_state=S, num_mcts_searches=N, **extra)
+    kind = "self-play-reuse" if "reuse_tree" in extra else "self-play-many"
+    assert set(syn._held) == {kind}
+    envs = [e for e in oracle_targets(gym, states, raw) for _ in range(S)]
+    envs = [e.clone() for e in envs]
+    finished = np.array([e.success() for e in envs])
+    ret = np.zeros(B, dtype=F32)
+    rows, lives, rewards, moves, obs = [], [], [], [], []
+    decisions = [rec for kind_, rec in log if kind_ == "decide"]
+    real_moves = [rec for kind_, rec in log if kind_ == "move"]
+    assert len(decisions) == len(real_moves) == batch.stats["steps"]
+    for t, (rec, mv) in enumerate(zip(decisions, real_moves)):
+        assert rec["sample"] is True and rec["seed"] == seed and rec["counter"] == t
+        np.testing.assert_array_equal(rec["finished"] != 0, finished, err_msg=f"decision {t}")
+        draws = rng_draw((seed ^ STREAM) & MASK64, np.arange(B, dtype=np.uint64), t)
+        want = np.array([A if finished[e] else draw_from(rec["counts"][e, :A], int(draws[e])) for e in range(B)], dtype=np.int32)
+        np.testing.assert_array_equal(rec["move"], want, err_msg=f"decision {t}: the draws from the rows of counts")
+        np.testing.assert_array_equal(mv["actions"], want)
+        rows.append(rec["counts"][:, :A])
+        lives.append((~finished).astype(np.uint8))
+        obs.append(np.stack([e.dense_obs().reshape(-1) for e in envs]))
+        reward = np.zeros(B, dtype=F32)
+        for e, env in enumerate(envs):
+            if not finished[e]:
+                env.step(int(want[e]))
+                reward[e] = F32(env.reward())
+                ret[e] = F32(ret[e] + reward[e])
+                finished[e] = env.is_final()
+        rewards.append(reward)
+        moves.append(want)
+    want = pack(np.stack(rows), np.stack(rewards), np.stack(lives), np.stack(moves))
+    expect_samples(batch, want, lambda index: obs[index // B][index % B], str(extra))
+    np.testing.assert_array_equal(bits(batch.returns.cpu().numpy()), bits(ret))
+    np.testing.assert_array_equal(batch.success.cpu().numpy(), np.array([e.success() for e in envs]))
+    np.testing.assert_array_equal(batch.lengths.cpu().numpy(), np.stack(lives).sum(axis=0))
+    assert batch.n > 0 and batch.stats["episodes"] == B and ("reuse" in batch.stats) == ("reuse_tree" in extra) and ("leaves" in batch.stats) == ("mcts_leaves" in extra)
+
+
+@pytest.mark.parametrize("case", ["lf_5_line", "clifford_3q_custom"])
+def test_device_side_targets_replayed_on_a_second_handle(case):
+    """states=None: a second VecEnv of the same configuration and batch, with the same difficulty and reset(reset_seed), stepped through each
+    episode's actions in index order, gives the rewards behind z, the episode ends and the success flags."""
+    from qiskit_gym_amd.synthesis import BatchedSynthesis
+
+    gym, policy, _, _ = golden_case(case, 1)
+    E, N, difficulty, reset_seed = 64, 4, 5, 11
+    A, T = len(gym.config["gateset"]), gym.config["max_depth"]
+    syn = BatchedSynthesis(gym, policy, seed=2)
+    batch = syn.self_play(num_episodes=E, difficulty=difficulty, reset_seed=reset_seed, num_mcts_searches=N)
+    assert set(syn._held) == {"self-play"} and batch.stats["episodes"] == E and batch.stats["bad"] == 0 and batch.stats["valid"] == batch.n
+    index, actions, z = batch.index.cpu().numpy(), batch.actions.cpu().numpy(), batch.z.cpu().numpy()
+    lengths, success = batch.lengths.cpu().numpy(), batch.success.cpu().numpy()
+    assert (np.diff(index) > 0).all() and batch.n == int(lengths.sum()) > 0
+    second = gym.vec(E, add_inverts=False, add_perms=False, track_solution=False)
+    second.difficulty = difficulty
+    second.reset(reset_seed)
+    second.sync()
+    start_done = second.success.cpu().numpy() != 0
+    np.testing.assert_array_equal(lengths == 0, start_done)  # a target that the reset left solved makes no decision
+    rewards = np.zeros((T, E), dtype=F32)
+    ended = start_done.copy()
+    for t in range(int(lengths.max())):
+        at = index[(index // E) == t]
+        act = np.full(E, A, dtype=np.int32)
+        act[at % E] = actions[(index // E) == t]
+        np.testing.assert_array_equal(np.sort(at % E), np.nonzero(~ended)[0], err_msg=f"decision {t}: exactly the episodes still running have a sample")
+        second.step(torch.as_tensor(act, device="cuda"))
+        second.sync()
+        rewards[t] = second.reward.cpu().numpy()
+        now = second.done.cpu().numpy() != 0
+        np.testing.assert_array_equal(ended | now, ended | (lengths == t + 1), err_msg=f"decision {t}: the episodes that end here")
+        ended |= now
+    assert ended.all() or int(lengths.max()) == T
+    np.testing.assert_array_equal(second.success.cpu().numpy() != 0, success)
+    want = np.zeros(E, dtype=F32)  # the reverse f32 sums, decision by decision from the end
+    for i in range(batch.n - 1, -1, -1):
+        t, e = divmod(int(index[i]), E)
+        want[e] = F32(rewards[t, e] + want[e])
+        assert bits(z[i]) == bits(want[e]), (i, t, e)
+    fwd = np.zeros(E, dtype=F32)
+    for i in range(batch.n):
+        t, e = divmod(int(index[i]), E)
+        fwd[e] = F32(fwd[e] + rewards[t, e])
+    np.testing.assert_array_equal(bits(batch.returns.cpu().numpy()), bits(fwd))
+    second.close()
+    print(f"{case}: {batch.stats}; lengths {np.bincount(lengths).tolist()}")
+    assert batch.stats["episodes_solved"] == float(success.sum()) / E and len(set(lengths.tolist())) >= 2
+
+
+def snapshot(batch):
+    return {k: getattr(batch, k).clone() for k in ("obs", "pi", "z", "actions", "index", "returns", "success", "lengths")}, dict(batch.stats)
+
+
+def test_seeds_handles_and_the_searches_beside_it():
+    from qiskit_gym_amd.synthesis import BatchedSynthesis
+
+    gym, policy, states, _ = golden_case("clifford_3q_custom", 6)
+    kw = dict(num_mcts_searches=4)
+    syn, other = BatchedSynthesis(gym, policy, seed=5), BatchedSynthesis(gym, policy, seed=6)
+    before = syn.solve(states, num_searches=2, mcts_sampled=True, **kw)
+    before_stats = dict(syn.last_stats)
+    first, first_stats = snapshot(syn.self_play(states=states, episodes_per_state=2, **kw))
+    held = syn._held["self-play"]
+    vecs, buffers = held.vecs, held.log
+    again, again_stats = snapshot(syn.self_play(states=states, episodes_per_state=2, **kw))
+    assert syn._held["self-play"].vecs is vecs and syn._held["self-play"].log is buffers  # the same handles and buffers ...
+    assert again_stats == first_stats and all(first[k].equal(again[k]) for k in first)  # ... and the same seed repeats the batch
+    changed, _ = snapshot(other.self_play(states=states, episodes_per_state=2, **kw))
+    n = min(len(first["actions"]), len(changed["actions"]), (len(states) - 1) * 2)  # decision 0: the same trees under both seeds, other draws
+    assert not first["actions"][:n].equal(changed["actions"][:n])
+    # the episodes are those of the sampled search under the same seed: the same returns and successes, search by search
+    assert first_stats["searches_solved"] == before_stats["searches_solved"] and first_stats["steps"] == before_stats["steps"]
+    assert {k for k in syn._held if k.startswith("self-play")} == {"self-play"} and set(syn._held) == {"self-play", "mcts-sampled"}
+    assert syn.solve(states, num_searches=2, mcts_sampled=True, **kw) == before and syn.last_stats == before_stats
+    fresh = BatchedSynthesis(gym, policy, seed=5)
+    fresh.self_play(states=states, episodes_per_state=2, **kw)
+    assert set(fresh._held) == {"self-play"}  # after self_play alone only self-play kinds are held
+    small = syn.self_play(states=states, episodes_per_state=2, capacity=5, **kw)  # a batch with room for five samples: the first five
+    assert small.n == 5 and small.stats["valid"] == first_stats["valid"] and small.index.equal(first["index"][:5]) and small.pi.equal(first["pi"][:5])
+
+
+def test_misuse_is_a_value_error_before_any_handle_is_built():
+    import qiskit_gym_amd.envs as envs
+    from qiskit_gym_amd.collector import BasicPolicy
+    from qiskit_gym_amd.synthesis import BatchedSynthesis
+    from test_gpu_beam import line_gateset
+
+    gym, policy, states, _ = golden_case("clifford_3q_custom", 6)
+    syn = BatchedSynthesis(gym, policy, seed=5)
+    ok = dict(states=states, num_mcts_searches=4)
+    for bad in (dict(num_mcts_searches=4), dict(ok, num_episodes=4), dict(ok, difficulty=3), dict(states=states), dict(ok, num_mcts_searches=0),
+                dict(ok, C=0.0), dict(ok, mcts_nodes=9), dict(ok, reuse_tree=True, mcts_nodes=3), dict(ok, mcts_leaves=0), dict(ok, mcts_leaves=8),
+                dict(ok, virtual_loss=0.5), dict(ok, mcts_leaves=2, virtual_loss=-1.0), dict(ok, episodes_per_state=0), dict(ok, capacity=0),
+                dict(states=[], num_mcts_searches=4), dict(num_episodes=0, num_mcts_searches=4), dict(num_episodes=4, episodes_per_state=2, num_mcts_searches=4),
+                dict(ok, episodes_per_state=2 ** 20),  # the forest limit
+                dict(num_episodes=2 ** 18, num_mcts_searches=1)):  # the log limit: 32 decisions x 262 144 episodes of counts, words and samples
+        with pytest.raises(ValueError):
+            syn.self_play(**bad)
+    assert not syn._held
+    n = 31  # a PauliGym of 2 * 31 + 5 observation columns: no packed observation
+    wide = envs.PauliGym(n, line_gateset("pauli", n, ["H", "CX"]), max_depth=4)
+    with pytest.raises(ValueError, match="64 observation columns"):
+        BatchedSynthesis(wide, BasicPolicy(8, 8)).self_play(num_episodes=2, num_mcts_searches=2)
