@@ -5,7 +5,8 @@
 // tests/mctsmodel.py, tests/mctssample_model.py and tests/mctsreuse_model.py restate them in numpy and the kernels agree with them bit for bit.
 //
 // qg_mcts_select_many and qg_mcts_backup_many are the first two for k descents per tree and launch (virtual visits between the descents);
-// tests/mctsmany_model.py restates them.
+// tests/mctsmany_model.py restates them.  What a pair shares is written once, in inline functions: a level's loads, scoring and lane read
+// (mcts_level_*), the new node's stores and the walk to the root (mcts_new_node, mcts_walk_up); the four kernels stay four.
 //
 // The forest is a struct of plain arrays (qg_mcts_forest): per (tree, node) parent, reward, value, visits, wsum, terminal; per (tree, node,
 // action) child and prior; per tree n_nodes.  One WAVE per tree in every kernel, several trees per workgroup; a wave owns its tree for the
@@ -58,6 +59,68 @@ __device__ inline uint64_t mcts_wave_max(uint64_t v) {
     return v;
 }
 
+// One level of a descent, as both selection kernels make it.  What the wave holds of node x after the level's one trip to memory -- everything
+// in it is addressed by x alone: the lane's entries of the child and prior rows (action lane + 64 k), the node's value and terminal flag.
+struct MctsLevel {
+    int32_t c[4];
+    float p[4];
+    float vx;
+    bool term;
+};
+
+__device__ inline MctsLevel mcts_level_load(const qg_mcts_forest &f, uint64_t base, uint32_t x, uint32_t lane) {
+    MctsLevel l;
+    const uint64_t row = (base + x) * f.num_actions;
+    l.term = f.terminal[base + x] != 0;
+    l.vx = f.value[base + x];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t ac = lane + QG_WAVE * k;
+        l.c[k] = ac < f.num_actions ? f.child[row + ac] : -1;
+        l.p[k] = ac < f.num_actions ? f.prior[row + ac] : 0.0f;
+    }
+    return l;
+}
+
+// The lane's best candidate at node x (visits_x of them so far, n nodes in the tree), as key = order(score) << 32 | ~action, 0: none; `st` is
+// the wave's LDS copy of (visits, wsum); bit k of `taken`: the lane's action of slice k is no candidate.  `bad`: a child index that is no node
+// of this tree, or no step down.
+__device__ inline uint64_t mcts_level_key(const MctsLevel &l, const uint2 *st, uint32_t visits_x, uint32_t x, uint32_t n, uint32_t A, float C, uint32_t lane,
+                                          uint32_t taken, bool &bad) {
+    const float sq = __builtin_sqrtf((float)(int32_t)visits_x);
+    uint64_t key = 0;
+    bool wrong = false;  // (a local, handed out once at the end: EXPERIMENTS.md section 24)
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t ac = lane + QG_WAVE * k;
+        if (ac >= A || ((taken >> k) & 1u)) continue;
+        float q = l.vx;
+        int32_t na = 0;
+        if (l.c[k] >= 0) {
+            if ((uint32_t)l.c[k] >= n || (uint32_t)l.c[k] <= x) {
+                wrong = true;
+                continue;
+            }
+            const uint2 s = st[l.c[k]];
+            na = (int32_t)s.x;
+            q = __uint_as_float(s.y) / (float)na;
+        }
+        const float u = ((C * l.p[k]) * sq) / (float)(1 + na);
+        const uint32_t o = mcts_order(q + u);
+        const uint64_t kk = ((uint64_t)o << 32) | (uint64_t)(0xFFFFFFFFu - ac);
+        if (o && kk > key) key = kk;
+    }
+    bad = wrong;
+    return key;
+}
+
+// the child under action `best`, by a read of the lane that holds it; < 0: an unexpanded edge
+__device__ inline int32_t mcts_level_child(const MctsLevel &l, uint32_t best) {
+    const uint32_t k = best >> 6;
+    const int32_t mine = k == 0 ? l.c[0] : k == 1 ? l.c[1] : k == 2 ? l.c[2] : l.c[3];
+    return __shfl(mine, (int)(best & (QG_WAVE - 1)), 64);
+}
+
 struct SelectArgs {
     qg_mcts_forest f;
     const uint8_t *finished;  // or nullptr
@@ -85,54 +148,21 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_select_kernel(const Sele
         for (uint32_t j = lane; j < n; j += QG_WAVE) st[j] = make_uint2((uint32_t)f.visits[base + j], __float_as_uint(f.wsum[base + j]));
         __builtin_amdgcn_wave_barrier();  // the wave reads what its other lanes wrote: LDS keeps a wave's accesses in order
         for (uint32_t level = 0; level < cap; ++level) {
-            const uint64_t row = (base + x) * A;
-            // the level's one trip: everything here is addressed by x alone
-            const bool term = f.terminal[base + x] != 0;
-            const float vx = f.value[base + x];
-            int32_t c[4];
-            float p[4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                const uint32_t ac = lane + QG_WAVE * k;
-                c[k] = ac < A ? f.child[row + ac] : -1;
-                p[k] = ac < A ? f.prior[row + ac] : 0.0f;
-            }
-            if (term) {  // the descent ends on a terminal node: nothing is expanded
+            const MctsLevel l = mcts_level_load(f, base, x, lane);
+            if (l.term) {  // the descent ends on a terminal node: nothing is expanded
                 leaf = (int32_t)x;
                 break;
             }
-            const float sq = __builtin_sqrtf((float)(int32_t)st[x].x);
-            uint64_t key = 0;
-            bool bad = false;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                const uint32_t ac = lane + QG_WAVE * k;
-                if (ac >= A) continue;
-                float q = vx;
-                int32_t na = 0;
-                if (c[k] >= 0) {
-                    if ((uint32_t)c[k] >= n || (uint32_t)c[k] <= x) {  // no node of this tree, or no step down
-                        bad = true;
-                        continue;
-                    }
-                    const uint2 s = st[c[k]];
-                    na = (int32_t)s.x;
-                    q = __uint_as_float(s.y) / (float)na;
-                }
-                const float u = ((a.C * p[k]) * sq) / (float)(1 + na);
-                const uint32_t o = mcts_order(q + u);
-                const uint64_t kk = ((uint64_t)o << 32) | (uint64_t)(0xFFFFFFFFu - ac);
-                if (o && kk > key) key = kk;
-            }
+            bool bad;
+            const uint64_t key = mcts_level_key(l, st, st[x].x, x, n, A, a.C, lane, 0u, bad);
             if (__ballot(bad)) break;  // leaf stays -1: the tree's work ends here
             const uint64_t top = mcts_wave_max(key);
             if (top == 0) {  // no candidate (every score a NaN): nothing to expand
                 leaf = (int32_t)x;
                 break;
             }
-            const uint32_t best = 0xFFFFFFFFu - (uint32_t)top, k = best >> 6;
-            const int32_t mine = k == 0 ? c[0] : k == 1 ? c[1] : k == 2 ? c[2] : c[3];
-            const int32_t next = __shfl(mine, (int)(best & (QG_WAVE - 1)), 64);
+            const uint32_t best = 0xFFFFFFFFu - (uint32_t)top;
+            const int32_t next = mcts_level_child(l, best);
             if (next < 0) {  // an unexpanded edge: the new node is n_nodes, if the tree has room
                 if (n < cap) {
                     leaf = (int32_t)n;
@@ -167,6 +197,30 @@ __device__ inline void mcts_open_node(const qg_mcts_forest &f, uint64_t node, co
         f.child[node * f.num_actions + ac] = -1;
         f.prior[node * f.num_actions + ac] = expf(logp[ac]);
     }
+}
+
+// the per-node fields of the new node j of the tree at `base`, the child of node x: one lane's stores
+__device__ inline void mcts_new_node(const qg_mcts_forest &f, uint64_t base, int64_t j, int64_t x, float reward, float value, bool term) {
+    f.parent[base + j] = (int32_t)x;
+    f.reward[base + j] = reward;
+    f.value[base + j] = value;
+    f.visits[base + j] = 0;
+    f.wsum[base + j] = 0.0f;
+    f.terminal[base + j] = term ? 1 : 0;
+}
+
+// The walk from node y to the root with the leaf's value g, on one lane -- the lane that stored every field it loads, its stores in program order
+// before these loads: one trip per level, every address is y's.  A parent that is no step up ends it, and the root is then not counted.
+__device__ inline void mcts_walk_up(const qg_mcts_forest &f, uint64_t base, uint32_t y, float g) {
+    for (uint32_t step = 0; step < f.cap && y != 0; ++step) {
+        const int32_t up = f.parent[base + y];
+        g = f.reward[base + y] + g;
+        f.visits[base + y] += 1;
+        f.wsum[base + y] += g;
+        if (up < 0 || (uint32_t)up >= y) return;
+        y = (uint32_t)up;
+    }
+    if (y == 0) f.visits[base] += 1;
 }
 
 __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_kernel(const BackupArgs a) {
@@ -208,12 +262,7 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_kernel(const Back
         g = term ? 0.0f : a.values[m];
         mcts_open_node(f, base + (uint64_t)j, logp, lane);
         if (lane == 0) {
-            f.parent[base + j] = (int32_t)x;
-            f.reward[base + j] = a.reward[m];
-            f.value[base + j] = g;
-            f.visits[base + j] = 0;
-            f.wsum[base + j] = 0.0f;
-            f.terminal[base + j] = term ? 1 : 0;
+            mcts_new_node(f, base, j, x, a.reward[m], g, term);
             f.child[(base + (uint64_t)x) * A + ac] = (int32_t)j;
             f.n_nodes[m] = (int32_t)(n + 1);
         }
@@ -222,18 +271,7 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_kernel(const Back
         if ((uint32_t)leaf >= n) return;
         g = f.value[base + (uint32_t)leaf];
     }
-    if (lane != 0) return;
-    // the walk, on one lane (its own stores above are in program order before these loads): one trip per level, every address is y's
-    uint32_t y = (uint32_t)leaf;
-    for (uint32_t step = 0; step < cap && y != 0; ++step) {
-        const int32_t up = f.parent[base + y];
-        g = f.reward[base + y] + g;
-        f.visits[base + y] += 1;
-        f.wsum[base + y] += g;
-        if (up < 0 || (uint32_t)up >= y) return;  // no step up: the root is not counted
-        y = (uint32_t)up;
-    }
-    if (y == 0) f.visits[base] += 1;
+    if (lane == 0) mcts_walk_up(f, base, (uint32_t)leaf, g);
 }
 
 struct SelectManyArgs {
@@ -276,22 +314,12 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_select_many_kernel(const
         uint32_t x = 0;
         int32_t leaf = -1, act = (int32_t)A, dst = none;
         for (uint32_t level = 0; level < cap; ++level) {
-            const uint64_t row = (base + x) * A;
-            const bool term = f.terminal[base + x] != 0;
-            const float vx = f.value[base + x];
-            int32_t c[4];
-            float p[4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                const uint32_t ac = lane + QG_WAVE * k;
-                c[k] = ac < A ? f.child[row + ac] : -1;
-                p[k] = ac < A ? f.prior[row + ac] : 0.0f;
-            }
+            const MctsLevel l = mcts_level_load(f, base, x, lane);
             const uint2 sx = st[x];  // x < n
             __builtin_amdgcn_wave_barrier();  // every lane has read the node's pair before lane 0 changes it
             // the descent stands on x once, and everything it reads of x it has read: the virtual visit
             const uint2 after = make_uint2(sx.x + 1u, x != 0 ? __float_as_uint(__uint_as_float(sx.y) - a.vloss) : sx.y);
-            if (term) {  // the descent ends on a terminal node: nothing is expanded
+            if (l.term) {  // the descent ends on a terminal node: nothing is expanded
                 if (lane == 0) st[x] = after;
                 leaf = (int32_t)x;
                 break;
@@ -302,29 +330,8 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_select_many_kernel(const
                 const uint32_t pa = (uint32_t)__shfl((int)pend_a, (int)__builtin_ctzll(hit), 64);
                 if ((pa & (QG_WAVE - 1)) == lane) taken |= 1u << (pa >> 6);
             }
-            const float sq = __builtin_sqrtf((float)(int32_t)sx.x);
-            uint64_t key = 0;
-            bool bad = false;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                const uint32_t ac = lane + QG_WAVE * k;
-                if (ac >= A || ((taken >> k) & 1u)) continue;
-                float q = vx;
-                int32_t na = 0;
-                if (c[k] >= 0) {
-                    if ((uint32_t)c[k] >= n || (uint32_t)c[k] <= x) {  // no node of this tree, or no step down
-                        bad = true;
-                        continue;
-                    }
-                    const uint2 s = st[c[k]];
-                    na = (int32_t)s.x;
-                    q = __uint_as_float(s.y) / (float)na;
-                }
-                const float u = ((a.C * p[k]) * sq) / (float)(1 + na);
-                const uint32_t o = mcts_order(q + u);
-                const uint64_t kk = ((uint64_t)o << 32) | (uint64_t)(0xFFFFFFFFu - ac);
-                if (o && kk > key) key = kk;
-            }
+            bool bad;
+            const uint64_t key = mcts_level_key(l, st, sx.x, x, n, A, a.C, lane, taken, bad);
             if (__ballot(bad)) {  // leaf stays -1, and the tree's work ends here: no later descent is made
                 run = false;
                 break;
@@ -336,9 +343,8 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_select_many_kernel(const
                 leaf = (int32_t)x;
                 break;
             }
-            const uint32_t best = 0xFFFFFFFFu - (uint32_t)top, k = best >> 6;
-            const int32_t mine = k == 0 ? c[0] : k == 1 ? c[1] : k == 2 ? c[2] : c[3];
-            const int32_t next = __shfl(mine, (int)(best & (QG_WAVE - 1)), 64);
+            const uint32_t best = 0xFFFFFFFFu - (uint32_t)top;
+            const int32_t next = mcts_level_child(l, best);
             if (next < 0) {  // an unexpanded edge: the new node is n_nodes + the edges chosen before, if the tree has room
                 if (n + grown < cap) {  // (grown <= 64: no overflow)
                     leaf = (int32_t)(n + grown);
@@ -413,36 +419,12 @@ __global__ __launch_bounds__(64 * MCTS_WAVES) void mcts_backup_many_kernel(const
             g = term ? 0.0f : a.values[e];
             mcts_open_node(f, base + (uint64_t)j, a.logp + e * a.ld, lane);
             if (lane == owner) *edge = (int32_t)j;
-            if (lane == 0) {
-                f.parent[base + j] = (int32_t)x;
-                f.reward[base + j] = a.reward[e];
-                f.value[base + j] = g;
-                f.visits[base + j] = 0;
-                f.wsum[base + j] = 0.0f;
-                f.terminal[base + j] = term ? 1 : 0;
-            }
+            if (lane == 0) mcts_new_node(f, base, j, x, a.reward[e], g, term);
             n += 1;
         } else if ((uint32_t)leaf >= n) {
             continue;
         }
-        if (lane == 0) {
-            if (!expand) g = f.value[base + (uint32_t)leaf];
-            // the walk, on the lane that stored every field it loads: one trip per level, every address is y's
-            uint32_t y = (uint32_t)leaf;
-            bool whole = true;
-            for (uint32_t step = 0; step < cap && y != 0; ++step) {
-                const int32_t up = f.parent[base + y];
-                g = f.reward[base + y] + g;
-                f.visits[base + y] += 1;
-                f.wsum[base + y] += g;
-                if (up < 0 || (uint32_t)up >= y) {  // no step up: the root is not counted
-                    whole = false;
-                    break;
-                }
-                y = (uint32_t)up;
-            }
-            if (whole && y == 0) f.visits[base] += 1;
-        }
+        if (lane == 0) mcts_walk_up(f, base, (uint32_t)leaf, expand ? g : f.value[base + (uint32_t)leaf]);
     }
     if (lane == 0 && n != n0) f.n_nodes[m] = (int32_t)n;
 }
@@ -711,6 +693,33 @@ static int mcts_check_forest(const qg_mcts_forest *f, const char *who) {
     return QG_OK;
 }
 
+// the four output arrays of a selection
+static int mcts_check_picked(const int32_t *src, const int32_t *dst, const int32_t *act, const int32_t *leaf) {
+    if (!src || !dst || !act || !leaf) return set_error(QG_ERR_INVALID, "null argument");
+    if (((uintptr_t)src % 4) || ((uintptr_t)dst % 4) || ((uintptr_t)act % 4) || ((uintptr_t)leaf % 4))
+        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    return QG_OK;
+}
+
+// the operands of a backup; `link`: those of a simulation (the selection's four, reward and done) must be there too
+static int mcts_check_operands(const qg_mcts_forest *f, bool link, const int32_t *src, const int32_t *dst, const int32_t *act, const int32_t *leaf,
+                               const float *logp, uint64_t ld, const float *values, const float *reward, const uint8_t *done) {
+    if (!logp || !values) return set_error(QG_ERR_INVALID, "null argument");
+    if (link && (!src || !dst || !act || !leaf || !reward || !done)) return set_error(QG_ERR_INVALID, "null argument");
+    if (ld < f->num_actions) return set_error(QG_ERR_INVALID, "bad shape: ld >= num_actions");
+    if (((uintptr_t)src % 4) || ((uintptr_t)dst % 4) || ((uintptr_t)act % 4) || ((uintptr_t)leaf % 4) || ((uintptr_t)logp % 4) ||
+        ((uintptr_t)values % 4) || ((uintptr_t)reward % 4))
+        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    return QG_OK;
+}
+
+static int mcts_check_many(const qg_mcts_forest *f, uint32_t k, uint32_t stride, const char *who) {
+    if (k < 1 || k > stride || stride > plan::MCTS_MAX_LEAVES)
+        return set_error(QG_ERR_INVALID, "%s: 1 <= k <= stride <= %u (a descent per lane of the tree's wave)", who, plan::MCTS_MAX_LEAVES);
+    if (f->n_trees * stride >= 0x7FFFFFFFull) return set_error(QG_ERR_INVALID, "%s: n_trees * stride must stay below 2^31 - 1", who);
+    return QG_OK;
+}
+
 }  // namespace qg
 
 using namespace qg;
@@ -722,9 +731,7 @@ extern "C" size_t qg_mcts_forest_bytes(uint64_t n_trees, uint32_t cap, uint32_t 
 extern "C" int qg_mcts_select(const qg_mcts_forest *forest, float c_puct, const uint8_t *finished_dev, int32_t *src_dev, int32_t *dst_dev, int32_t *act_dev,
                               int32_t *leaf_dev, void *stream) {
     if (const int rc = mcts_check_forest(forest, "mcts_select")) return rc;
-    if (!src_dev || !dst_dev || !act_dev || !leaf_dev) return set_error(QG_ERR_INVALID, "null argument");
-    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4))
-        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (const int rc = mcts_check_picked(src_dev, dst_dev, act_dev, leaf_dev)) return rc;
     if (forest->n_trees == 0) return QG_OK;
     SelectArgs a;
     a.f = *forest;
@@ -747,12 +754,7 @@ extern "C" int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int3
                               const uint8_t *done_dev, void *stream) {
     if (const int rc = mcts_check_forest(forest, "mcts_backup")) return rc;
     if (mode != QG_MCTS_ROOT && mode != QG_MCTS_BACKUP) return set_error(QG_ERR_INVALID, "mode must be 0 (root) or 1 (backup)");
-    if (!logp_dev || !values_dev) return set_error(QG_ERR_INVALID, "null argument");
-    if (mode == QG_MCTS_BACKUP && (!src_dev || !dst_dev || !act_dev || !leaf_dev || !reward_dev || !done_dev)) return set_error(QG_ERR_INVALID, "null argument");
-    if (ld < forest->num_actions) return set_error(QG_ERR_INVALID, "bad shape: ld >= num_actions");
-    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4) || ((uintptr_t)logp_dev % 4) ||
-        ((uintptr_t)values_dev % 4) || ((uintptr_t)reward_dev % 4))
-        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (const int rc = mcts_check_operands(forest, mode == QG_MCTS_BACKUP, src_dev, dst_dev, act_dev, leaf_dev, logp_dev, ld, values_dev, reward_dev, done_dev)) return rc;
     if (forest->n_trees == 0) return QG_OK;
     BackupArgs a;
     a.f = *forest;
@@ -772,21 +774,12 @@ extern "C" int qg_mcts_backup(const qg_mcts_forest *forest, int mode, const int3
     return QG_OK;
 }
 
-static int mcts_check_many(const qg_mcts_forest *f, uint32_t k, uint32_t stride, const char *who) {
-    if (k < 1 || k > stride || stride > plan::MCTS_MAX_LEAVES)
-        return set_error(QG_ERR_INVALID, "%s: 1 <= k <= stride <= %u (a descent per lane of the tree's wave)", who, plan::MCTS_MAX_LEAVES);
-    if (f->n_trees * stride >= 0x7FFFFFFFull) return set_error(QG_ERR_INVALID, "%s: n_trees * stride must stay below 2^31 - 1", who);
-    return QG_OK;
-}
-
 extern "C" int qg_mcts_select_many(const qg_mcts_forest *forest, float c_puct, float virtual_loss, uint32_t k, uint32_t stride, const uint8_t *finished_dev,
                                    int32_t *src_dev, int32_t *dst_dev, int32_t *act_dev, int32_t *leaf_dev, void *stream) {
     if (const int rc = mcts_check_forest(forest, "mcts_select_many")) return rc;
     if (const int rc = mcts_check_many(forest, k, stride, "mcts_select_many")) return rc;
     if (!(virtual_loss >= 0.0f) || virtual_loss > 3.402823466e+38f) return set_error(QG_ERR_INVALID, "mcts_select_many: virtual_loss must be finite and >= 0");
-    if (!src_dev || !dst_dev || !act_dev || !leaf_dev) return set_error(QG_ERR_INVALID, "null argument");
-    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4))
-        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (const int rc = mcts_check_picked(src_dev, dst_dev, act_dev, leaf_dev)) return rc;
     if (forest->n_trees == 0) return QG_OK;
     SelectManyArgs a;
     a.f = *forest;
@@ -811,11 +804,7 @@ extern "C" int qg_mcts_backup_many(const qg_mcts_forest *forest, uint32_t k, uin
                                    const float *reward_dev, const uint8_t *done_dev, void *stream) {
     if (const int rc = mcts_check_forest(forest, "mcts_backup_many")) return rc;
     if (const int rc = mcts_check_many(forest, k, stride, "mcts_backup_many")) return rc;
-    if (!logp_dev || !values_dev || !src_dev || !dst_dev || !act_dev || !leaf_dev || !reward_dev || !done_dev) return set_error(QG_ERR_INVALID, "null argument");
-    if (ld < forest->num_actions) return set_error(QG_ERR_INVALID, "bad shape: ld >= num_actions");
-    if (((uintptr_t)src_dev % 4) || ((uintptr_t)dst_dev % 4) || ((uintptr_t)act_dev % 4) || ((uintptr_t)leaf_dev % 4) || ((uintptr_t)logp_dev % 4) ||
-        ((uintptr_t)values_dev % 4) || ((uintptr_t)reward_dev % 4))
-        return set_error(QG_ERR_INVALID, "32-bit arrays must be aligned to their element size");
+    if (const int rc = mcts_check_operands(forest, true, src_dev, dst_dev, act_dev, leaf_dev, logp_dev, ld, values_dev, reward_dev, done_dev)) return rc;
     if (forest->n_trees == 0) return QG_OK;
     BackupManyArgs a;
     a.f = *forest;

@@ -43,6 +43,7 @@ results (returns, winners, `live`) is likewise one thing in every mode: `collect
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -98,7 +99,7 @@ SELF_PLAY_MAX_LOG_BYTES = 1 << 30  # what `self_play` allocates at most for its 
 
 
 class _SelfPlayLog:
-    """The recorder of `_mcts_search` for `self_play`: per decision t and episode e the root's visit counts, the live flag, the packed
+    """The recorder of `_TreeSearch` for `self_play`: per decision t and episode e the root's visit counts, the live flag, the packed
     observation before the move, the real step's reward and the move, all on the device, and the `az_pack` outputs they are packed into.
     `reset` (states=None): (difficulty, seed) for the real envs' own reset instead of loaded targets."""
 
@@ -145,6 +146,162 @@ def _winner(solved: torch.Tensor, ret: torch.Tensor):
     of equal maxima: the lowest index."""
     score = torch.where(solved, ret, torch.full(ret.shape, -float("inf"), device=ret.device))
     return score, score.argmax(dim=1)
+
+
+@dataclass(frozen=True)
+class _MctsOptions:
+    """A tree search as `_check_mcts` resolved it: `N` simulations per decision under `C`; `S` searches per target, their moves drawn (None: one tree,
+    the most visited action); `cap` nodes per tree, carried between decisions (None: N + 1, no reuse); `K` leaves per tree and round under
+    `virtual_loss`.  The one place that knows the default capacity, the handle kinds' names and their batch shapes."""
+    N: int
+    C: float
+    S: Optional[int]
+    cap: Optional[int]
+    K: int
+    virtual_loss: float
+
+    @staticmethod
+    def default_cap(N: int) -> int:  # `reuse_tree` without `mcts_nodes`
+        return min(2 * N + 1, MCTS_MAX_CAP)
+
+    @property
+    def nodes(self) -> int:  # the nodes a tree has room for
+        return self.N + 1 if self.cap is None else self.cap
+
+    def rounds(self) -> List[int]:  # the descents k_r of a decision's R = ceil(N / K) rounds: K, in the last what is left of N
+        return [min(self.K, self.N - r * self.K) for r in range(-(-self.N // self.K))]
+
+    def kind(self, prefix: Optional[str] = None) -> str:
+        """`prefix` ("self-play"; None: "mcts" / "mcts-sampled"), "-reuse" with a second pool, "-many" with K leaf envs per tree."""
+        base = prefix if prefix is not None else "mcts" if self.S is None else "mcts-sampled"
+        return base + ("-reuse" if self.cap is not None else "") + ("-many" if self.K > 1 else "")
+
+    def batches(self, trees: int) -> tuple:
+        """The leaf batch (env m * K + i: descent i of tree m), the pool (env m * nodes + j: node j; reuse: two, taking turns), the real envs."""
+        return (trees * self.K, *(trees * self.nodes,) * (1 if self.cap is None else 2), trees)
+
+
+# what a tree search leaves: the answers, `last_stats`, the decisions made; `returns` (sampled searches) and `success` per tree; `self_play`'s samples
+_MctsResult = namedtuple("_MctsResult", "solutions stats steps returns success packed")
+
+
+class _TreeSearch:
+    """The PUCT tree search of `solve(num_mcts_searches=N)` and `self_play` on the handles of `held`: the leaf batch, which is all the forward
+    object reads, the pool(s) of node envs and the real envs.  Rules: include/qgym.h, restated in tests/mcts*model.py; tree m * S + s is search s
+    of target m.  A decision makes R rounds of k_r descents (`_MctsOptions.rounds`): N of one on `mcts_select` / `mcts_backup` (K = 1), or
+    ceil(N / K) on the `_many` pair, virtual visits between a round's descents; the pair is chosen here, once, and looked up in this module at
+    every call.  `leaves` [R, M, K], every round's leaf outputs, is read by the count of descents that did not count: kept under reuse and
+    K >= 2 only (the N + 1 nodes of a plain search of one leaf cannot fill)."""
+
+    def __init__(self, opts: _MctsOptions, held: _Handles, seed: int, rec: Optional[_SelfPlayLog] = None):
+        self.opts, self.seed, self.rec = opts, seed, rec
+        self.leaf, self.pool, *other, self.real = held.vecs
+        self.other = other[0] if other else None  # reuse: the pool the kept nodes' envs move into
+        real, K, per_round = self.real, opts.K, opts.rounds()
+        M, dev, i32, i64 = real.batch, real.device, torch.int32, torch.int64  # M: trees
+        self.T = T = int(real._cfg.max_depth)
+        self.forest = mcts_forest(M, opts.N, real.num_actions(), dev, cap=opts.cap)
+        self.ids, self.per_round = torch.arange(M, dtype=i32, device=dev), per_round
+        self.roots = self.ids * opts.nodes
+        self.slots = self.ids if K == 1 else torch.arange(M * K, dtype=i32, device=dev)  # the leaf batch's envs: what a round copies back
+        self.picked = tuple(torch.empty(M * K, dtype=i32, device=dev) for _ in range(4))  # src, dst, act, leaf of a round
+        self.drawn = torch.empty(M, dtype=i32, device=dev)
+        self.ret = None if opts.S is None else torch.zeros(M, dtype=torch.float32, device=dev)  # a sampled search's return per tree
+        if K == 1:  # called alike, the search handed in: kept here, a closure over `self` is a cycle that holds the forest; one descent ignores k
+            self.select = lambda s, k, out: mcts_select(s.forest, opts.C, s.finished, *out)
+            self.backup = lambda s, k, rows, values, picked: mcts_backup(s.forest, rows, values, s.leaf.reward, s.leaf.done, *picked)
+        else:
+            self.select = lambda s, k, out: mcts_select_many(s.forest, opts.C, K, k, opts.virtual_loss, s.finished, *out)
+            self.backup = lambda s, k, rows, values, picked: mcts_backup_many(s.forest, K, rows, values, s.leaf.reward, s.leaf.done, *picked, k=k)
+        self.leaves = torch.empty((len(per_round), M, K), dtype=i32, device=dev) if self.other is not None or K > 1 else None  # for the stats
+        self.made = (torch.arange(K, device=dev)[None, :] < torch.tensor(per_round, device=dev)[:, None])[:, None, :] if K > 1 else None  # i < k_r
+        self.outs = [self.picked if self.leaves is None else (*self.picked[:3], self.leaves[r].view(-1)) for r in range(len(per_round))]  # per round
+        if self.other is not None:  # and per decision the live trees and their carried sizes
+            self.env_src = torch.empty(M * opts.cap, dtype=i32, device=dev)
+            self.sizes, self.lives = torch.zeros((T, M), dtype=i32, device=dev), torch.zeros((T, M), dtype=torch.bool, device=dev)
+        self.missed, self.nodes, self.decisions = (torch.zeros((), dtype=i64, device=dev) for _ in range(3))
+
+    def _round(self, r: int, k: int):
+        """k descents per tree.  One that is refused or not made names its tree's root, no gate (A) and, as `dst`, no env of the pool."""
+        leaf, picked = self.leaf, self.select(self, k, self.outs[r])
+        leaf.copy_envs(self.pool, picked[0])  # src
+        leaf.step(picked[2])  # act
+        rows, values = self.fwd.logp_values(leaf)
+        self.pool.copy_envs(leaf, self.slots, picked[1])  # dst
+        self.backup(self, k, rows, values, picked)
+
+    def _decide(self, t: int) -> torch.Tensor:
+        """Decision t, one launch: the most visited action, or (`S`) one drawn by the visits; `rec` logs the real envs first and keeps the counts."""
+        how = {} if self.opts.S is None else dict(sample=True, seed=self.seed, counter=t)
+        if self.rec is not None:
+            self.rec.before(t, self.real, self.finished)
+            how["counts"] = self.rec.counts[t]
+        return mcts_decide(self.forest, finished=self.finished, move=self.drawn, **how)
+
+    def _carry(self, t: int, move: torch.Tensor):
+        """`reuse_tree`: the move's subtree becomes the tree, the kept nodes' envs move; a tree whose real env just ended is left alone."""
+        mcts_rebase(self.forest, move, self.finished, self.env_src)
+        self.other.copy_envs(self.pool, self.env_src)  # into the other pool: `copy_envs` allows no index on both sides within one handle
+        self.pool, self.other = self.other, self.pool
+        torch.eq(self.finished, 0, out=self.lives[t])
+        torch.mul(self.forest.n_nodes, self.lives[t], out=self.sizes[t])
+
+    def run(self, fwd: _Forward) -> _MctsResult:  # from the targets the real envs hold now
+        leaf, real, M, steps, self.fwd = self.leaf, self.real, self.real.batch, 0, fwd
+        self.finished = real.success.bool().to(torch.uint8)  # a target that is already solved needs no gates
+        for t in range(self.T):
+            if t == 0 or self.other is None:  # a fresh tree per real env, the root its clone (the leaf batch has K envs per tree: the first M)
+                leaf.copy_envs(real, self.ids)
+                rows, values = self.fwd.logp_values(leaf)
+                self.pool.copy_envs(leaf, self.ids, self.roots)
+                mcts_backup(self.forest, rows[:M], values[:M], done=self.finished, root=True)
+            for r, k in enumerate(self.per_round):
+                self._round(r, k)
+            live = self.finished == 0
+            if self.leaves is not None:  # descents that did not count (leaf < 0: a full tree), over live trees and descents made
+                lost = (self.leaves < 0) & live[None, :, None]
+                self.missed += (lost if self.made is None else lost & self.made).sum()
+            move = self._decide(t)
+            self.nodes += (self.forest.n_nodes * live).sum()
+            self.decisions += live.sum()
+            real.step(move)
+            if self.rec is not None:
+                self.rec.after(t, real, move)
+            if self.ret is not None:  # a search's return: the f32 sum, in step order, of the rewards of the steps it was live for
+                self.ret += torch.where(live, real.reward, torch.zeros_like(self.ret))
+            self.finished |= real.done.bool().to(torch.uint8)
+            if self.other is not None:
+                self._carry(t, move)
+            steps = t + 1
+            if t % 8 == 7 and bool(self.finished.all()):
+                break
+        return self._answers(steps)
+
+    def _answers(self, steps: int) -> _MctsResult:
+        """Per target the real env's own solution log where its episode succeeded; `S`: that of its winning search (`_winner`)."""
+        o, real, M, A, S = self.opts, self.real, self.real.batch, self.real.num_actions(), self.opts.S or 1
+        packed = None if self.rec is None else self.rec.pack(steps)  # the samples, packed behind the loop on its stream
+        real.sync()
+        sols, lens = real.solutions(self.T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
+        success = real.success.bool()
+        stats = {"mcts": o.N}
+        if o.S is None:
+            mine, ok = range(M), success.cpu().numpy()
+        else:
+            won = success.view(-1, S)
+            mine = (torch.arange(M // S, device=real.device) * S + _winner(won, self.ret.view(-1, S))[1]).tolist()
+            stats.update(searches=S, searches_solved=int(won.sum()) / M)
+            ok = won.any(dim=1).cpu().numpy()
+        # a finished env was handed A from then on, which the log of some env kinds records: such entries are no gates and no markers
+        out = [[int(x) for x in sols[e, : lens[e]] if x < A or x >= ROTATION_MARKER] if ok[m] else None for m, e in enumerate(mine)]
+        gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
+        stats.update({"targets": M // S, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0,
+                      "nodes": float(self.nodes) / max(int(self.decisions), 1), "kernels": self.fwd.kernels})
+        if self.other is not None:
+            stats.update(reuse=True, capacity=o.cap, carried=float(self.sizes.sum()) / max(int(self.lives.sum()), 1), refused=int(self.missed))
+        if o.K > 1:
+            stats.update(leaves=o.K, rounds=len(self.per_round), idle=int(self.missed))
+        return _MctsResult(out, stats, steps, self.ret, success, packed)
 
 
 class _Forward:
@@ -267,11 +424,9 @@ class BatchedSynthesis:
         """The handles of `kind`, one per entry of `batches`: "search" (the sampled and greedy searches' batch), "replay" (the winners of a
         PauliGym search, replayed with the solution log on) or "beam" (the two batches of targets * width envs that take turns as source and
         destination of the per-step copy, and the winners, all three with the same constructor arguments: the rule of `copy_envs`; no layout
-        choice depends on the batch size) or "mcts" (the pool of targets * (N + 1) node envs, the leaf batch and the real batch of one env per
-        target, again all with the same constructor arguments) or "mcts-sampled" (the same three for targets * searches trees) or "mcts-reuse" /
-        "mcts-sampled-reuse" (`reuse_tree`: the leaf batch, TWO pools of trees * cap node envs that take turns as source and destination of
-        the copy between two decisions, and the real batch); each of the four again with "-many" appended (`mcts_leaves=K`: the
-        same handles with a leaf batch of trees * K envs).  One batch shape at a time per kind: the handles own device memory."""
+        choice depends on the batch size) or a tree search's kind (`_MctsOptions.kind` and `.batches`: the leaf batch, the pool or pools of
+        node envs and the real batch, again all with the same constructor arguments).  One batch shape at a time per kind: the handles own
+        device memory."""
         key = (*batches, perms)  # add_perms: twists() only, the env steps alike
         held = self._held.get(kind)
         if held is not None and held.key != key:
@@ -439,147 +594,18 @@ class BatchedSynthesis:
             self.last_stats.update(bound=bound, bounded=int(bounded.sum()))
         return out
 
-    def _mcts_search(self, states, held: _Handles, N: int, C: float, kernels: bool, searches: Optional[int] = None, cap: Optional[int] = None,
-                     K: int = 1, vloss: float = 0.0, rec: Optional[_SelfPlayLog] = None):
-        """The search of `solve(num_mcts_searches=N)` on the handles of `held`: the leaf batch, which is all the forward object reads, the pool
-        (node j of tree m is env m * (N + 1) + j) and the real envs.  Per decision one forward pass on the roots and N simulations of `mcts_select`,
-        clone + step, one forward pass, clone back, `mcts_backup`; the rules are stated in include/qgym.h and tests/mctsmodel.py.
-        `searches` None: one tree per target, the move is the root's most visited action.  `searches` = S (`mcts_sampled`): S trees per
-        target, tree and real env m * S + s is search s of target m; the move is drawn from the root's visit counts (`mcts_decide`, counter
-        t) and a target's answer is that of its successful search of the greatest return (tests/mctssample_model.py).
-        `cap` (`reuse_tree`): the trees have room for cap nodes and `held` has a second pool.  Decision 0 runs as ever; after every decision
-        `mcts_rebase` makes the chosen move's subtree the tree and its `env_src` moves the kept nodes' envs into the other pool (`copy_envs`
-        allows no index on both sides within one handle), the pools swap, and the next decision makes its N simulations on what was
-        carried: no copy of the real envs, no root forward pass, no root backup (tests/mctsreuse_model.py).
-        `K` >= 2 (`mcts_leaves`): the leaf batch has trees * K envs, env m * K + i for descent i of tree m, and a decision makes
-        R = ceil(N / K) rounds of `mcts_select_many` (k_r = min(K, N - r K) descents, virtual visits and `vloss` between them), clone + step,
-        one forward pass on the whole leaf batch, clone back, `mcts_backup_many` (tests/mctsmany_model.py).  K = 1 is the loop as it was.
-        `rec` (`self_play`, with `searches`): the same loop, logged -- before the real step of decision t the real envs' packed observation and
-        which of them are live, the decision's rows of visit counts (`mcts_decide(counts=)`), after the step its rewards and the moves; with
-        `rec.reset` the real envs are reset on the device instead of loaded from `states`.  Without it not one launch, stat or call differs."""
-        reuse = cap is not None
-        if reuse:
-            leaf, pool, other, real = held.vecs
-        else:
-            leaf, pool, real = held.vecs
-        S = 1 if searches is None else searches
-        M, A, dev = real.batch, real.num_actions(), real.device  # M: trees, `S` per target
-        T = int(real._cfg.max_depth)
-        if reuse:
-            forest = mcts_forest(M, N, A, dev, cap=cap)
-            env_src = torch.empty(M * cap, dtype=torch.int32, device=dev)
-            # the stats, without a launch per simulation: every simulation's leaves, and per decision the live trees and their carried sizes
-            leaves = torch.empty((N, M), dtype=torch.int32, device=dev)
-            sizes, lives = torch.zeros((T, M), dtype=torch.int32, device=dev), torch.zeros((T, M), dtype=torch.bool, device=dev)
-            refused = torch.zeros((), dtype=torch.int64, device=dev)
-        else:
-            cap = N + 1
-            forest = mcts_forest(M, N, A, dev)
+    def _tree_search(self, states, held: _Handles, opts: _MctsOptions, kernels: bool, rec: Optional[_SelfPlayLog] = None) -> _MctsResult:
+        """`_TreeSearch` from `states`, every target `S` times, or (`rec.reset`) from the real envs' own reset on the device; sets `last_stats`."""
+        search, real = _TreeSearch(opts, held, self.seed, rec), held.vecs[-1]  # the forest and the buffers first
         fwd = self._forward(held, 1, None, kernels, rows=True)
         if rec is not None and rec.reset is not None:
             real.difficulty = rec.reset[0]
             real.reset(rec.reset[1])
         else:
-            self._load(real, states, S)
-        if searches is not None:
-            ret = torch.zeros(M, dtype=torch.float32, device=dev)
-        if searches is not None or reuse:
-            drawn = torch.empty(M, dtype=torch.int32, device=dev)
-        ids = torch.arange(M, dtype=torch.int32, device=dev)
-        roots = ids * cap
-        finished = real.success.bool().to(torch.uint8)  # a target that is already solved needs no gates
-        parked = torch.full((M,), A, dtype=torch.int32, device=dev)  # out of range: no gate (clifford.rs:324)
-        picked = tuple(torch.empty(M * K, dtype=torch.int32, device=dev) for _ in range(4))  # src, dst, act, leaf of a simulation / a round
-        if K > 1:
-            R = -(-N // K)
-            per_round = [min(K, N - r * K) for r in range(R)]
-            slots = torch.arange(M * K, dtype=torch.int32, device=dev)
-            round_leaves = torch.empty((R, M, K), dtype=torch.int32, device=dev)  # every round's leaves: the stats, without a launch per round
-            made = (torch.arange(K, device=dev)[None, :] < torch.tensor(per_round, device=dev)[:, None])[:, None, :]  # [R, 1, K]: i < k_r
-            idle = torch.zeros((), dtype=torch.int64, device=dev)
-        keys = torch.arange(A - 1, -1, -1, dtype=torch.int64, device=dev)  # equal visits: the lowest action has the greatest key
-        nodes, decisions = torch.zeros((), dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
-        steps = 0
-        for t in range(T):
-            if t == 0 or not reuse:
-                leaf.copy_envs(real, ids)
-                rows, values = fwd.logp_values(leaf)
-                pool.copy_envs(leaf, ids, roots)
-                mcts_backup(forest, rows[:M], values[:M], done=finished, root=True)  # (the leaf batch has K envs per tree: the roots are the first M)
-            for r in range(R if K > 1 else 0):
-                src, dst, act, lf = mcts_select_many(forest, C, K, per_round[r], vloss, finished, *picked[:3], round_leaves[r].view(-1))
-                leaf.copy_envs(pool, src)  # a descent that is refused or not made names its tree's root and no gate
-                leaf.step(act)
-                rows, values = fwd.logp_values(leaf)
-                pool.copy_envs(leaf, slots, dst)
-                mcts_backup_many(forest, K, rows, values, leaf.reward, leaf.done, src, dst, act, lf, k=per_round[r])
-            if K > 1:  # descents that did not count: a full tree
-                idle += ((round_leaves < 0) & made & (finished == 0)[None, :, None]).sum()
-            for s in range(N if K == 1 else 0):
-                src, dst, act, lf = mcts_select(forest, C, finished, *picked[:3], leaves[s] if reuse else picked[3])
-                leaf.copy_envs(pool, src)
-                leaf.step(act)  # A where nothing is expanded: no gate, and `dst` names no env of the pool
-                rows, values = fwd.logp_values(leaf)
-                pool.copy_envs(leaf, ids, dst)
-                mcts_backup(forest, rows, values, leaf.reward, leaf.done, src, dst, act, lf)
-            if reuse and K == 1:  # a full tree: the simulation that wants to expand does not count
-                refused += ((leaves < 0) & (finished == 0)).sum()
-            if searches is None and reuse:  # the same decision on its kernel: one launch
-                move = mcts_decide(forest, finished=finished, move=drawn)
-            elif searches is None:
-                # the decision: the root's expanded action of the most visits, the lowest among equals; A where the root has no child
-                child = forest.child[:, 0, :].to(torch.int64)
-                visits = torch.gather(forest.visits.to(torch.int64), 1, child.clamp(min=0))
-                best = torch.where(child >= 0, visits * A + keys, -1).max(dim=1).values  # a key per (visits, action): no two alike
-                move = torch.where((best >= 0) & (finished == 0), A - 1 - best % A, parked).to(torch.int32)
-            elif rec is not None:  # the same draw, and the rows of counts it was made from are kept
-                rec.before(t, real, finished)
-                move = mcts_decide(forest, sample=True, seed=self.seed, counter=t, finished=finished, move=drawn, counts=rec.counts[t])
-            else:  # drawn in proportion to the visits; A for a finished tree
-                move = mcts_decide(forest, sample=True, seed=self.seed, counter=t, finished=finished, move=drawn)
-            live = finished == 0
-            nodes += (forest.n_nodes * live).sum()
-            decisions += live.sum()
-            real.step(move)
-            if rec is not None:
-                rec.after(t, real, move)
-            if searches is not None:
-                ret += torch.where(live, real.reward, torch.zeros_like(ret))
-            finished |= real.done.bool().to(torch.uint8)
-            if reuse:  # a tree whose real env just ended is left alone and copies nothing
-                mcts_rebase(forest, move, finished, env_src)
-                other.copy_envs(pool, env_src)
-                pool, other = other, pool
-                torch.eq(finished, 0, out=lives[t])
-                torch.mul(forest.n_nodes, lives[t], out=sizes[t])
-            steps = t + 1
-            if t % 8 == 7 and bool(finished.all()):
-                break
-        if rec is not None:  # the samples, packed behind the loop on its stream; what the search kept per episode
-            rec.packed, rec.steps, rec.returns, rec.success = rec.pack(steps), steps, ret, real.success.bool()
-        real.sync()
-        sols, lens = real.solutions(T + 64)  # the log holds an episode's steps, PauliEnv: plus one entry per rotation (<= 32)
-        ok = real.success.bool()
-        stats = {"mcts": N}
-        if searches is None:
-            mine = range(M)
-            ok = ok.cpu().numpy()
-        else:  # per target the successful search of the greatest return, the lowest s among equals; its env's own log is the answer
-            won = ok.view(-1, S)
-            mine = (torch.arange(M // S, device=dev) * S + _winner(won, ret.view(-1, S))[1]).tolist()
-            stats.update(searches=S, searches_solved=int(won.sum()) / M)
-            ok = won.any(dim=1).cpu().numpy()
-        # a finished env was handed A from then on, which the log of some env kinds records: such entries are no gates and no markers
-        out = [[int(x) for x in sols[e, : lens[e]] if x < A or x >= ROTATION_MARKER] if ok[m] else None for m, e in enumerate(mine)]
-        gates = [sum(1 for x in s if x < ROTATION_MARKER) for s in out if s is not None]
-        stats.update({"targets": M // S, "steps": steps, "solved": int(ok.sum()), "mean_gates": float(np.mean(gates)) if gates else 0.0,
-                      "nodes": float(nodes) / max(int(decisions), 1), "kernels": fwd.kernels})
-        if reuse:
-            stats.update(reuse=True, capacity=cap, carried=float(sizes.sum()) / max(int(lives.sum()), 1), refused=int(refused if K == 1 else idle))
-        if K > 1:
-            stats.update(leaves=K, rounds=R, idle=int(idle))
-        self.last_stats = stats
-        return out
+            self._load(real, states, 1 if opts.S is None else opts.S)
+        res = search.run(fwd)
+        self.last_stats = res.stats
+        return res
 
     @torch.no_grad()
     def solve(self, states: Sequence[Sequence[int]], deterministic: bool = False, num_searches: int = 100, fast: Optional[bool] = None,
@@ -663,17 +689,17 @@ class BatchedSynthesis:
         (Q: the child's mean backed-up return, the node's own value for an edge not yet tried; ties to the lowest action;
         `collector.mcts_select`), expands one node -- a clone of its parent's env (`VecEnv.copy_envs`) stepped with the action, asked
         about by one forward pass for all targets -- and adds its value plus the rewards on the way up to every node above it
-        (`collector.mcts_backup`).  After N simulations the real env takes the root's most visited action (the lowest among equals); a real
-        env that is final gets no more gates and its tree no more simulations; the loop ends like the other searches'.  The answer is
-        the real env's solution log where the episode ended in success (PauliGym: rotation markers included), else None.  The exact
-        rules, operation by operation, are in include/qgym.h and restated in tests/mctsmodel.py.  fast=True runs the forward passes on
-        the policy-layer kernels (`mid_head_logp`: rows and values), None / False on the torch forward.  `last_stats`: "mcts" (N),
-        "targets", "steps" (decisions), "solved", "mean_gates", "nodes" (mean nodes per tree and decision) and "kernels".  ValueError:
-        N < 0; C <= 0; max_expand_depth != 1 (not built: what twisterl means by it cannot be read from the reference);
-        deterministic=False (unless `mcts_sampled`, below); together with beam_width, merge_duplicates, bound,
+        (`collector.mcts_backup`).  After N simulations the real env takes the root's most visited action (the lowest among equals; one
+        launch, `collector.mcts_decide`, in every mode); a real env that is final gets no more gates and its tree no more simulations; the
+        loop ends like the other searches'.  The answer is the real env's solution log where the episode ended in success (PauliGym:
+        rotation markers included), else None.  The exact rules, operation by operation, are in include/qgym.h and restated in
+        tests/mctsmodel.py.  fast=True runs the forward passes on the policy-layer kernels (`mid_head_logp`: rows and values), None / False
+        on the torch forward.  `last_stats`: "mcts" (N), "targets", "steps" (decisions), "solved", "mean_gates", "nodes" (mean nodes per
+        tree and decision) and "kernels".  ValueError: N < 0; C <= 0; max_expand_depth != 1 (not built: what twisterl means by it cannot
+        be read from the reference); deterministic=False (unless `mcts_sampled`, below); together with beam_width, merge_duplicates, bound,
         twists or twist_kernels; a forest -- targets * (N + 1) * (21 + 8 * num_actions) bytes -- of more than 1 GiB
-        (`policy_kernels.MCTS_MAX_FOREST_BYTES`; the pool of targets * (N + 1) envs comes on top); N + 1 > 8 192 or more than 256
-        actions is the library's QGymError.
+        (`policy_kernels.MCTS_MAX_FOREST_BYTES`; the pool of targets * (N + 1) envs comes on top); N + 1 > 8 192 or more than 256 actions
+        is the library's QGymError.  Every mode, here and below, has handles of a kind of its own (`_MctsOptions.kind`, `.batches`).
 
         mcts_sampled=True, with num_mcts_searches=N >= 1 and deterministic=False (default False: every code path, handle key and `last_stats`
         as without the argument, the ValueError for a tree search with deterministic=False included -- which is why this mode is opted
@@ -685,9 +711,9 @@ class BatchedSynthesis:
         episodes.  A search's return is the f32 sum, in step order, of the rewards of the steps it was live for; a target's answer is the
         solution log of its successful search of the greatest return, the lowest s among equals (None without one; PauliGym: rotation
         markers included, no replay).  The rules are restated in tests/mctssample_model.py.  `last_stats`: "mcts", "searches" (S),
-        "targets", "steps", "solved", "searches_solved" (successful searches / all), "mean_gates", "nodes", "kernels".  The handles are
-        of a kind of their own ("mcts-sampled").  ValueError: without num_mcts_searches >= 1; with deterministic=True; with beam_width,
-        merge_duplicates, bound, twists or twist_kernels; and the tree search's own, the forest limit now on targets * S trees.
+        "targets", "steps", "solved", "searches_solved" (successful searches / all), "mean_gates", "nodes", "kernels".  ValueError: without
+        num_mcts_searches >= 1; with deterministic=True; with beam_width, merge_duplicates, bound, twists or twist_kernels; and the tree
+        search's own, the forest limit now on targets * S trees.
 
         reuse_tree=True, with num_mcts_searches=N >= 1, deterministic or `mcts_sampled` (default False: not one launch, handle or
         `last_stats` entry changes): the chosen move's subtree is kept between decisions.  The search handles step deterministically, so
@@ -695,14 +721,13 @@ class BatchedSynthesis:
         have room for cap = `mcts_nodes` nodes, by default min(2 N + 1, 8192).  Decision 0 runs as above; after every decision
         `collector.mcts_rebase` compacts every live tree to that subtree on the device (the new root keeps its visits, 1 + the simulations
         below it) and the kept nodes' envs move into a second pool; decisions t >= 1 make their N simulations on the carried tree, without
-        the copy of the real envs, the root's forward pass and the root backup; the deterministic search's decision is `collector.mcts_decide`'s
-        most visited action, one launch.  A tree that is full makes no further nodes: a simulation
+        the copy of the real envs, the root's forward pass and the root backup.  A tree that is full makes no further nodes: a simulation
         that wants to expand does not count (`collector.mcts_select`: leaf = -1).  The rules are in include/qgym.h and restated in
         tests/mctsreuse_model.py.  `last_stats` gains "reuse" (True), "capacity" (cap), "carried" (mean nodes right after the rebase, over
         live trees and decisions t >= 1) and "refused" ((live tree, simulation) pairs that did not count); "nodes" is the mean size at
-        the decision, carried nodes included.  The handles are of a kind of their own ("mcts-reuse", "mcts-sampled-reuse"): the leaf
-        batch, two pools of trees * cap envs, the real batch.  ValueError: reuse_tree without num_mcts_searches >= 1; mcts_nodes without
-        reuse_tree; mcts_nodes outside [N + 1, 8192]; the forest limit counts cap nodes per tree.
+        the decision, carried nodes included.  The handles: the leaf batch, two pools of trees * cap envs, the real batch.  ValueError:
+        reuse_tree without num_mcts_searches >= 1; mcts_nodes without reuse_tree; mcts_nodes outside [N + 1, 8192]; the forest limit counts
+        cap nodes per tree.
 
         mcts_leaves=K >= 2, with num_mcts_searches=N >= K (default 1: not one launch, handle or `last_stats` entry changes): K leaves per
         tree and round of launches.  A decision makes R = ceil(N / K) rounds instead of N simulations; round r makes k_r = min(K, N - r K)
@@ -712,34 +737,21 @@ class BatchedSynthesis:
         k_r leaves are cloned, stepped and evaluated in one forward pass on a leaf batch of trees * K envs (env m * K + i is descent i of
         tree m) and linked and backed up in one launch (`collector.mcts_backup_many`).  A decision spends at most N simulations, so
         cap = N + 1 still holds them.  It combines with fast=True, `mcts_sampled` and `reuse_tree`: the decision and the rebase do not care
-        how the tree was grown.  The rules are in include/qgym.h and restated in tests/mctsmany_model.py.  The handles are of kinds of
-        their own (the kind's name + "-many"), so a K = 1 handle set is never reused with another leaf size.  `last_stats` gains "leaves"
-        (K), "rounds" (R) and "idle" ((live tree, descent) pairs that did not count: leaf < 0, a full tree; with `reuse_tree` "refused" is
-        the same number).  ValueError: mcts_leaves < 1 or > 64; mcts_leaves > 1 without num_mcts_searches >= 1; mcts_leaves >
+        how the tree was grown.  The rules are in include/qgym.h and restated in tests/mctsmany_model.py.  `last_stats` gains "leaves" (K),
+        "rounds" (R) and "idle" ((live tree, descent) pairs that did not count: leaf < 0, a full tree; with `reuse_tree` "refused" is the
+        same number).  ValueError: mcts_leaves < 1 or > 64; mcts_leaves > 1 without num_mcts_searches >= 1; mcts_leaves >
         num_mcts_searches; virtual_loss negative or not finite; virtual_loss != 0 with mcts_leaves = 1."""
         M = len(states)
         S = max(1, int(num_searches)) if mcts_sampled else 1
         self._check_options(M == 0, fast, beam_width, merge_duplicates, twists, twist_kernels, bound)
-        N = self._check_mcts(M * S, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
-                             mcts_sampled, reuse_tree, mcts_nodes, mcts_leaves, virtual_loss)
+        opts = self._check_mcts(M * S, num_mcts_searches, C, max_expand_depth, deterministic, S if mcts_sampled else None, reuse_tree, mcts_nodes,
+                                mcts_leaves, virtual_loss, dict(beam_width=beam_width is not None, merge_duplicates=merge_duplicates,
+                                                                bound=bound is not None, twists=twists is not None, twist_kernels=twist_kernels))
         if M == 0:
             return []
-        K = int(mcts_leaves)
-        if N and K > 1:  # the same searches in rounds of K leaves: a leaf batch of trees * K envs, handles of kinds of their own
-            B = M * S
-            kind = ("mcts-sampled" if mcts_sampled else "mcts") + ("-reuse" if reuse_tree else "") + "-many"
-            cap = (int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)) if reuse_tree else None
-            held = self._handles(kind, (B * K, B * cap, B * cap, B) if reuse_tree else (B * K, B * (N + 1), B))
-            return self._mcts_search(states, held, N, float(C), fast is True, S if mcts_sampled else None, cap, K, float(virtual_loss))
-        if N and reuse_tree:
-            B, cap = M * S, int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)
-            held = self._handles("mcts-sampled-reuse" if mcts_sampled else "mcts-reuse", (B, B * cap, B * cap, B))
-            return self._mcts_search(states, held, N, float(C), fast is True, S if mcts_sampled else None, cap)
-        if N and mcts_sampled:
-            B = M * S
-            return self._mcts_search(states, self._handles("mcts-sampled", (B, B * (N + 1), B)), N, float(C), fast is True, S)
-        if N:
-            return self._mcts_search(states, self._handles("mcts", (M, M * (N + 1), M)), N, float(C), fast is True)  # kernels: on request only
+        if opts is not None:
+            held = self._handles(opts.kind(), opts.batches(M * S))
+            return self._tree_search(states, held, opts, fast is True).solutions  # kernels: on request only
         views = None if twists is None else self._views(int(twists))
         if beam_width is None:
             return self._sampled_search(states, deterministic, num_searches, fast, views, twist_kernels)
@@ -789,7 +801,8 @@ class BatchedSynthesis:
         if states is not None and len(states) == 0:
             raise ValueError("self_play: no states")
         E = int(num_episodes) if states is None else len(states) * S
-        N = self._check_mcts(E, False, None, False, None, False, None, num_mcts_searches, C, 1, True, reuse_tree, mcts_nodes, mcts_leaves, virtual_loss)
+        opts = self._check_mcts(E, num_mcts_searches, C, searches=S, reuse_tree=reuse_tree, mcts_nodes=mcts_nodes, mcts_leaves=mcts_leaves,
+                                virtual_loss=virtual_loss)
         cfg = self.env.config
         n, A, T = int(cfg["num_qubits"]), len(cfg["gateset"]), int(cfg["max_depth"])
         kind = self.env.env_kind
@@ -804,23 +817,20 @@ class BatchedSynthesis:
         if nbytes > SELF_PLAY_MAX_LOG_BYTES:
             raise ValueError(f"self_play: the log of {T} decisions x {E} episodes and {cap_samples} samples takes up to {nbytes} bytes, more than the limit "
                              f"of {SELF_PLAY_MAX_LOG_BYTES}")
-        K = int(mcts_leaves)
-        tree_cap = (int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)) if reuse_tree else None
-        name = "self-play" + ("-reuse" if reuse_tree else "") + ("-many" if K > 1 else "")
-        held = self._handles(name, (E * K, E * tree_cap, E * tree_cap, E) if reuse_tree else (E * K, E * (N + 1), E))
+        held = self._handles(opts.kind("self-play"), opts.batches(E))
         real = held.vecs[-1]
         if held.log is None or held.log.shape != (T, E, A, cap_samples):
             held.log = None  # (the old buffers go first)
             held.log = _SelfPlayLog(T, E, A, real, cap_samples)
         rec = held.log
         rec.reset = None if states is not None else (real.difficulty if difficulty is None else int(difficulty), int(reset_seed))
-        self._mcts_search(states, held, N, float(C), fast is True, S, tree_cap, K, float(virtual_loss), rec=rec)
-        packed = rec.packed
+        res = self._tree_search(states, held, opts, fast is True, rec)
+        packed = res.packed
         n_samples, valid, bad = (int(x) for x in packed.n.tolist())  # the one host read of the collection
-        stats = dict(self.last_stats, episodes=E, episodes_solved=float(rec.success.sum()) / E, samples=n_samples, valid=valid, bad=bad)
+        stats = dict(res.stats, episodes=E, episodes_solved=float(res.success.sum()) / E, samples=n_samples, valid=valid, bad=bad)
         return SelfPlayBatch(n=n_samples, obs=packed.words[:n_samples], pi=packed.pi[:n_samples], z=packed.z[:n_samples], actions=packed.move[:n_samples],
-                             index=packed.index[:n_samples], returns=rec.returns, success=rec.success,
-                             lengths=rec.live[: rec.steps].sum(dim=0, dtype=torch.int32), stats=stats, obs_cols=real.obs_shape_[1])
+                             index=packed.index[:n_samples], returns=res.returns, success=res.success,
+                             lengths=rec.live[: res.steps].sum(dim=0, dtype=torch.int32), stats=stats, obs_cols=real.obs_shape_[1])
 
     def _check_options(self, empty: bool, fast, beam_width, merge_duplicates, twists, twist_kernels, bound):
         """ValueError for a combination of `solve`'s options that does not exist; what needs a handle's config (the metrics weights under `bound`)
@@ -853,53 +863,42 @@ class BatchedSynthesis:
                 raise ValueError("bound: a PauliGym step adds pauli_layer_reward per released rotation (pauli.rs:634), and a target may hold rotations "
                                  "beyond the observed columns: the reward still to come has no bound the search can see")
 
-    def _check_mcts(self, trees: int, deterministic, beam_width, merge_duplicates, twists, twist_kernels, bound, num_mcts_searches, C, max_expand_depth,
-                    mcts_sampled, reuse_tree=False, mcts_nodes=None, mcts_leaves=1, virtual_loss=0.0) -> int:
-        """`num_mcts_searches` as an int, after the ValueErrors of `solve`'s tree search on `trees` trees; 0: no tree search, and `C` and
-        `max_expand_depth` mean nothing."""
-        N = int(num_mcts_searches)
-        if N < 0:
-            raise ValueError("num_mcts_searches must be at least 0")
-        if mcts_sampled and N == 0:
-            raise ValueError("mcts_sampled=True needs num_mcts_searches >= 1: it draws the moves of a tree search")
-        if reuse_tree and N == 0:
-            raise ValueError("reuse_tree=True needs num_mcts_searches >= 1: it keeps the subtree of a tree search's move")
-        if mcts_nodes is not None and not reuse_tree:
-            raise ValueError("mcts_nodes needs reuse_tree=True: without it a tree holds the N + 1 nodes of one decision")
+    def _check_mcts(self, trees: int, num_mcts_searches, C, max_expand_depth=1, deterministic=False, searches: Optional[int] = None, reuse_tree=False,
+                    mcts_nodes=None, mcts_leaves=1, virtual_loss=0.0, conflicts: Optional[Dict[str, bool]] = None) -> Optional[_MctsOptions]:
+        """The tree search on `trees` trees these arguments resolve to, after its ValueErrors; None (N = 0): none, and `C` and `max_expand_depth` mean
+        nothing.  `searches`: S of `mcts_sampled`, else None.  `conflicts`: which of `solve`'s other options are on, by name -- it takes none."""
+        N, mcts_sampled = int(num_mcts_searches), searches is not None
         K, vl = int(mcts_leaves), float(virtual_loss)
-        if not 1 <= K <= MCTS_MAX_LEAVES:
-            raise ValueError(f"mcts_leaves must satisfy 1 <= mcts_leaves <= {MCTS_MAX_LEAVES}, got {K}")
-        if not (vl >= 0.0 and vl < float("inf")):
-            raise ValueError("virtual_loss must be finite and at least 0")
-        if K > 1 and N == 0:
-            raise ValueError("mcts_leaves > 1 needs num_mcts_searches >= 1: it is the leaf batch of a tree search")
-        if vl != 0.0 and K == 1:
-            raise ValueError("virtual_loss needs mcts_leaves > 1: one descent per launch leaves no virtual visits behind")
-        if K > N >= 1:
-            raise ValueError(f"mcts_leaves={K} is more than num_mcts_searches={N}: a decision makes at most N descents")
+        for bad, why in ((N < 0, "num_mcts_searches must be at least 0"),
+                         (mcts_sampled and N == 0, "mcts_sampled=True needs num_mcts_searches >= 1: it draws the moves of a tree search"),
+                         (reuse_tree and N == 0, "reuse_tree=True needs num_mcts_searches >= 1: it keeps the subtree of a tree search's move"),
+                         (mcts_nodes is not None and not reuse_tree, "mcts_nodes needs reuse_tree=True: without it a tree holds the N + 1 nodes of one decision"),
+                         (not 1 <= K <= MCTS_MAX_LEAVES, f"mcts_leaves must satisfy 1 <= mcts_leaves <= {MCTS_MAX_LEAVES}, got {K}"),
+                         (not (vl >= 0.0 and vl < float("inf")), "virtual_loss must be finite and at least 0"),
+                         (K > 1 and N == 0, "mcts_leaves > 1 needs num_mcts_searches >= 1: it is the leaf batch of a tree search"),
+                         (vl != 0.0 and K == 1, "virtual_loss needs mcts_leaves > 1: one descent per launch leaves no virtual visits behind"),
+                         (K > N >= 1, f"mcts_leaves={K} is more than num_mcts_searches={N}: a decision makes at most N descents")):
+            if bad:
+                raise ValueError(why)
         if N == 0:
-            return 0
-        if not float(C) > 0.0:
-            raise ValueError("C must be positive")
-        if int(max_expand_depth) != 1:
-            raise ValueError("max_expand_depth: only 1 is built (one new node per simulation)")
-        if mcts_sampled and deterministic:
-            raise ValueError("mcts_sampled=True draws its moves: it cannot be combined with deterministic=True")
-        if not mcts_sampled and not deterministic:
-            raise ValueError("num_mcts_searches needs deterministic=True, or mcts_sampled=True to draw the moves from the visit counts")
-        mixed = [name for name, on in (("beam_width", beam_width is not None), ("merge_duplicates", merge_duplicates), ("bound", bound is not None),
-                                       ("twists", twists is not None), ("twist_kernels", twist_kernels)) if on]
+            return None
+        for bad, why in ((not float(C) > 0.0, "C must be positive"),
+                         (int(max_expand_depth) != 1, "max_expand_depth: only 1 is built (one new node per simulation)"),
+                         (mcts_sampled and deterministic, "mcts_sampled=True draws its moves: it cannot be combined with deterministic=True"),
+                         (not (mcts_sampled or deterministic), "num_mcts_searches needs deterministic=True, or mcts_sampled=True to draw the moves from the visit counts")):
+            if bad:
+                raise ValueError(why)
+        mixed = [name for name, on in (conflicts or {}).items() if on]
         if mixed:
             raise ValueError(f"num_mcts_searches cannot be combined with {', '.join(mixed)}")
-        nodes = N + 1
-        if reuse_tree:
-            nodes = int(mcts_nodes) if mcts_nodes is not None else min(2 * N + 1, MCTS_MAX_CAP)
-            if not N + 1 <= nodes <= MCTS_MAX_CAP:
-                raise ValueError(f"mcts_nodes must satisfy num_mcts_searches + 1 = {N + 1} <= mcts_nodes <= {MCTS_MAX_CAP}, got {nodes}")
-        nbytes = int(_lib.load().qg_mcts_forest_bytes(trees, min(nodes, 2 ** 32 - 1), len(self.env.config["gateset"])))
+        cap = (int(mcts_nodes) if mcts_nodes is not None else _MctsOptions.default_cap(N)) if reuse_tree else None
+        if cap is not None and not N + 1 <= cap <= MCTS_MAX_CAP:
+            raise ValueError(f"mcts_nodes must satisfy num_mcts_searches + 1 = {N + 1} <= mcts_nodes <= {MCTS_MAX_CAP}, got {cap}")
+        opts = _MctsOptions(N, float(C), searches, cap, K, vl)
+        nbytes = int(_lib.load().qg_mcts_forest_bytes(trees, min(opts.nodes, 2 ** 32 - 1), len(self.env.config["gateset"])))
         if nbytes > MCTS_MAX_FOREST_BYTES:
             raise ValueError(f"num_mcts_searches={N}: the forest of {trees} trees takes {nbytes} bytes, more than the limit of {MCTS_MAX_FOREST_BYTES}")
-        return N
+        return opts
 
     def _sampled_search(self, states, deterministic: bool, num_searches: int, fast: Optional[bool], views: Optional[List[int]], twist_kernels: bool):
         """The sampled and the greedy search of `solve`: every (target, search) pair is one env of the "search" handle, one view per search;

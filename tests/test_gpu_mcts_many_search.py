@@ -178,13 +178,11 @@ def test_search_against_the_model_round_by_round(monkeypatch, call):
             expect_trees(rec["forest"], f, label)
             expanded += int(grown.sum())
             several += int((grown.reshape(B, K).sum(axis=1) >= 2).sum())
-        if sampled or reuse:  # the decision on its kernel; the plain deterministic search decides in torch, as it did
-            kind_, rec = next(events)
-            assert kind_ == "decide" and rec["sample"] is sampled and (not sampled or (rec["seed"] == seed and rec["counter"] == t))
-            np.testing.assert_array_equal(rec["finished"] != 0, model.finished, err_msg=f"decision {t}")
+        kind_, rec = next(events)  # the decision on its kernel, in every mode
+        assert kind_ == "decide" and rec["sample"] is sampled and (not sampled or (rec["seed"] == seed and rec["counter"] == t))
+        np.testing.assert_array_equal(rec["finished"] != 0, model.finished, err_msg=f"decision {t}")
         move = model.decide()  # ... and the model's rebase
-        if sampled or reuse:
-            np.testing.assert_array_equal(rec["move"], move, err_msg=f"decision {t}: the decision")
+        np.testing.assert_array_equal(rec["move"], move, err_msg=f"decision {t}: the decision")
         kind_, rec = next(events)
         assert kind_ == "move"
         np.testing.assert_array_equal(rec["actions"], move, err_msg=f"decision {t}: the real envs' moves")

@@ -69,7 +69,8 @@ def search_table(M: int, difficulty: int):
 
 
 def torch_decide(forest, finished, keys, parked):
-    """The lines of `BatchedSynthesis._mcts_search` that take the deterministic search's decision."""
+    """The tensor-library lines with which the plain deterministic search took its decision before every mode went to `mcts_decide`: kept
+    as the historical comparison."""
     A = forest.A
     child = forest.child[:, 0, :].to(torch.int64)
     visits = torch.gather(forest.visits.to(torch.int64), 1, child.clamp(min=0))
