@@ -8,14 +8,10 @@ import torch
 from mctsmodel import FIELDS, Forest, backup, check_invariants, root
 from mctsreuse_model import carried_child, rebase, select
 from mctssample_model import decide_most, decide_sampled
+from util import bits  # noqa: F401  (the device tests import it from here)
 
 C = 2 ** 0.5
 NODE_FIELDS = ("parent", "reward", "value", "visits", "wsum", "terminal", "child", "prior")
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({1: np.uint8, 4: np.uint32}[x.dtype.itemsize])
 
 
 class Data:

@@ -25,11 +25,11 @@ The rules, on top of those of the three models (include/qgym.h states them for t
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional
+from typing import List, Optional
 
 import numpy as np
 
-from mctsmodel import F32, Forest, MctsModel, best_action, scores
+from mctsmodel import F32, Forest, MctsModel, best_action, run_alone, scores  # noqa: F401  (`run_alone`: the one driver, for every model)
 from mctsreuse_model import _Reuse
 from mctssample_model import SampledMctsModel
 
@@ -231,24 +231,3 @@ class ManyReuseMctsModel(_Many, _Reuse, MctsModel):
 
 class ManyReuseSampledMctsModel(_Many, _Reuse, SampledMctsModel):
     """`ReuseSampledMctsModel` with `leaves=`, `virtual_loss=`."""
-
-
-def run_alone(model, evaluate: Callable, after_round: Optional[Callable] = None, after_decision: Optional[Callable] = None):
-    """The model as its own device (`mctsmodel.run_alone`, `mctsreuse_model.run_alone`).  `evaluate(envs) -> (logp f32 [len, A], values f32
-    [len])`, None entries get any row; `after_round(model)` after every backup, `after_decision(model, move)` after every decision."""
-    def priors(envs):
-        logp, values = evaluate(envs)
-        return np.exp(np.asarray(logp, dtype=F32)).astype(F32), np.asarray(values, dtype=F32)
-
-    while not model.ended:
-        if model.t == 0 or not isinstance(model, _Reuse):
-            model.start(*priors(model.roots()))
-        for _ in range(model.rounds):
-            model.select()
-            model.backup(*priors(model.expand()))
-            if after_round is not None:
-                after_round(model)
-        move = model.decide()
-        if after_decision is not None:
-            after_decision(model, move)
-    return model.result()

@@ -181,13 +181,17 @@ def check_invariants(f: Forest, sims: Optional[Sequence[int]] = None):
 
 
 class MctsModel:
-    """The whole search on oracle envs.  Driven step by step -- `start`, then N times `select` / `expand` / `backup`, then `decide` -- with
-    the policy's numbers handed in, so a device's own can be used; `run_alone` drives it with a function."""
+    """The whole search on oracle envs.  Driven step by step -- `start`, then `rounds` times `select` / `expand` / `backup`, then `decide`
+    -- with the policy's numbers handed in, so a device's own can be used; `run_alone` drives it with a function.  Here a round is one
+    descent per tree (K = 1, no virtual loss) and the trees are rebuilt for every decision; the mix-ins of mctsmany_model and
+    mctsreuse_model change either."""
+    carries = False  # True: the chosen move's subtree is kept between decisions, so `start` is for decision 0 only
 
     def __init__(self, targets: Sequence, N: int, A: int, max_depth: int, C: float = 2 ** 0.5):
         self.real = [t.clone() for t in targets]  # track_solution on
         self.M, self.N, self.A, self.T, self.C = len(self.real), int(N), int(A), int(max_depth), float(C)
         self.finished = np.array([env.success() for env in self.real], dtype=bool)
+        self.K, self.vl, self.rounds = 1, 0.0, self.N
         self.forest = Forest(self.M, self.N, self.A)
         self.pool: List[dict] = [{} for _ in range(self.M)]  # per tree: node -> env
         self.t = 0
@@ -195,6 +199,10 @@ class MctsModel:
         self.moves: List[np.ndarray] = []
         self.node_counts: List[int] = []
         self.picked = self.fresh = None
+
+    def k_of(self, r: int) -> int:
+        """The descents per tree of round r."""
+        return 1
 
     def roots(self) -> list:
         """The envs the policy is asked about at the start of a decision: the real ones."""
@@ -258,19 +266,24 @@ class MctsModel:
         return sols, stats
 
 
-def run_alone(model: MctsModel, evaluate: Callable, after_simulation: Optional[Callable] = None):
-    """The model as its own device.  `evaluate(envs) -> (logp f32 [k, A], values f32 [k])` for a list of oracle envs (None entries get any
-    row); `after_simulation(model)` is called after every backup."""
+def run_alone(model: MctsModel, evaluate: Callable, after_simulation: Optional[Callable] = None, after_decision: Optional[Callable] = None):
+    """The model as its own device, whichever of the family.  `evaluate(envs) -> (logp f32 [len, A], values f32 [len])` for a list of oracle
+    envs (None entries get any row); a model with carried trees is asked about its roots at decision 0 only.  `after_simulation(model)` is
+    called after every backup -- every round, where a round makes several descents -- and `after_decision(model, move)` after every
+    decision and its rebase."""
     def priors(envs):
         logp, values = evaluate(envs)
         return np.exp(np.asarray(logp, dtype=F32)).astype(F32), np.asarray(values, dtype=F32)
 
     while not model.ended:
-        model.start(*priors(model.roots()))
-        for _ in range(model.N):
+        if model.t == 0 or not model.carries:
+            model.start(*priors(model.roots()))
+        for _ in range(model.rounds):
             model.select()
             model.backup(*priors(model.expand()))
             if after_simulation is not None:
                 after_simulation(model)
-        model.decide()
+        move = model.decide()
+        if after_decision is not None:
+            after_decision(model, move)
     return model.result()

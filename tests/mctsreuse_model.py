@@ -25,11 +25,11 @@ The rules, on top of those of mctsmodel and mctssample_model.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional
+from typing import List, Optional
 
 import numpy as np
 
-from mctsmodel import F32, Forest, MctsModel, best_action, scores
+from mctsmodel import F32, Forest, MctsModel, best_action, run_alone, scores  # noqa: F401  (`run_alone`: the one driver, for every model)
 from mctssample_model import SampledMctsModel
 
 MAX_CAP = 8192
@@ -133,6 +133,7 @@ def rebase(f: Forest, move, finished=None) -> np.ndarray:
 
 class _Reuse:
     """What both searches share; in front of `MctsModel` / `SampledMctsModel` in the bases."""
+    carries = True
 
     def __init__(self, *args, cap: Optional[int] = None, **kw):
         super().__init__(*args, **kw)
@@ -180,24 +181,3 @@ class ReuseMctsModel(_Reuse, MctsModel):
 
 class ReuseSampledMctsModel(_Reuse, SampledMctsModel):
     """`SampledMctsModel(targets, S, N, A, max_depth, seed, C)` with `cap=`: the sampled search, trees carried."""
-
-
-def run_alone(model, evaluate: Callable, after_simulation: Optional[Callable] = None, after_decision: Optional[Callable] = None):
-    """`mctsmodel.run_alone` for a reuse model: the policy is asked about the roots at decision 0 only.  `after_decision(model, move)` is
-    called after every decision's rebase."""
-    def priors(envs):
-        logp, values = evaluate(envs)
-        return np.exp(np.asarray(logp, dtype=F32)).astype(F32), np.asarray(values, dtype=F32)
-
-    while not model.ended:
-        if model.t == 0:
-            model.start(*priors(model.roots()))
-        for _ in range(model.N):
-            model.select()
-            model.backup(*priors(model.expand()))
-            if after_simulation is not None:
-                after_simulation(model)
-        move = model.decide()
-        if after_decision is not None:
-            after_decision(model, move)
-    return model.result()

@@ -6,12 +6,9 @@ import re
 import numpy as np
 
 from azmodel import F32, pack, returns_to_go
+from util import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
 
 
 def random_log(rng, T, E, A, monotone=True, p_zero=0.1, p_bad=0.0):

@@ -1,9 +1,9 @@
 """`BatchedSynthesis.self_play` against `SelfPlayModel` (tests/azmodel.py): the sampled tree search of tests/mctssample_model.py with every
 decision logged and the log packed into training samples.
 
-As in tests/test_gpu_mcts_sampled.py the model is driven with the device's own rows and values: stand-ins on `synthesis.mcts_select`,
-`synthesis.mcts_backup` and `synthesis.mcts_decide` (written again here, for `self_play`) call the real function and keep what it read and
-wrote, a stand-in on `VecEnv.step` the actions every handle was given.  The model makes the same search on oracle envs; every draw, every
+As in tests/test_gpu_mcts_sampled.py the model is driven with the device's own rows and values: the recorder of tests/mctsrecord.py puts
+stand-ins on the tree calls of `synthesis`, which call the real function and keep what it read and wrote, and on `VecEnv.step`, which keeps
+the actions every handle was given; its replay walks the log against the model.  The model makes the same search on oracle envs; every draw, every
 sample's index, action, pi and z (by bit pattern), the expanded observation against the oracle env's at that decision, the returns, the
 success flags, the lengths and the stats must be the device's.  For `reuse_tree` and `mcts_leaves` the forest is not verified again (their own
 tests do that): the oracle envs replay the decisions from the rows of counts the device's decision wrote."""
@@ -13,13 +13,12 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-from azmodel import F32, SelfPlayModel, pack  # noqa: E402
-from mctsmodel import FIELDS  # noqa: E402
-from mctssample_model import MASK64, STREAM, counts, draw_from  # noqa: E402
-from test_gpu_mcts import CASES, expect_forest, golden_case  # noqa: E402
-from test_gpu_mcts_kernels import bits  # noqa: E402
+from azmodel import F32, pack  # noqa: E402
+from mctsrecord import Draws, model_for, record, replay  # noqa: E402
+from mctssample_model import MASK64, STREAM, draw_from  # noqa: E402
+from test_gpu_mcts import CASES, golden_case  # noqa: E402
 from test_gpu_sampled_search import oracle_targets  # noqa: E402
-from util import rng_draw  # noqa: E402
+from util import bits, rng_draw  # noqa: E402
 
 CALLS = [(case, 3, 4, None) for case in CASES] + [("clifford-3q", 3, 16, True)]
 SEARCH_STATS = {"mcts", "searches", "targets", "steps", "solved", "searches_solved", "mean_gates", "nodes", "kernels"}
@@ -29,57 +28,6 @@ OWN_STATS = {"episodes", "episodes_solved", "samples", "valid", "bad"}
 def call_id(call):
     case, S, N, fast = call
     return f"{case}-S={S}-N={N}" + ("-fast" if fast else "")
-
-
-def recorded_self_play(monkeypatch, syn, **kw):
-    """`syn.self_play(**kw)` with the stand-ins in place.  Returns (the batch, the calls in order -- ("root" | "select" | "backup" | "decide" |
-    "move", what the call read and wrote, as numpy copies))."""
-    from qiskit_gym_amd import synthesis
-    from qiskit_gym_amd.vec import VecEnv
-
-    log, steps = [], []
-    real_select, real_backup, real_decide, real_step = synthesis.mcts_select, synthesis.mcts_backup, synthesis.mcts_decide, VecEnv.step
-
-    def cpu(t):
-        return None if t is None else t.cpu().numpy().copy()
-
-    def snapshot(forest):
-        return {name: cpu(getattr(forest, name)) for name in FIELDS}
-
-    def select(forest, C, finished=None, *out):
-        res = real_select(forest, C, finished, *out)
-        log.append(("select", dict(C=C, finished=cpu(finished), picked=[cpu(t) for t in res])))
-        return res
-
-    def backup(forest, logp, values, reward=None, done=None, src=None, dst=None, act=None, leaf=None, root=False):
-        res = real_backup(forest, logp, values, reward, done, src, dst, act, leaf, root)
-        log.append(("root" if root else "backup", dict(logp=cpu(logp), values=cpu(values), reward=cpu(reward), done=cpu(done),
-                                                       picked=[cpu(t) for t in (src, dst, act, leaf)], forest=snapshot(forest))))
-        return res
-
-    def decide(forest, sample=False, seed=0, counter=0, finished=None, move=None, counts=None):
-        assert counts is not None, "self_play asks every decision for its rows of counts"
-        res = real_decide(forest, sample, seed, counter, finished, move, counts)
-        log.append(("decide", dict(sample=sample, seed=seed, counter=counter, finished=cpu(finished), move=cpu(res), counts=cpu(counts))))
-        return res
-
-    def step(self, actions, coins=None):
-        steps.append((self, len(log), cpu(actions).astype(np.int64)))
-        return real_step(self, actions, coins)
-
-    with monkeypatch.context() as m:
-        m.setattr(synthesis, "mcts_select", select)
-        m.setattr(synthesis, "mcts_backup", backup)
-        m.setattr(synthesis, "mcts_decide", decide)
-        m.setattr(VecEnv, "step", step)
-        batch = syn.self_play(**kw)
-    real = [h for k, h in syn._held.items() if k.startswith("self-play")][0].vecs[-1]
-    moves = 0
-    for v, at, actions in steps:
-        if v is real:
-            log.insert(at + moves, ("move", dict(actions=actions)))
-            moves += 1
-    return batch, log
 
 
 def expect_samples(batch, want, observation, label):
@@ -106,52 +54,18 @@ def test_self_play_against_the_model_decision_by_decision(monkeypatch, call):
     gym, policy, states, raw = CASES[case]()
     seed = 1
     syn = BatchedSynthesis(gym, policy, seed=seed)
-    batch, log = recorded_self_play(monkeypatch, syn, states=states, episodes_per_state=S, num_mcts_searches=N, fast=fast)
+    got = record(monkeypatch, syn, lambda syn: syn.self_play(states=states, episodes_per_state=S, num_mcts_searches=N, fast=fast))
+    batch = got.out
     stats = batch.stats
     A, T, M = len(gym.config["gateset"]), gym.config["max_depth"], len(states)
     B = M * S
-    assert set(syn._held) == {"self-play"} and syn._held["self-play"].key == (B, B * (N + 1), B, False)
+    assert set(syn._held) == {got.kind} == {"self-play"} and got.held.key == (B, B * (N + 1), B, False)
     assert set(stats) == SEARCH_STATS | OWN_STATS and stats["kernels"] is bool(fast) and stats["mcts"] == N and stats["episodes"] == B
-    assert {k: stats[k] for k in SEARCH_STATS} == syn.last_stats
-    model = SelfPlayModel(oracle_targets(gym, states, raw), S, N, A, T, seed=seed)
-    f = model.forest
-    events = iter(log)
-    off_top = 0
-    for t in range(stats["steps"]):
-        assert not model.ended, f"the search went on after decision {t}"
-        kind_, rec = next(events)
-        assert kind_ == "root"
-        np.testing.assert_array_equal(rec["done"] != 0, model.finished, err_msg=f"decision {t}: which real envs are final")
-        model.start(rec["forest"]["prior"][:, 0, :], rec["values"])
-        expect_forest(rec["forest"], f, f"decision {t}: root")
-        for s in range(N):
-            label = f"decision {t} simulation {s}"
-            kind_, rec = next(events)
-            assert kind_ == "select"
-            src, dst, act, leaf = model.select()
-            for name, g, w in zip(("src", "dst", "act", "leaf"), rec["picked"], (src, dst, act, leaf)):
-                np.testing.assert_array_equal(g, w, err_msg=f"{label}: {name}")
-            model.expand()
-            kind_, rec = next(events)
-            assert kind_ == "backup"
-            prior = np.zeros((B, A), dtype=np.float32)
-            for m in np.nonzero(act < A)[0]:
-                prior[m] = rec["forest"]["prior"][m, leaf[m]]
-            model.backup(prior, rec["values"])
-            expect_forest(rec["forest"], f, label)
-        kind_, rec = next(events)
-        assert kind_ == "decide" and rec["sample"] is True and rec["seed"] == seed and rec["counter"] == t
-        np.testing.assert_array_equal(rec["finished"] != 0, model.finished, err_msg=f"decision {t}")
-        live = ~model.finished
-        n_a = counts(f)
-        np.testing.assert_array_equal(rec["counts"][:, :A], n_a, err_msg=f"decision {t}: the rows of counts")
-        draw = model.decide()
-        np.testing.assert_array_equal(rec["move"], draw, err_msg=f"decision {t}: the draws")
-        off_top += int((n_a[np.arange(B), np.minimum(draw, A - 1)] < n_a.max(axis=1))[live].sum())
-        kind_, rec = next(events)
-        assert kind_ == "move"
-        np.testing.assert_array_equal(rec["actions"], draw, err_msg=f"decision {t}: the real envs' moves")
-    assert model.ended and next(events, None) is None, f"the search stopped after {stats['steps']} decisions, the model goes on"
+    assert {k: stats[k] for k in SEARCH_STATS} == syn.last_stats == got.stats
+    model = model_for(oracle_targets(gym, states, raw), S=S, N=N, A=A, T=T, seed=seed, self_play=True)
+    draws = Draws(rows=True)  # the decision's rows of counts against the model's forest, the draws off the top
+    replay(got.log, model, seed=seed, on_decide=draws)
+    off_top = draws.off_top
     _, want_stats = model.result()
     for key in want_stats:
         assert stats[key] == want_stats[key], key
@@ -182,9 +96,9 @@ def test_carried_trees_and_several_leaves_log_the_same_way(monkeypatch, extra):
     S, N, seed = 2, 4, 3
     A, T, B = len(gym.config["gateset"]), gym.config["max_depth"], len(states) * S
     syn = BatchedSynthesis(gym, policy, seed=seed)
-    batch, log = recorded_self_play(monkeypatch, syn, states=states, episodes_per_state=S, num_mcts_searches=N, **extra)
-    kind = "self-play-reuse" if "reuse_tree" in extra else "self-play-many"
-    assert set(syn._held) == {kind}
+    got = record(monkeypatch, syn, lambda syn: syn.self_play(states=states, episodes_per_state=S, num_mcts_searches=N, **extra))
+    batch, log = got.out, got.log
+    assert set(syn._held) == {got.kind} == {"self-play-reuse" if "reuse_tree" in extra else "self-play-many"}
     envs = [e for e in oracle_targets(gym, states, raw) for _ in range(S)]
     envs = [e.clone() for e in envs]
     finished = np.array([e.success() for e in envs])
@@ -195,6 +109,7 @@ def test_carried_trees_and_several_leaves_log_the_same_way(monkeypatch, extra):
     assert len(decisions) == len(real_moves) == batch.stats["steps"]
     for t, (rec, mv) in enumerate(zip(decisions, real_moves)):
         assert rec["sample"] is True and rec["seed"] == seed and rec["counter"] == t
+        assert rec["counts"] is not None, "self_play asks every decision for its rows of counts"
         np.testing.assert_array_equal(rec["finished"] != 0, finished, err_msg=f"decision {t}")
         draws = rng_draw((seed ^ STREAM) & MASK64, np.arange(B, dtype=np.uint64), t)
         want = np.array([A if finished[e] else draw_from(rec["counts"][e, :A], int(draws[e])) for e in range(B)], dtype=np.int32)

@@ -13,14 +13,10 @@ from mctsreuse_model import ReuseMctsModel, ReuseSampledMctsModel, carried_child
 from oracle import OracleEnv
 from test_mctsmodel import handmade, target_envs
 from test_reference_policies import MODELS, load
+from util import bits
 
 C = 2 ** 0.5
 NODE_FIELDS = ("parent", "reward", "value", "visits", "wsum", "terminal", "child", "prior")
-
-
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view({1: np.uint8, 4: np.uint32}[x.dtype.itemsize])
 
 
 def same(a, b):

@@ -55,6 +55,12 @@ def set_difficulty(ov, gv, d: int):
     assert gv.difficulty == d
 
 
+def bits(x) -> np.ndarray:
+    """The bit patterns of an array of 1- or 4-byte elements."""
+    x = np.ascontiguousarray(x)
+    return x.view({1: np.uint8, 4: np.uint32}[x.dtype.itemsize])
+
+
 def f32_bits(x) -> np.ndarray:
     return np.asarray(x, dtype=np.float32).view(np.uint32)
 
